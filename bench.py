@@ -15,9 +15,16 @@ torch.distributed.run when it was not launched by it; every rank owns its own cl
 collective); the timed region is bracketed by barrier + synchronize and the MAX over ranks is reported.  --gather also
 times the optional consolidation of the per-rank outputs on rank 0 (RCCL send/recv over xGMI), reported separately.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
-  roofline     algorithmic bytes (640 B PCM in + 4*n_mels B out per frame) / kernel time vs 8 TB/s
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  A plain run sets up, warms up,
+times exactly --steps steps, writes its outputs if --dump-outputs is given and prints the line: its `roofline` comes from the same
+timed steps (`traffic`: the committed profiles/traffic.json).  --full adds everything else, each in runs of its own outside the timed steps:
+  parity       a spot check of three clips against the C oracle
+  value_ci     five more event-timed windows; roofline.kernel_ms from an event pair around the dominant kernel alone
+  roofline     traffic re-measured with rocprofv3 --pmc (unless --no-traffic)
   cpu_baseline the C oracle (a port of Spectrogram::compute_mel_spectrogram_cpu) on the host cores
+  the legs next to `value` (N = 1: speech, cfg3, cfg4, f64, ...; N > 1: config 5), the PCIe-inclusive host API figures
+--dump-outputs DIR: DIR/mel.npy, float32 [clips][frames][n_mels], a fixed seeded sample of whole clips (at most 32 MiB) of what the
+last timed step wrote; the inputs are synthetic and the same from run to run, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -71,6 +78,9 @@ def parse_args():
                                                                "run is not the first RCCL run (the line then carries `dist`)")
     ap.add_argument("--dry-run", action="store_true", help="no GPU: spawn the ranks (gloo), plan every rank's shard, run the timing protocol on a "
                                                             "sleep and print the JSON line -- the CPU test of the launch path")
+    ap.add_argument("--full", action="store_true", help="also run every check and figure beyond the timed steps (parity, value_ci, the dominant kernel "
+                                                         "alone, traffic, cpu_baseline, the extra legs, host API); the --no-* options above prune it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write a fixed seeded sample of the last timed step's output to DIR/mel.npy (float32)")
     return ap.parse_args()
 
 
@@ -197,14 +207,14 @@ def dry_run(args) -> None:
                 "residency": [{"rank": r, "pcm_bytes": int(t[2]), "mel_bytes": int(t[3]), "guard_list_bytes": int(t[4]), "total_GB": float(int(t[2]) + int(t[3]) + int(t[4])) / 1e9}
                               for r, t in enumerate(allr)],
                 "hbm_per_gpu_GB": 288.0}
-        if world > 1 and not args.explicit_config and not args.no_cfg5:        # the extra leg of a plain `bench.py --gpus N`
+        if args.full and world > 1 and not args.explicit_config and not args.no_cfg5:        # the extra leg of `bench.py --gpus N --full`
             fpc5 = (CONFIGS[5][1] * int(SR) - N_FFT) // HOP + 1
             sh5 = [list(shard_range(CONFIGS[5][0], r, world)) for r in range(world)]
             line["cfg5"] = {"scaling": "strong", "shards": sh5, "per_rank_frames": [(b - a) * fpc5 for a, b in sh5]}
-        if world == 1 and args.config == 2 and not args.no_speech:
+        if args.full and world == 1 and args.config == 2 and not args.no_speech:
             line["speech"] = {"input": "tests/golden/jfk_f32le.wav tiled to the config-2 batch"}
             line["speech128"] = {"input": "the same through the 128-mel bank (Whisper large-v3)"}
-        if world == 1 and args.config == 2 and not args.no_legs:
+        if args.full and world == 1 and args.config == 2 and not args.no_legs:
             line["legs"] = list(LEG_NAMES) + ["host_api_single_clip_ms"]
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -264,12 +274,13 @@ def run_workload(args, config: int, primary: bool, steps: int, warmup: int, M, t
                 k = fill(s)
                 mel.compute_uniform_device(pcm.data_ptr(), clip_len, clip_len, k, out.data_ptr(), stream=stream)
 
-    # parity spot check first (3 clips vs the oracle), so that nothing CPU-bound sits between the spin-up and
+    # --full: parity spot check first (3 clips vs the oracle), so that nothing CPU-bound sits between the spin-up and
     # the timed region: the GPU drops back to its idle clocks within milliseconds of an empty queue
-    mel.compute_uniform_device(pcm.data_ptr(), clip_len, clip_len, k0, out.data_ptr(), stream=stream)
-    torch.cuda.synchronize()
     parity, queued = None, None
-    if rank == 0:
+    if args.full:
+        mel.compute_uniform_device(pcm.data_ptr(), clip_len, clip_len, k0, out.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+    if args.full and rank == 0:
         from oracle import oracle as O
         worst = 0.0
         o3 = out[: k0 * fpc * n_mels].view(k0, fpc, n_mels)
@@ -310,10 +321,15 @@ def run_workload(args, config: int, primary: bool, steps: int, warmup: int, M, t
 
     elapsed = timed_steps(timed_step, torch.cuda.synchronize, steps, 0, dist if distributed else None, red_dev)
     my_kernel_ms = ev0.elapsed_time(ev1) / steps      # HIP events on the launch stream: a whole step (AUTO: the f32 kernel + the gated f64 launch)
-    # dispersion of the figure: five more windows of the same K steps (at most 200), event-timed back to back behind the
-    # timed region; `value` stays what the contract says (the K steps above), `value_ci` says how far a window of that length moves
+    # --dump-outputs: the sample is copied on the launch stream now, before anything else writes `out`; it reaches the host after the line's figures
+    sample = None
+    if primary and args.dump_outputs and rank == 0:
+        k_last = n_clips - (sub - 1) * sub_clips          # clips of the last pass over the buffer (all of them when sub == 1)
+        sample = output_sample(torch, out, k_last, fpc, n_mels, first_clip + (sub - 1) * sub_clips)
+    # --full: dispersion of the figure: five more windows of the same K steps (at most 200), event-timed back to back behind
+    # the timed region; `value` stays what the contract says (the K steps above), `value_ci` says how far a window of that length moves
     windows = []
-    if primary:
+    if primary and args.full:
         wsteps = max(1, min(steps, 200))
         for _ in range(5):
             w0, w1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -325,7 +341,7 @@ def run_workload(args, config: int, primary: bool, steps: int, warmup: int, M, t
     # the dominant kernel on its own: an event pair around the first kernel of each of 200 more calls (melspec_time_first_kernel), the
     # figure a kernel trace reports -- `roofline.achieved` is quoted on it; the step time above stays what `value` is made of
     first_ms = None
-    if primary and sub == 1 and args.precision != "f64":
+    if primary and args.full and sub == 1 and args.precision != "f64":
         torch.cuda.synchronize()
         first_ms = mel.time_first_kernel(pcm.data_ptr(), clip_len, clip_len, n_clips, out.data_ptr(), warmup=20, iters=200)
     kernel_ms = my_kernel_ms
@@ -340,8 +356,33 @@ def run_workload(args, config: int, primary: bool, steps: int, warmup: int, M, t
     mel_name = mel.plain_kernel_name()
     res = dict(elapsed=elapsed, per_rank=per_rank, kernel_ms=kernel_ms, frames_per_step=frames_per_step, n_clips=n_clips, sub=sub,
                parity=parity, queued=queued, spinup_steps=spinup_steps, scaling=scaling, n_mels=n_mels, clip_seconds=clip_seconds,
-               clip_len=clip_len, total_or_per=total_or_per, fpc=fpc, kernel=mel_name, mel=mel, out=out, pcm=pcm, stream=stream, first_ms=first_ms, windows=windows)
+               clip_len=clip_len, total_or_per=total_or_per, fpc=fpc, kernel=mel_name, mel=mel, out=out, pcm=pcm, stream=stream, first_ms=first_ms, windows=windows,
+               sample=sample)
     return res
+
+
+DUMP_BYTES = 32 << 20       # --dump-outputs: at most this much of the output (the 1024 x 10 s step writes 327 MB)
+
+
+def output_sample(torch, out, n_clips: int, fpc: int, n_mels: int, first_clip: int) -> dict:
+    """A fixed sample of the mel rows in `out` ([n_clips][fpc][n_mels]): whole clips drawn with seed 0, in clip order, each cut to its first
+    frames only if one clip alone exceeds DUMP_BYTES.  The copy is queued on the current stream; `mel` is still on the device."""
+    import numpy as np
+    n = max(1, min(n_clips, DUMP_BYTES // (fpc * n_mels * 4)))
+    frames = min(fpc, DUMP_BYTES // (n_mels * 4))
+    idx = np.sort(np.random.default_rng(0).choice(n_clips, n, replace=False))
+    rows = out[: n_clips * fpc * n_mels].view(n_clips, fpc, n_mels).index_select(0, torch.from_numpy(idx).to(out.device))[:, :frames].clone()
+    return {"mel": rows, "clips": [first_clip + int(c) for c in idx]}
+
+
+def write_outputs(path: str, sample: dict) -> dict:
+    """--dump-outputs: DIR/mel.npy (float32); returns what the line says about it."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    mel = sample["mel"].cpu().numpy().astype(np.float32)
+    np.save(os.path.join(path, "mel.npy"), mel)
+    return {"dir": path, "files": {"mel.npy": list(mel.shape)}, "clips": sample["clips"],
+            "note": f"the last timed step's output: {mel.shape[0]} whole clips drawn with seed 0 (their first {mel.shape[1]} frames), float32"}
 
 
 def speech_leg(M, torch, dev, stream, n_clips: int, clip_len: int, n_mels: int) -> dict:
@@ -733,7 +774,7 @@ def main() -> None:
     elapsed, per_rank, kernel_ms, frames_per_step = w["elapsed"], w["per_rank"], w["kernel_ms"], w["frames_per_step"]
     n_clips, sub, parity, queued, spinup_steps, scaling = w["n_clips"], w["sub"], w["parity"], w["queued"], w["spinup_steps"], w["scaling"]
     n_mels, clip_seconds, clip_len, total_or_per, fpc = w["n_mels"], w["clip_seconds"], w["clip_len"], w["total_or_per"], w["fpc"]
-    mel, out, stream = w["mel"], w["out"], w["stream"]
+    mel, out, stream, sample = w["mel"], w["out"], w["stream"], w["sample"]
 
     # which device every rank ran on: an N-GPU line must show N distinct devices
     props = torch.cuda.get_device_properties(dev)
@@ -771,7 +812,7 @@ def main() -> None:
             gather = {"seconds": gdt, "gigabytes_into_rank0": gb, "GB_per_s": gb / gdt, "note": "RCCL send/recv, not part of `value`"}
 
     host_io = None
-    if not args.no_host_io and rank == 0 and world == 1:          # like cpu_baseline: at N = 1 only
+    if args.full and not args.no_host_io and rank == 0 and world == 1:          # like cpu_baseline: at N = 1 only
         from oracle import oracle as O
         # 64 host clips per call through melspec_compute_batch_host, caller-owned buffers reused from call to call (a fresh numpy
         # output per call measures the page faults of its first touch instead): pageable, then pinned (melspec_host_alloc)
@@ -801,7 +842,7 @@ def main() -> None:
 
     # the real-input leg (N = 1, the default workload) and, for N > 1 without --config, north_star's 65 536 x 30 s per-clip split
     speech = speech128 = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_speech and args.precision == "auto" and args.n_mels is None:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_speech and args.precision == "auto" and args.n_mels is None:
         def leg_or_error(fn):           # like the extra legs: a failing leg costs its own entry, never the line
             try:
                 return fn()
@@ -813,7 +854,7 @@ def main() -> None:
         # the same real input through Whisper large-v3's bank (configs[3]'s 128 mels, on the config-2 batch): the kernel real large-v3 input runs on
         speech128 = leg_or_error(lambda: speech_leg(M, torch, dev, stream, n_clips, clip_len, 128))
     legs = None
-    if rank == 0 and world == 1 and args.config == 2 and not args.no_legs and args.precision == "auto" and args.n_mels is None and args.clips is None and args.clip_seconds is None:
+    if args.full and rank == 0 and world == 1 and args.config == 2 and not args.no_legs and args.precision == "auto" and args.n_mels is None and args.clips is None and args.clip_seconds is None:
         try:
             legs = extra_legs(M, torch, dev, stream)
         except BaseException as e:              # its own set-up (the shared PCM buffer) failed: every leg is lost, the line is not
@@ -821,7 +862,7 @@ def main() -> None:
                 raise
             legs = {k: {"error": f"{type(e).__name__}: {e}"[:400]} for k in LEG_NAMES}
     cfg5 = None
-    if world > 1 and not explicit_config and not args.no_cfg5:
+    if args.full and world > 1 and not explicit_config and not args.no_cfg5:
         kernel_name = mel.plain_kernel_name()
         mel.close()
         del w, out
@@ -860,7 +901,7 @@ def main() -> None:
                                       "2 x FETCH_SIZE + WRITE_SIZE per launch; not re-measured in this run")
             except Exception:
                 traffic = None
-        if not args.no_traffic and world == 1 and args.config == 2 and traffic_kernel_ok:
+        if args.full and not args.no_traffic and world == 1 and args.config == 2 and traffic_kernel_ok:
             live, note = measure_traffic(args.config)
             if live is not None:
                 traffic, traffic_source = live, note
@@ -928,10 +969,12 @@ def main() -> None:
             res["dist"] = dict(dist_info, distinct_devices=len({(i or {}).get("uuid") or (i or {}).get("device_index") for i in idents}))
         if args.one_device:
             res["rehearsal"] = "every rank on GPU 0 over gloo: exercises the N > 1 code path on a 1-GPU box, the figures are not measurements"
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(clip_len, n_mels, args.cpu_seconds, 1024)
             res["cpu_baseline"] = cb
             res["realtime_x_vs_cpu"] = value / cb["value"]
+        if sample is not None:
+            res["dump_outputs"] = write_outputs(args.dump_outputs, sample)
         print(json.dumps(res), flush=True)
 
     if mel is not None:

@@ -248,10 +248,10 @@ def test_bench_spawns_its_ranks(gpus, config):
     assert line["max_over_ranks_s"] >= 0.002 * gpus * 3 * 0.9
 
 
-def test_plain_bench_line_carries_the_speech_leg_and_config5():
-    """What the driver runs: `bench.py` (N = 1) carries the real-input leg next to `value`; `bench.py --gpus N` without --config
-    also times north_star's 65 536 x 30 s per-clip split (configs[4]) whose per-rank frames sum to 196 476 928.  --dry-run: the
-    plan of both records without a GPU."""
+def test_full_bench_line_carries_the_speech_leg_and_config5():
+    """`bench.py --full` (N = 1) carries the real-input leg next to `value`; `bench.py --gpus N --full` without --config also times
+    north_star's 65 536 x 30 s per-clip split (configs[4]) whose per-rank frames sum to 196 476 928.  A plain run carries neither: it
+    times the steps of `value` and nothing else.  --dry-run: the plan of both records without a GPU."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
 
@@ -260,16 +260,18 @@ def test_plain_bench_line_carries_the_speech_leg_and_config5():
         assert p.returncode == 0, p.stderr[-2000:]
         return json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
 
-    one = run()
+    one = run("--full")
     assert one["n_gpus"] == 1 and one["config"] == 2 and "speech" in one and "cfg5" not in one
-    # the legs the driver's plain N = 1 run carries next to `value`
-    assert one["legs"] == ["cfg3", "cfg3_split", "cfg4", "f64", "mel_major", "w512", "nemo", "nemo_f32", "host_api_single_clip_ms"] and "legs" not in run("--no-legs")
-    two = run("--gpus", "2")
+    # the legs the N = 1 --full run carries next to `value`
+    assert one["legs"] == ["cfg3", "cfg3_split", "cfg4", "f64", "mel_major", "w512", "nemo", "nemo_f32", "host_api_single_clip_ms"] and "legs" not in run("--full", "--no-legs")
+    two = run("--gpus", "2", "--full")
     assert two["n_gpus"] == 2 and two["config"] == 2 and two["scaling"] == "weak" and two["shards"] == [[0, 1024], [1024, 2048]]
     c5 = two["cfg5"]
     assert c5["scaling"] == "strong" and c5["shards"][0][0] == 0 and c5["shards"][-1][1] == 65536
     assert sum(c5["per_rank_frames"]) == 196476928
-    assert "cfg5" not in run("--gpus", "2", "--config", "2")
+    assert "cfg5" not in run("--gpus", "2", "--config", "2", "--full")
+    plain, plain2 = run(), run("--gpus", "2")
+    assert plain["n_gpus"] == 1 and not {"speech", "speech128", "legs", "cfg5"} & set(plain) and "cfg5" not in plain2
 
 
 def test_a_failing_leg_costs_its_entry_not_the_line():
@@ -293,6 +295,56 @@ def test_a_failing_leg_costs_its_entry_not_the_line():
     assert set(legs) == set(bench.LEG_NAMES) | {"host_api_single_clip_ms"}
     for name, rec in legs.items():
         assert set(rec) == {"error"} and "no device in this test" in rec["error"], (name, rec)
+
+
+def test_dump_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: the same whole clips every time (seed 0, in clip order), at most DUMP_BYTES, one clip cut to its first frames only
+    when it alone is larger; written as float32."""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    n, fpc, n_mels = 50, 7, 3
+    out = torch.arange(n * fpc * n_mels + 11, dtype=torch.float32)           # a buffer longer than the step's output, like a sub-shard's
+    monkeypatch.setattr(bench, "DUMP_BYTES", 10 * fpc * n_mels * 4)
+    s1, s2 = bench.output_sample(torch, out, n, fpc, n_mels, 100), bench.output_sample(torch, out, n, fpc, n_mels, 100)
+    assert s1["clips"] == s2["clips"] and len(s1["clips"]) == 10 and s1["clips"] == sorted(set(s1["clips"])) and 100 <= s1["clips"][0] and s1["clips"][-1] < 150
+    assert torch.equal(s1["mel"], out[: n * fpc * n_mels].view(n, fpc, n_mels)[[c - 100 for c in s1["clips"]]])
+    rec = bench.write_outputs(str(tmp_path / "d"), s1)
+    got = np.load(tmp_path / "d" / "mel.npy")
+    assert got.dtype == np.float32 and got.shape == (10, fpc, n_mels) and rec["files"] == {"mel.npy": [10, fpc, n_mels]}
+    monkeypatch.setattr(bench, "DUMP_BYTES", 5 * n_mels * 4)
+    s3 = bench.output_sample(torch, out, n, fpc, n_mels, 0)
+    assert len(s3["clips"]) == 1 and tuple(s3["mel"].shape) == (1, 5, n_mels)
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(gpu, oracle, tmp_path):
+    """A plain run times exactly --steps steps and does nothing else (no parity check, no value_ci, no legs, no CPU baseline, no host API).
+    --dump-outputs writes a seeded sample of the last step's output: the same clips and the same bits in two runs, the oracle's log-mel of
+    those clips within 1e-4."""
+    import json
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    lines = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--clips", "128", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600, env=env)
+        assert p.returncode == 0, p.stderr[-3000:]
+        out = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(out) == 1
+        lines.append(json.loads(out[0]))
+    line = lines[0]
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["n_gpus"] == 1
+    assert abs(line["value"] - 128 * 998 * 7 / (line["ms_per_step"] * 7e-3)) <= 1e-6 * line["value"]
+    assert line["parity_max_abs_diff"] is None and line["value_ci"] is None
+    assert not {"cpu_baseline", "host_api_frames_per_s_pcie_inclusive", "host_api_single_clip_ms"} & set(line)
+    assert not {"speech", "cfg3", "cfg4", "f64", "nemo"} & set(line["config"])
+    clips = line["dump_outputs"]["clips"]
+    assert clips == lines[1]["dump_outputs"]["clips"] and len(clips) == (32 << 20) // (998 * 80 * 4) and clips == sorted(set(clips)) and clips[-1] < 128
+    a, b = np.load(tmp_path / "a" / "mel.npy"), np.load(tmp_path / "b" / "mel.npy")
+    assert a.dtype == np.float32 and a.shape == (len(clips), 998, 80) and np.array_equal(a, b)
+    for k in (0, len(clips) - 1):
+        want = oracle.compute_mel_spectrogram_cpu(oracle.synth_pcm(clips[k], 160000), 400, 160, 80, 16000.0)
+        assert np.abs(a[k] - want).max() <= 1e-4, clips[k]
 
 
 def test_valu_fields_come_from_the_committed_isa_table():
@@ -333,7 +385,7 @@ def test_bench_multi_rank_path_rehearsed_on_one_gpu(gpu):
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--one-device", "--clips", "64", "--cfg5-clips", "96",
-                        "--steps", "5", "--warmup", "1"], capture_output=True, text=True, timeout=600, env=env)
+                        "--steps", "5", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -357,7 +409,7 @@ def test_bench_distributed_branch_runs_on_rccl_at_world_size_one(gpu):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = env.get("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--clips", "64", "--steps", "5", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-host-io", "--no-traffic", "--no-speech", "--no-legs"], capture_output=True, text=True, timeout=600, env=env)
+                        "--full", "--no-cpu-baseline", "--no-host-io", "--no-traffic", "--no-speech", "--no-legs"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/round_$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_line.err
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_line.err
 python - $OUT/bench_line.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))
