@@ -244,6 +244,34 @@ int melspec_compute_ragged_device_desc(melspec_ctx *ctx, const float *d_pcm, con
                                        uint32_t n_clips, float *d_out, const uint64_t *d_out_offsets, uint64_t max_total_frames,
                                        void *stream);
 
+/* ---- 16-bit ends: int16 PCM in, f16 / bf16 rows out --------------------------------------------------------------------------
+ * Audio arrives as 16-bit PCM (the reference's own example converts by hand, examples/vad_ten_eval/src/main.rs:298-299:
+ * `sample as f32 / 32768.0`) and the encoders behind the rows run in f16 or bf16.  These calls read and write those types in
+ * the kernel's own load and store: no conversion pass, half the bytes each way.
+ *   MELSPEC_PCM_S16: the sample's value is int16 * 2^-15, exactly -- the call gives the bits of the f32 call on the batch
+ *   converted by `v as f32 / 32768.0`.  MELSPEC_OUT_F16 / _BF16: the f32 row value rounded to nearest even.
+ * Strides, offsets, lengths and capacities count ELEMENTS (samples in, row values out), never bytes; only natural alignment
+ * of the element type is required (a ragged int16 clip may start at an odd sample, an f16 output at an odd element).
+ * Everything else -- frame count, short clips, stream ordering, precision modes, error codes -- is that of
+ * melspec_compute_uniform_device / _ragged_device / _host.  (F32, F32) is always supported and is the existing path.  The
+ * other five combinations are computed by the contexts of melspec_create(.., 400, hop, 16000, n_mels) with Whisper's 80- or
+ * 128-mel bank (melspec_supports_io == 1); every other context returns MELSPEC_ERR_UNSUPPORTED and does not touch the output. */
+#define MELSPEC_PCM_F32  0
+#define MELSPEC_PCM_S16  1      /* int16_t, value = sample * 2^-15 exactly */
+#define MELSPEC_OUT_F32  0
+#define MELSPEC_OUT_F16  1      /* IEEE binary16, round to nearest even of the f32 row value */
+#define MELSPEC_OUT_BF16 2      /* bfloat16, round to nearest even; a NaN stays a NaN */
+/* 1 if this context computes (pcm_dtype, out_dtype) batches, 0 if not (then the calls below return MELSPEC_ERR_UNSUPPORTED). */
+int melspec_supports_io(const melspec_ctx *ctx, int pcm_dtype, int out_dtype);
+int melspec_compute_uniform_device_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                      uint32_t n_clips, void *d_out, int out_dtype, void *stream);
+int melspec_compute_ragged_device_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                     const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
+                                     const uint64_t *h_out_offsets, void *stream);
+/* melspec_compute_host with 16-bit ends: the int16 bytes are what crosses the bus, and so are the 16-bit rows. */
+int melspec_compute_host_io(melspec_ctx *ctx, const void *samples, int pcm_dtype, size_t n_samples,
+                            void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames);
+
 /* Benchmark helper (the reference's #[ignore] Instant-timed benches, src/cuda.rs:547-613): runs
  * `warmup` untimed and `iters` timed melspec_compute_uniform_device calls on the context's own
  * stream between two HIP events and returns the average milliseconds per call. */

@@ -109,6 +109,10 @@ SIGNATURES = {
     "melspec_compute_uniform_device_interleaved": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int,
                                                              C.c_uint64, _vp]),
     "melspec_compute_ragged_device": (C.c_int, [_vp, _vp, _u64p, _u64p, C.c_uint32, _vp, _u64p, _vp]),
+    "melspec_supports_io": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "melspec_compute_uniform_device_io": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp]),
+    "melspec_compute_ragged_device_io": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, _vp, C.c_int, _u64p, _vp]),
+    "melspec_compute_host_io": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "melspec_compute_ragged_device_desc": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint64, _vp]),
     "melspec_time_uniform_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, C.c_int, _f32p]),
     "melspec_time_first_kernel": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, C.c_int, _f32p]),

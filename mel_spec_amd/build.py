@@ -14,8 +14,10 @@ LAB_LIB_PATH = os.path.join(PKG_DIR, "libmelspec_hip_lab.so")   # -DMELSPEC_LAB:
 # translation units (one kernel family each, csrc/host_common.hpp has the map) and the flags only they get: melspec_runs.hip holds the
 # run-per-wave f32 Whisper kernels, scheduled for ILP (csrc/melspec_runs.hip says why; the default strategy is the better one for
 # everything else)
-SOURCES = ["host_api.hip", "whisper400.hip", "fbank512.hip", "pow2.hip", "aux.hip", "melspec_runs.hip"]
-UNIT_FLAGS = {"melspec_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+# melspec_io_runs.hip / melspec_io64.hip: the same kernels with int16 PCM in / f16, bf16 rows out (csrc/whisper400_io_kernels.hpp), units of
+# their own so that the kernels above keep the instructions they have; the f32 ones get melspec_runs.hip's strategy
+SOURCES = ["host_api.hip", "whisper400.hip", "fbank512.hip", "pow2.hip", "aux.hip", "melspec_runs.hip", "melspec_io_runs.hip", "melspec_io64.hip"]
+UNIT_FLAGS = {"melspec_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "melspec_io_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
 
 def _inputs():

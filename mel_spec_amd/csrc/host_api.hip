@@ -498,6 +498,117 @@ int melspec_compute_host(melspec_ctx *c, const float *samples, size_t n_samples,
     return MELSPEC_OK;
 }
 
+// ---- int16 PCM in / f16, bf16 rows out ----------------------------------------------------------------------------------------------
+namespace {
+inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
+inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
+// 0: go on (io = the launch's code, 0 for (F32, F32)); otherwise the status to return
+int io_args(const melspec_ctx *c, int pcm_dtype, int out_dtype, int &io) {
+    if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
+    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
+        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    if (io && !ctx_supports_io(c)) {
+        g_last_error = "int16 PCM / f16, bf16 rows are computed by the n_fft = 400 contexts with Whisper's 80- or 128-mel bank only; this context is n_fft = " +
+                       std::to_string(c->fft_size) + ", hop = " + std::to_string(c->hop_size) + ", n_mels = " + std::to_string(c->n_mels) +
+                       (c->fast ? " (another filterbank)" : "");
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    return MELSPEC_OK;
+}
+}  // namespace
+
+int melspec_supports_io(const melspec_ctx *c, int pcm_dtype, int out_dtype) {
+    if (!c || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || ctx_supports_io(c) ? 1 : 0;
+}
+
+int melspec_compute_uniform_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                      uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
+    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_compute_uniform_device(c, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_out), stream);
+    if (n_clips == 0) return MELSPEC_OK;
+    uint64_t fpc; ctx_num_frames(c, clip_len, fpc);
+    if (fpc == 0) return MELSPEC_OK;
+    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if ((reinterpret_cast<uintptr_t>(d_pcm) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (io_out_bytes(out_dtype) - 1)))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    if (n_clips > 1 && clip_stride < clip_len && clip_stride != 0)
+        return fail(MELSPEC_ERR_INVALID_ARG, "clip_stride smaller than clip_len");
+    HIP_TRY(hipSetDevice(c->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    // the plan counts elements; the kernels read the two base addresses as their own types (BatchDesc)
+    const BatchPlan pl = plan_uniform(static_cast<const float *>(d_pcm), static_cast<float *>(d_out), clip_stride, fpc, n_clips, c->n_mels, ctx_frames_per_unit(c));
+    return launch_ctx(c, pl.desc, s, io);
+}
+
+int melspec_compute_ragged_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                     uint32_t n_clips, void *d_out, int out_dtype, const uint64_t *h_out_offsets, void *stream) {
+    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_compute_ragged_device(c, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_out), h_out_offsets, stream);
+    if (n_clips == 0) return MELSPEC_OK;
+    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
+    std::vector<uint64_t> frames(n_clips);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) { ctx_num_frames(c, h_lengths[i], frames[i]); total += frames[i]; }
+    if (total == 0) return MELSPEC_OK;
+    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if ((reinterpret_cast<uintptr_t>(d_pcm) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (io_out_bytes(out_dtype) - 1)))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(c->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    rc = plan_ragged(c->ragged, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_out), h_offsets, frames, h_out_offsets, n_clips, c->n_mels,
+                     ctx_frames_per_unit(c), pl, slot);
+    if (!rc) rc = launch_ctx(c, pl.desc, s, io);
+    plan_ragged_done(slot, s);
+    return rc;
+}
+
+int melspec_compute_host_io(melspec_ctx *c, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
+                            size_t out_capacity_elems, size_t *n_frames) {
+    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_compute_host(c, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, n_frames);
+    if (n_frames) *n_frames = 0;
+    uint64_t frames; ctx_num_frames(c, n_samples, frames);
+    if (frames == 0) return MELSPEC_OK;
+    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+    if (out_capacity_elems < frames * static_cast<uint64_t>(c->n_mels)) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(c->dev.device));
+    // push_segments' cut (the same sample count per piece), in bytes of the two element types
+    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
+    const uint64_t fft = static_cast<uint64_t>(c->fft_size), hop = static_cast<uint64_t>(c->hop_size);
+    const char *src = static_cast<const char *>(samples);
+    char *dst = static_cast<char *>(out);
+    std::vector<HostSeg> segs;
+    auto seg = [&](uint64_t s0, uint64_t n, uint64_t f0, uint64_t nf) {
+        segs.push_back(HostSeg{reinterpret_cast<const float *>(src + s0 * ib), n, reinterpret_cast<float *>(dst + f0 * static_cast<uint64_t>(c->n_mels) * ob), nf});
+    };
+    if (n_samples <= kPipeChunkSamples) seg(0, n_samples, 0, frames);
+    else {
+        const uint64_t per = (kPipeChunkSamples - fft) / hop + 1;      // frames per piece
+        for (uint64_t f0 = 0; f0 < frames; f0 += per) {
+            const uint64_t nf = frames - f0 < per ? frames - f0 : per;
+            seg(f0 * hop, (nf - 1) * hop + fft, f0, nf);
+        }
+    }
+    const char *where = "";
+    rc = c->pipe.run(segs, c->n_mels, kPipeChunkSamples, c->stream,
+                     [c, pcm_dtype, out_dtype](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out, const uint64_t *ooffs, hipStream_t s) {
+                         return melspec_compute_ragged_device_io(c, d_in, pcm_dtype, offs, lens, n, d_out, out_dtype, ooffs, s);
+                     }, &where, ib, ob);
+    if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
+    if (rc) return rc;
+    if (n_frames) *n_frames = static_cast<size_t>(frames);
+    return MELSPEC_OK;
+}
+
 int melspec_compute_batch_host(melspec_ctx *c, const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips,
                                float *out, const uint64_t *out_offsets, size_t out_capacity_floats, uint64_t *total_frames) {
     if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");

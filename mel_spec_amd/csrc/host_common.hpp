@@ -433,7 +433,9 @@ FixSink sink_armed(melspec_ctx *c, FixSink sink, const BatchDesc &desc, unsigned
 // MELSPEC_PRECISION_AUTO: the context's sink for a launch on `stream` (note list sized for the batch, statistics words, host-mapped
 // figures; with_vote: the vote's tally and verdict words too)
 int auto_sink(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream, bool with_vote, FixSink &sink);
-int launch_ctx(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream);
+// io: 0, or pcm_dtype | out_dtype << 4 of melspec_compute_*_io (not both F32): desc.pcm / desc.out then point at int16 samples / f16, bf16
+// rows, the batch is a plain one planned on the host for six frames per unit and the context passes ctx_supports_io
+int launch_ctx(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream, int io = 0);
 int launch_stft(melspec_ctx *c, const BatchDesc &desc, int bins, int dtype, hipStream_t s);
 // ---- pow2.hip / fbank512.hip: the parts of launch_ctx / launch_stft that run on their kernels ---------------------------------------
 int launch_generic_stft(melspec_ctx *c, const BatchDesc &desc, int bins, int dtype, hipStream_t s);
@@ -448,6 +450,13 @@ bool twelve_waves_for(const melspec_ctx *c, bool layout);      // whisper400.hip
 // keeps 141 SGPRs' worth of slot tables and reloads 13 spilled registers inside the unit loop (tools/hotloop_spills.py); those banks stay
 // on whisper400_precise_kernel's layout form.
 inline bool six64_layout_ok(const melspec_ctx *c) { return c->six64 && !c->six64_wide && c->six_static != 0; }
+
+// int16 PCM in / f16, bf16 rows out: the contexts whose plain batches run the six-frame kernels with one of the compile-time Whisper banks
+// in every precision mode -- 80 mels (whisper400_six_runs_kernel + whisper400_six64_kernel<9, .>) and 128 mels (whisper400_six_wide_runs_kernel
+// + whisper400_six64_kernel<15, .>)
+inline bool ctx_supports_io(const melspec_ctx *c) {
+    return c->fast && c->six64 && ((c->six && c->six_static == 1 && !c->six64_wide) || (!c->six && c->six_wide32 && c->six64_wide));
+}
 
 inline int ctx_frames_per_unit(melspec_ctx *c, bool layout = false) {
     if (c->fast) {

@@ -105,7 +105,9 @@ private:
     bool stop_ = false;
 };
 
-// one unit of a host call: n samples at src -> frames * n_mels floats at dst (a whole clip or a frame-aligned piece of one)
+// one unit of a host call: n samples at src -> frames * n_mels floats at dst (a whole clip or a frame-aligned piece of one).
+// melspec_compute_host_io: src / dst are the addresses of 16-bit samples / rows (run()'s in_elem / out_elem say so); n and frames count
+// elements whatever their size.
 struct HostSeg {
     const float *src;
     uint64_t n;
@@ -191,9 +193,11 @@ struct HostPipe {
     // launch(d_in, offsets, lengths, n, d_out, out_offsets, stream) -> library status (0 = ok): the kernels of one chunk,
     // queued on `compute`; clip i of the chunk = d_in + offsets[i] (lengths[i] samples) -> d_out + out_offsets[i].
     // Returns 0, a positive hipError_t, or the launch's status; *where names the failing call.
+    // in_elem / out_elem: bytes per sample / per output value (the device buffers are handed to `launch` as float pointers whatever they hold)
     template <class Launch>
-    int run(const std::vector<HostSeg> &segs, int n_mels, uint64_t chunk_samples, hipStream_t compute, Launch &&launch, const char **where) {
-        const int rc = run_impl(segs, n_mels, chunk_samples, compute, launch, where);
+    int run(const std::vector<HostSeg> &segs, int n_mels, uint64_t chunk_samples, hipStream_t compute, Launch &&launch, const char **where,
+            size_t in_elem = sizeof(float), size_t out_elem = sizeof(float)) {
+        const int rc = run_impl(segs, n_mels, chunk_samples, compute, launch, where, in_elem, out_elem);
         if (rc != 0) {
             // A call that fails half-way must not return while copies are still reading `samples` or writing `out`, and the next call
             // reuses the buffers and events from chunk 0: drain all three streams (their own errors do not matter any more).
@@ -207,7 +211,8 @@ struct HostPipe {
     }
 
     template <class Launch>
-    int run_impl(const std::vector<HostSeg> &segs, int n_mels, uint64_t chunk_samples, hipStream_t compute, Launch &&launch, const char **where) {
+    int run_impl(const std::vector<HostSeg> &segs, int n_mels, uint64_t chunk_samples, hipStream_t compute, Launch &&launch, const char **where,
+                 size_t in_elem, size_t out_elem) {
 #define MS_PIPE_TRY(expr)                                        \
     do {                                                         \
         const hipError_t e_ = (expr);                            \
@@ -217,9 +222,10 @@ struct HostPipe {
         if (segs.empty()) return 0;
         MS_PIPE_TRY(init());
         // cheap screen on the ends of the batch; every merged piece of a chunk is then checked on its own (clips may live anywhere)
-        const bool in_pinned = host_ptr_is_pinned(segs.front().src) && host_ptr_is_pinned(segs.back().src + segs.back().n - 1);
+        const bool in_pinned = host_ptr_is_pinned(segs.front().src) &&
+                               host_ptr_is_pinned(reinterpret_cast<const char *>(segs.back().src) + (segs.back().n - 1) * in_elem);
         const bool out_pinned = host_ptr_is_pinned(segs.front().dst) &&
-                                host_ptr_is_pinned(segs.back().dst + segs.back().frames * static_cast<uint64_t>(n_mels) - 1);
+                                host_ptr_is_pinned(reinterpret_cast<const char *>(segs.back().dst) + (segs.back().frames * static_cast<uint64_t>(n_mels) - 1) * out_elem);
         struct Chunk { size_t first, count; uint64_t samples, out_floats; bool staged_out; };
         std::vector<Chunk> chunks;
         uint64_t total_samples = 0, total_out = 0;
@@ -227,7 +233,7 @@ struct HostPipe {
         // small calls: one chunk, copied by the runtime straight from / to the caller's memory on the compute stream (its
         // pageable path is as fast as pinned DMA up to a few tens of MB and there is nothing to overlap).  Larger calls: chunks
         // of chunk_samples (16 MiB of PCM; cutting 64 x 10 s into 8 chunks instead of 3 lost 12 %: per-chunk launches and events)
-        const bool direct = (total_samples + total_out) * sizeof(float) <= kDirectBytes;
+        const bool direct = total_samples * in_elem + total_out * out_elem <= kDirectBytes;
         if (direct) chunk_samples = ~0ull;
         for (size_t i = 0; i < segs.size();) {
             Chunk c{i, 0, 0, 0, false};
@@ -247,7 +253,7 @@ struct HostPipe {
             size_t dev = 0;
             for (size_t i = c.first; i < c.first + c.count; ++i) {
                 const char *h = output ? reinterpret_cast<const char *>(segs[i].dst) : reinterpret_cast<const char *>(segs[i].src);
-                const size_t bytes = static_cast<size_t>(output ? segs[i].frames * static_cast<uint64_t>(n_mels) : segs[i].n) * sizeof(float);
+                const size_t bytes = static_cast<size_t>(output ? segs[i].frames * static_cast<uint64_t>(n_mels) : segs[i].n) * (output ? out_elem : in_elem);
                 if (bytes) {
                     if (!v.empty() && v.back().host + v.back().bytes == h) v.back().bytes += bytes;
                     else v.push_back(Piece{h, bytes, dev});
@@ -273,8 +279,8 @@ struct HostPipe {
         };
         if (direct && chunks.size() == 1 && pieces_of(chunks[0], false).size() <= kDirectPieces && pieces_of(chunks[0], true).size() <= kDirectPieces) {
             const Chunk &c = chunks[0];
-            MS_PIPE_TRY(grow_dev(d_in[0], d_in_cap[0], static_cast<size_t>(c.samples) * sizeof(float) + 16));
-            MS_PIPE_TRY(grow_dev(d_out[0], d_out_cap[0], static_cast<size_t>(c.out_floats) * sizeof(float) + 16));
+            MS_PIPE_TRY(grow_dev(d_in[0], d_in_cap[0], static_cast<size_t>(c.samples) * in_elem + 16));
+            MS_PIPE_TRY(grow_dev(d_out[0], d_out_cap[0], static_cast<size_t>(c.out_floats) * out_elem + 16));
             for (const Piece &p : pieces_of(c, false))
                 MS_PIPE_TRY(hipMemcpyAsync(static_cast<char *>(d_in[0]) + p.dev_off, p.host, p.bytes, hipMemcpyHostToDevice, compute));
             uint64_t so = 0, oo = 0;
@@ -295,7 +301,7 @@ struct HostPipe {
             Chunk &c = chunks[k];
             const int b = static_cast<int>(k % kBuf);
             if (k >= kBuf) { const int rc = retire_out(k - kBuf); if (rc) return rc; }      // frees h_out[b]; d_out[b] drained
-            const size_t in_bytes = static_cast<size_t>(c.samples) * sizeof(float), out_bytes = static_cast<size_t>(c.out_floats) * sizeof(float);
+            const size_t in_bytes = static_cast<size_t>(c.samples) * in_elem, out_bytes = static_cast<size_t>(c.out_floats) * out_elem;
             if (in_bytes + 16 > d_in_cap[b]) {
                 if (k >= kBuf) MS_PIPE_TRY(hipEventSynchronize(ev_cmp[b]));                    // the kernels of chunk k-2 read it
                 MS_PIPE_TRY(grow_dev(d_in[b], d_in_cap[b], in_bytes + 16));

@@ -28,8 +28,8 @@ namespace melspec {
 // How work units (tiles of frames) map onto clips.  Uniform batches are pure arithmetic;
 // ragged batches look the clip up in a per-16-units table and a prefix table of units per clip.
 struct BatchDesc {
-    const float *pcm;
-    float *out;
+    const float *pcm;          // base addresses: float for every kernel but the *_io_* ones, which read them as their own sample / row
+    float *out;                //   types (int16 in, f16 / bf16 out); every stride and offset below counts ELEMENTS of those types
     uint64_t clip_stride;      // uniform: samples between clip starts
     uint64_t out_stride;       // uniform: floats between clip outputs
     uint64_t frames_per_clip;  // uniform
@@ -59,21 +59,25 @@ __device__ __forceinline__ uint64_t batch_n_units(const BatchDesc &b) { return b
 
 constexpr uint32_t kUnitBlock = 16;   // granularity of BatchDesc::d_unit_block
 
-struct UnitLoc {
-    const float *pcm;   // first sample of the clip
-    float *out;         // first output float of the clip
+// In / Out: the sample and row types of the kernel (float everywhere but in the *_io_* kernels of melspec_io*.hip)
+template <class In = float, class Out = float>
+struct UnitLocT {
+    const In *pcm;      // first sample of the clip
+    Out *out;           // first output value of the clip
     uint64_t frames;    // frames in the clip
     uint64_t unit;      // unit index inside the clip
     uint32_t clip;      // the clip
 };
+using UnitLoc = UnitLocT<>;
 
-__device__ __forceinline__ UnitLoc locate_unit(const BatchDesc &b, uint64_t unit) {
-    UnitLoc r;
+template <class In = float, class Out = float>
+__device__ __forceinline__ UnitLocT<In, Out> locate_unit(const BatchDesc &b, uint64_t unit) {
+    UnitLocT<In, Out> r;
     if (b.d_unit_prefix == nullptr) {
         const uint64_t clip = unit / b.units_per_clip;
         r.unit = unit - clip * b.units_per_clip;
-        r.pcm = b.pcm + clip * b.clip_stride;
-        r.out = b.out + clip * b.out_stride;
+        r.pcm = reinterpret_cast<const In *>(b.pcm) + clip * b.clip_stride;
+        r.out = reinterpret_cast<Out *>(b.out) + clip * b.out_stride;
         r.frames = b.frames_per_clip;
         r.clip = static_cast<uint32_t>(clip);
     } else {
@@ -93,8 +97,8 @@ __device__ __forceinline__ UnitLoc locate_unit(const BatchDesc &b, uint64_t unit
             }
         }
         r.unit = unit - p0;
-        r.pcm = b.pcm + off0;
-        r.out = b.out + oo0;
+        r.pcm = reinterpret_cast<const In *>(b.pcm) + off0;
+        r.out = reinterpret_cast<Out *>(b.out) + oo0;
         r.frames = fr0;
         r.clip = lo;
     }
@@ -356,24 +360,25 @@ struct RoundSync {
 };
 
 // A wave's contiguous run of units of a ragged batch and the clip it is in (everything wave-uniform, in scalar registers).
-struct ClipRun {
+template <class In = float, class Out = float>
+struct ClipRunT {
     uint64_t unit, end, c_start, c_end, c_frames;
-    const float *c_pcm;
-    float *c_out;
+    const In *c_pcm;
+    Out *c_out;
     uint32_t clip;
     __device__ __forceinline__ void load_clip(const BatchDesc &b) {
         if (b.d_unit_prefix == nullptr) {                 // uniform batch: arithmetic
             c_start = (uint64_t)clip * b.units_per_clip;
             c_end = c_start + b.units_per_clip;
             c_frames = b.frames_per_clip;
-            c_pcm = b.pcm + (uint64_t)clip * b.clip_stride;
-            c_out = b.out + (uint64_t)clip * b.out_stride;
+            c_pcm = reinterpret_cast<const In *>(b.pcm) + (uint64_t)clip * b.clip_stride;
+            c_out = reinterpret_cast<Out *>(b.out) + (uint64_t)clip * b.out_stride;
             return;
         }
         c_start = scalar64(b.d_unit_prefix[clip]);
         c_frames = scalar64(b.d_frames[clip]);
-        c_pcm = b.pcm + scalar64(b.d_off[clip]);
-        c_out = b.out + scalar64(b.d_out_off[clip]);
+        c_pcm = reinterpret_cast<const In *>(b.pcm) + scalar64(b.d_off[clip]);
+        c_out = reinterpret_cast<Out *>(b.out) + scalar64(b.d_out_off[clip]);
     }
     // the clip that holds `unit` (unit < the batch's units)
     __device__ __forceinline__ void place(const BatchDesc &b) {
@@ -403,8 +408,8 @@ struct ClipRun {
         unit = u;
         place(b);
     }
-    __device__ __forceinline__ UnitLoc loc() const {
-        UnitLoc r;
+    __device__ __forceinline__ UnitLocT<In, Out> loc() const {
+        UnitLocT<In, Out> r;
         r.unit = unit - c_start; r.pcm = c_pcm; r.out = c_out; r.frames = c_frames; r.clip = clip;
         return r;
     }
@@ -417,6 +422,7 @@ struct ClipRun {
         }
     }
 };
+using ClipRun = ClipRunT<>;
 
 constexpr int kWaveWaves = 8;     // waves per workgroup of the 5-frame n_fft = 400 kernels (two workgroups per CU)
 constexpr int kPreciseWaves = 8;  // ... of whisper400_precise_kernel / whisper400_stft_kernel (one workgroup per CU)

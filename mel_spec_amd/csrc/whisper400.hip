@@ -1,13 +1,21 @@
 // whisper400.hip -- launchers of the fused n_fft = 400 kernels (whisper400_kernels.hpp): launch_ctx picks the kernel a batch of a
 // melspec_ctx runs on -- f32 with the precision guard and the vote, or f64 -- and launch_stft exports the spectrum (row a3).
 #include "host_common.hpp"
-#include "whisper400_kernels.hpp"
+#include "whisper400_io_kernels.hpp"
 namespace melspec {
 // emitted by melspec_runs.hip (compiled with its own scheduling strategy; see there)
 extern template __global__ void whisper400_six_runs_kernel<kSixMaxSlots, LensSix80>(const FastParams);
 extern template __global__ void whisper400_wave_runs_kernel<8, LensI80>(const FastParams);
 extern template __global__ void whisper400_wave_runs_kernel<12, LensI128>(const FastParams);
 extern template __global__ void whisper400_six_wide_runs_kernel<kSixWideSlots, LensSix128>(const FastParams);
+// emitted by melspec_io_runs.hip / melspec_io64.hip: int16 PCM in and / or f16, bf16 rows out
+#define MS_IO_EXTERN(In, Out)                                                                                                  \
+    extern template __global__ void whisper400_six_runs_io_kernel<kSixMaxSlots, LensSix80, In, Out>(const FastParams);        \
+    extern template __global__ void whisper400_six_wide_runs_io_kernel<kSixWideSlots, LensSix128, In, Out>(const FastParams); \
+    extern template __global__ void whisper400_six64_io_kernel<kSixMaxSlots, LensSix80, In, Out>(const Six64Params);          \
+    extern template __global__ void whisper400_six64_io_kernel<kSixWideSlots, LensSix128, In, Out>(const Six64Params);
+MS_IO_COMBOS(MS_IO_EXTERN)
+#undef MS_IO_EXTERN
 }  // namespace melspec
 
 namespace melspec {
@@ -294,10 +302,87 @@ int launch_six_wide(melspec_ctx *c, const BatchDesc &desc, const FixSink &sink, 
     return MELSPEC_OK;
 }
 
-int launch_ctx(melspec_ctx *c, const BatchDesc &desc_in, hipStream_t stream) {
+// ---- int16 PCM in / f16, bf16 rows out (melspec_compute_*_io): the kernels of a (sample, row) combination and their launches --------------
+// The launches mirror launch_six_t<LensSix80> / launch_six_wide / launch_six64_t on a plain batch: same grid, same run per wave, same vote
+// sample, same sink -- AUTO gives the same bits and the same statistics as the f32 call on the converted batch.
+struct IoKernels {
+    void (*runs80)(const FastParams);
+    void (*runs128)(const FastParams);
+    void (*f64_80)(const Six64Params);
+    void (*f64_128)(const Six64Params);
+};
+template <class In, class Out>
+IoKernels io_kernels_of() {
+    return IoKernels{&whisper400_six_runs_io_kernel<kSixMaxSlots, LensSix80, In, Out>, &whisper400_six_wide_runs_io_kernel<kSixWideSlots, LensSix128, In, Out>,
+                     &whisper400_six64_io_kernel<kSixMaxSlots, LensSix80, In, Out>, &whisper400_six64_io_kernel<kSixWideSlots, LensSix128, In, Out>};
+}
+// io = pcm_dtype | out_dtype << 4, not (F32, F32); the kernels are allowed the whole LDS once per device and combination
+int io_kernels(int io, const IoKernels *&k) {
+    static const IoKernels table[2][3] = {{IoKernels{}, io_kernels_of<float, io_f16>(), io_kernels_of<float, io_bf16>()},
+                                          {io_kernels_of<io_s16, float>(), io_kernels_of<io_s16, io_f16>(), io_kernels_of<io_s16, io_bf16>()}};
+    static std::atomic<uint64_t> attr_done[2][3];
+    const int pcm = io & 15, out = io >> 4;
+    if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || io == 0) return fail(MELSPEC_ERR_INTERNAL, "io_kernels: no such combination");
+    k = &table[pcm][out];
+    if (!device_done(attr_done[pcm][out])) {
+        int rc = allow_big_lds(k->runs80, "hipFuncSetAttribute(whisper400_six_runs_io_kernel)");
+        if (!rc) rc = allow_big_lds(k->runs128, "hipFuncSetAttribute(whisper400_six_wide_runs_io_kernel)");
+        if (!rc) rc = allow_big_lds(k->f64_80, "hipFuncSetAttribute(whisper400_six64_io_kernel<9, .>)");
+        if (!rc) rc = allow_big_lds(k->f64_128, "hipFuncSetAttribute(whisper400_six64_io_kernel<15, .>)");
+        if (rc) return rc;
+        mark_device_done(attr_done[pcm][out]);
+    }
+    return MELSPEC_OK;
+}
+
+int launch_six_io(melspec_ctx *c, const BatchDesc &desc, const FixSink &sink, hipStream_t stream, const IoKernels *k) {
+    const bool wide = !c->six;                                                       // ctx_supports_io: then the 128-mel bank on twelve waves
+    const int waves = wide ? kSixWideWaves : kSixWaves;
+    const uint64_t blocks = (desc.n_units + waves - 1) / waves;
+    static const int per_cu = lab_int("MELSPEC_SIX_GRID_PER_CU", 1, 1, 4096);     // launch_six_t's
+    const dim3 grid(grid_for_xcd(blocks, c->dev.cus, wide ? 1 : per_cu)), block(waves * 64);
+    FixSink armed = sink_armed(c, sink, desc, grid.x);
+    armed.vote_groups = std::min<unsigned>(grid.x, static_cast<unsigned>(c->dev.cus));
+    const FastParams fp = wide ? fast_params(desc, c->ft6w, c->d_blob6w, c, armed) : fast_params(desc, c->ft6, c->d_blob6, c, armed);
+    hipLaunchKernelGGL(wide ? k->runs128 : k->runs80, grid, block, wide ? c->lds6w : c->lds6, stream, fp);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+int launch_six64_io(melspec_ctx *c, const BatchDesc &desc, const FixSink &stat, hipStream_t stream, const IoKernels *k, const unsigned *gate = nullptr,
+                    unsigned gate_value = 0) {
+    const uint64_t blocks = (desc.n_units + kSix64Waves - 1) / kSix64Waves;
+    static const int per_cu = lab_int("MELSPEC_SIX64_GRID_PER_CU", 1, 1, 4096);   // launch_six64_t's
+    const unsigned grid = grid_for_xcd(blocks, c->dev.cus, per_cu);
+    FixSink armed = sink_armed(c, stat, desc, grid);
+    if (gate) armed.frames |= kStatFromGated;
+    Six64Params pp{};
+    pp.b = desc;
+    pp.stat = armed;
+    pp.d_blob = static_cast<const uint32_t *>(c->d_blob64x.p);
+    pp.blob_words = static_cast<int>(c->t64.blob.size());
+    pp.mel_off_words = c->t64.mel_off_words;
+    pp.hop = c->hop_size;
+    pp.n_mels = c->n_mels;
+    pp.slots = c->ft6.slots;
+    pp.gate = gate; pp.gate_value = gate_value;
+    hipLaunchKernelGGL(c->six64_wide ? k->f64_128 : k->f64_80, dim3(grid), dim3(kSix64Waves * 64), c->lds64x, stream, pp);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+int launch_ctx(melspec_ctx *c, const BatchDesc &desc_in, hipStream_t stream, int io) {
     if (desc_in.n_units == 0) return MELSPEC_OK;
     BatchDesc desc = desc_in;
     const bool layout_batch = desc.mel_major || desc.out_width != desc.frames_per_clip;   // ragged batches: both zero
+    const IoKernels *iok = nullptr;
+    if (io) {
+        // the entry points ask ctx_supports_io before they plan: plain batches of the six-frame contexts, planned on the host
+        if (!ctx_supports_io(c) || layout_batch || desc.frames_per_unit != kSixFrames || desc.d_n_units != nullptr || desc.d_unit_ext != nullptr)
+            return fail(MELSPEC_ERR_INTERNAL, "launch_ctx: a 16-bit batch off the six-frame kernels");
+        const int rc = io_kernels(io, iok);
+        if (rc) return rc;
+    }
     if (desc.sync_rounds < 0) {
         // measured (profiles/r01_variants.txt): six-frame kernel, 16 waves: four waves 4 apart; precise kernel, 8 waves:
         // consecutive pairs; 5-frame kernel, two 8-wave workgroups per CU: pairs 4 apart
@@ -312,6 +397,7 @@ int launch_ctx(melspec_ctx *c, const BatchDesc &desc_in, hipStream_t stream) {
     if (!c->fast && c->fast512 && desc.frames_per_unit == kFbFPW) return launch_whisper512(c, desc, stream);
     if (!c->fast) return launch_generic(c->gt, desc, c->hop_size, 0, 1, 1, 0.0, 0.0, c->dev.cus, stream);
     if (c->precision == MELSPEC_PRECISION_F64) {
+        if (iok) return launch_six64_io(c, desc, FixSink{}, stream, iok);
         if ((layout_batch ? six64_layout_ok(c) : c->six64) && desc.frames_per_unit == kSixFrames && desc.d_unit_prefix == nullptr) {
             // mel-major stores of the twelve-wave kernel, measured (tools/mm64_sync_probe.py, 1024 x 10 s): consecutive pairs 0.491 ms, none 0.493,
             // pairs four apart 0.496, fours 0.512, fours one from each SIMD (the f32 kernel's best) 0.520, workgroup barrier 0.533
@@ -338,7 +424,9 @@ int launch_ctx(melspec_ctx *c, const BatchDesc &desc_in, hipStream_t stream) {
         c->first_kernel_events->push_back(pe0); c->first_kernel_events->push_back(pe1);
         HIP_TRY(hipEventRecord(pe0, stream));
     }
-    if (c->six && desc.frames_per_unit == kSixFrames)
+    if (iok)
+        rc = launch_six_io(c, desc, sink, stream, iok);
+    else if (c->six && desc.frames_per_unit == kSixFrames)
         rc = c->six_static == 1 ? launch_six_t<LensSix80>(c, desc, sink, stream) : c->six_static == 2 ? launch_six_t<LensSix64>(c, desc, sink, stream)
            : c->six_static == 3 ? launch_six_t<LensSix40>(c, desc, sink, stream) : launch_six_t<LensRuntime>(c, desc, sink, stream);
     else if (c->six_wide32 && desc.frames_per_unit == kSixFrames)
@@ -351,6 +439,7 @@ int launch_ctx(melspec_ctx *c, const BatchDesc &desc_in, hipStream_t stream) {
     const unsigned gate_value = (c->fix.seq & 0xffffffu) << 2 | kVoteDecided | kVoteHeavy;
     FixSink stat{};
     stat.count = sink.count; stat.acc = sink.acc; stat.host = sink.host;
+    if (iok) return launch_six64_io(c, desc, stat, stream, iok, sink.decision, gate_value);
     if (six64_layout_ok(c) && layout_batch && desc.frames_per_unit == kSixFrames && desc.d_unit_prefix == nullptr) {
         if (desc_in.sync_rounds < 0) desc.sync_rounds = 2;
         return launch_six64(c, desc, stat, stream, sink.decision, gate_value);          // the layouts on the six-frame f64 kernel: the f32 launch's own plan

@@ -17,7 +17,8 @@ static_assert(kWaveFixOff >= WaveLayout::kPmaxOff + kFPW * WaveLayout::kPmaxStri
 
 // f64 power row of frame `f` of the unit (whisper_fix64.hpp): every lane of the wave takes part
 // `next`: the frame recomputed after this one (nullptr: none); its samples are loaded while steps 2-4 run
-__device__ __forceinline__ void fix_power_row(int lane, FixSamples &smp, const float *next, const double *tab, const FixTw &tw, float *slice, int scratch_off, float *prow) {
+template <class In>
+__device__ __forceinline__ void fix_power_row(int lane, FixSamples &smp, const In *next, const double *tab, const FixTw &tw, float *slice, int scratch_off, float *prow) {
     double *z = reinterpret_cast<double *>(slice + scratch_off);
     fix_step1(lane, smp, tab, z);
     if (next) fix_load_samples(lane, next, smp);
@@ -35,9 +36,9 @@ __device__ __forceinline__ void fix_power_row(int lane, FixSamples &smp, const f
 // The f32 kernels do not call this inside their unit loop -- with the f64 code in the loop body the register allocator gives the
 // hot path 5 % (a call) to 40 % (inlined) away -- but note the unit (FixSink::list) and come back to it when their run is done.
 // Six frames x ten lanes.
-template <int NSLOTS, class Lens, bool LAYOUT>
+template <int NSLOTS, class Lens, bool LAYOUT, class In, class Out>
 __device__ __forceinline__ unsigned six_fix_unit(unsigned mask, int lane, int hop, int n_mels, const MelSlots &ms, const float *blob, float *slice,
-                                          const FixSink &fix, const FixTw &tw, const float *src, float *out_tile, long long row_w,
+                                          const FixSink &fix, const FixTw &tw, const In *src, Out *out_tile, long long row_w,
                                           int *ext = nullptr /* LAYOUT: the unit's record in BatchDesc::d_unit_ext, or nullptr */) {
     const int fl = lane / kSixLanes, j = lane - fl * kSixLanes;
     const bool in = lane < kSixFrames * kSixLanes;
@@ -284,7 +285,11 @@ __global__ __launch_bounds__(kSixWideWaves * 64, 3) void whisper400_six_wide_ker
 template <int NSLOTS, class Lens>
 __global__ __launch_bounds__(kSixWaves * 64, 4) void whisper400_six_runs_kernel(const FastParams p) {
 #define MS_SIX_RUNS_WAVES kSixWaves
+#define MS_SIX_RUNS_IN float
+#define MS_SIX_RUNS_OUT float
 #include "whisper400_six_runs_body.inc"
+#undef MS_SIX_RUNS_OUT
+#undef MS_SIX_RUNS_IN
 #undef MS_SIX_RUNS_WAVES
 }
 
@@ -294,7 +299,11 @@ __global__ __launch_bounds__(kSixWaves * 64, 4) void whisper400_six_runs_kernel(
 template <int NSLOTS, class Lens>
 __global__ __launch_bounds__(kSixWideWaves * 64, 3) void whisper400_six_wide_runs_kernel(const FastParams p) {
 #define MS_SIX_RUNS_WAVES kSixWideWaves
+#define MS_SIX_RUNS_IN float
+#define MS_SIX_RUNS_OUT float
 #include "whisper400_six_runs_body.inc"
+#undef MS_SIX_RUNS_OUT
+#undef MS_SIX_RUNS_IN
 #undef MS_SIX_RUNS_WAVES
 }
 
@@ -569,70 +578,11 @@ struct Six64Params {
 
 template <int NSLOTS, class Lens>
 __global__ __launch_bounds__(kSix64Waves * 64, 3) void whisper400_six64_kernel(const Six64Params p) {
-    constexpr int WAVES = kSix64Waves;
-    if (p.gate != nullptr && *p.gate != p.gate_value) return;        // the batch was light: the f32 launch has finished it
-    extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < p.blob_words; i += WAVES * 64) ldsw[i] = p.d_blob[i];
-    unsigned *wg_done = ldsw + p.blob_words + WAVES * Six64Layout::slice_doubles() * 2;
-    if (tid < 2) wg_done[tid] = 0;
-    __syncthreads();
-    const double *tb = reinterpret_cast<const double *>(ldsw);
-    // the shared phase-3 code addresses the mel tables as offsets from the base of the six-frame f32 blob
-    const float *fblob = reinterpret_cast<const float *>(ldsw + p.mel_off_words) - SixBlob::kMelStart;
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    double *rows = reinterpret_cast<double *>(ldsw + p.blob_words) + wave * Six64Layout::slice_doubles();
-    float *slice = reinterpret_cast<float *>(rows);
-    const int fl = lane / kSixLanes, j = lane - fl * kSixLanes;
-    const bool in = lane < kSixFrames * kSixLanes;
-    const int rofs = Six64Layout::row_offset(j);
-    const int n_mels = Lens::kStatic ? Lens::kMels : p.n_mels;
-    const int *starts = reinterpret_cast<const int *>(fblob + SixBlob::kMelStart) + j;
-    const bool stats = p.stat.acc != nullptr;
-    unsigned flagged = 0;
-
-    ClipRun cr;
-    if (!cr.init(p.b, (uint64_t)xcd_logical_block() * WAVES + wave, (uint64_t)gridDim.x * WAVES)) {
-        guard_wave_done(p.stat, wg_done, WAVES, lane, 0);
-        return;
-    }
-    for (; cr.unit < cr.end; ++cr.unit) {
-        cr.enter(p.b);
-        const uint64_t f0 = (cr.unit - cr.c_start) * kSixFrames;
-        const uint64_t left = cr.c_frames - f0;
-        const int nv = left < (uint64_t)kSixFrames ? (int)left : kSixFrames;
-        const float *src = cr.c_pcm + f0 * (uint64_t)p.hop;
-        const bool act = in && fl < nv;
-        MS_PRIO(0);
-        // The tables never change, and with __restrict__ the compiler knows it: left alone it hoists the unit loop's ~50 sixteen-byte table
-        // reads out of the loop (200 VGPRs of "loop invariants"), spills them in front of the loop and reloads them from scratch inside it.
-        // An offset it cannot see through makes the reads belong to the iteration.
-        int opaque0 = 0;
-        asm volatile("" : "+s"(opaque0));
-        const double *tbi = tb + opaque0;
-        six64_phases12(fl, j, act, rofs, p.hop, tbi, src, rows, slice);
-        __builtin_amdgcn_wave_barrier();
-        MS_PRIO(2);
-        float vals[NSLOTS];
-        {
-            int st[NSLOTS];
-#pragma unroll
-            for (int i = 0; i < NSLOTS; ++i) st[i] = starts[i * kSixLanes];       // lanes 60..63 read valid entries too
-            float rise[NSLOTS], fprev[NSLOTS], fnext[NSLOTS];
-            six_phase3_sums<NSLOTS, Lens>(fl, j, act, p.slots, fblob, slice, st, rise, fprev);
-#pragma unroll
-            for (int i = 0; i < NSLOTS; ++i) fnext[i] = wave_shift_down1(fprev[i]);
-            six_phase3_finish<NSLOTS>(fl, j, act, n_mels, rise, fnext, slice, vals);
-        }
-        __builtin_amdgcn_wave_barrier();
-        float *out_tile = cr.c_out + f0 * (uint64_t)n_mels;
-        const bool flag = six_phase4<NSLOTS, false, true>(fl, j, act, act, n_mels, slice, vals, out_tile, 0);
-        __builtin_amdgcn_wave_barrier();
-        if (stats) flagged += static_cast<unsigned>(__builtin_popcount(frame_mask<kSixLanes, kSixFrames>(__builtin_amdgcn_ballot_w64(flag))));
-    }
-    guard_wave_done(p.stat, wg_done, WAVES, lane, flagged);
+#define MS_SIX64_IN float
+#define MS_SIX64_OUT float
+#include "whisper400_six64_body.inc"
+#undef MS_SIX64_OUT
+#undef MS_SIX64_IN
 }
 
 // The same kernel for the padded / mel-major layouts (interleave_frames, src/mel.rs:480-544; BatchDesc::out_width / mel_major): the units

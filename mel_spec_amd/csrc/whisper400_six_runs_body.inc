@@ -1,5 +1,6 @@
 // whisper400_six_runs_body.inc -- the body of whisper400_six_runs_kernel, included once per kernel that shares it (whisper400_kernels.hpp) with
-// MS_SIX_RUNS_WAVES = the waves of its workgroup.  Text, not a function: the sixteen-wave kernel of the bench workload must compile to the
+// MS_SIX_RUNS_WAVES = the waves of its workgroup and MS_SIX_RUNS_IN / MS_SIX_RUNS_OUT = its sample and row types (float; the *_io_* kernels of
+// whisper400_io_kernels.hpp: their template parameters).  Text, not a function: the sixteen-wave kernel of the bench workload must compile to the
 // instructions it has (a shared __device__ body taking the parameters by reference changed its schedule: 5552 -> 5571 instructions).
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *blob = lds;
@@ -23,7 +24,7 @@
 #ifdef MELSPEC_LAB_STAMPS
     if (guard && tid == 0) p.fix.list[p.b.n_units + 4096 + (uint64_t)gridDim.x * MS_SIX_RUNS_WAVES + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
-    ClipRun cr;
+    ClipRunT<MS_SIX_RUNS_IN, MS_SIX_RUNS_OUT> cr;
     if (!cr.init(p.b, (uint64_t)xcd_logical_block() * MS_SIX_RUNS_WAVES + wave, (uint64_t)gridDim.x * MS_SIX_RUNS_WAVES)) {
         if (guard && p.fix.vote != nullptr && blockIdx.x < p.fix.vote_groups) vote_cast(p.fix, wg_done + 2, MS_SIX_RUNS_WAVES, lane, 0, 0);
         guard_wave_done(p.fix, wg_done, MS_SIX_RUNS_WAVES, lane, 0);
@@ -43,7 +44,7 @@
         const uint64_t f0 = (cr.unit - cr.c_start) * kSixFrames;
         const uint64_t left = cr.c_frames - f0;
         nv = left < (uint64_t)kSixFrames ? (int)left : kSixFrames;
-        const float *src = cr.c_pcm + f0 * (uint64_t)p.hop;
+        const MS_SIX_RUNS_IN *src = cr.c_pcm + f0 * (uint64_t)p.hop;
         const bool act = in && fl < nv;
         MS_PRIO(0);
         six_phase1(fl, j, act, p.hop, blob, src, slice);
@@ -72,7 +73,7 @@
             six_phase3_finish<NSLOTS>(fl, j, act, n_mels, rise, fnext, slice, vals);
         }
         __builtin_amdgcn_wave_barrier();
-        float *out_tile = cr.c_out + f0 * (uint64_t)n_mels;
+        MS_SIX_RUNS_OUT *out_tile = cr.c_out + f0 * (uint64_t)n_mels;
         const bool flag = six_phase4<NSLOTS, false, true>(fl, j, act, act, n_mels, slice, vals, out_tile, 0);
         __builtin_amdgcn_wave_barrier();
         uint64_t any = 0;
@@ -122,7 +123,7 @@
         uint64_t e = 0;
         if (lane == 0) e = notes[k];
         e = scalar64(e);
-        const UnitLoc loc = locate_unit(p.b, e >> 8);
+        const UnitLocT<MS_SIX_RUNS_IN, MS_SIX_RUNS_OUT> loc = locate_unit<MS_SIX_RUNS_IN, MS_SIX_RUNS_OUT>(p.b, e >> 8);
         const uint64_t f0 = loc.unit * kSixFrames;
         redone += six_fix_unit<NSLOTS, Lens, false>(static_cast<unsigned>(e & 0xff), tlane, p.hop, n_mels, p.slots, blob, tslice, p.fix, tw,
                                           loc.pcm + f0 * (uint64_t)p.hop, loc.out + f0 * (uint64_t)n_mels, 0);

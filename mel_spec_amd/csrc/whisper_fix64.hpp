@@ -67,6 +67,16 @@ MS_DEV void fix_load2(const float *p, float &a, float &b) {
     a = p[0]; b = p[1];
 #endif
 }
+// ... from 16-bit PCM: sample * 2^-15, exact (load2_unaligned's int16_t form in whisper_wave.hpp)
+MS_DEV void fix_load2(const int16_t *p, float &a, float &b) {
+#if defined(__HIPCC__)
+    typedef short s2u __attribute__((ext_vector_type(2), aligned(2)));
+    const s2u v = *reinterpret_cast<const s2u *>(p);
+    a = static_cast<float>(v.x) * 0x1p-15f; b = static_cast<float>(v.y) * 0x1p-15f;
+#else
+    a = static_cast<float>(p[0]) * 0x1p-15f; b = static_cast<float>(p[1]) * 0x1p-15f;
+#endif
+}
 
 // step 1: window + DFT-8 over n1 for column n2 = lane
 MS_DEV void fix_step1(int lane, const float *MS_RESTRICT frame, const double *MS_RESTRICT tab, double *MS_RESTRICT z) {
@@ -136,7 +146,8 @@ MS_DEV void fix_step4(int lane, const double *MS_RESTRICT tab, const double *MS_
 struct FixSamples {
     float a[8], b[8];
 };
-MS_DEV void fix_load_samples(int lane, const float *MS_RESTRICT frame, FixSamples &s) {
+template <class In>
+MS_DEV void fix_load_samples(int lane, const In *MS_RESTRICT frame, FixSamples &s) {
     const int l = lane < 25 ? lane : 0;          // every lane loads (no divergent branch around the loads); lanes >= 25 are not used
 #pragma unroll
     for (int n1 = 0; n1 < 8; ++n1) fix_load2(frame + 2 * ((25 * n1 + 8 * l) % 200), s.a[n1], s.b[n1]);

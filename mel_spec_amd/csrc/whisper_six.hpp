@@ -112,10 +112,12 @@ using LensSix64 = LensSixStatic<64, 2, 2, 2, 3, 4, 6, 10, 10>;
 using LensSix40 = LensSixStatic<40, 2, 3, 5, 11, 14>;
 
 // ---- phase 1: window, DFT-20 over n1 of column t, twiddle W_200^{t*k1}, 20 exchange rows ----------------------
-MS_DEV void six_phase1(int fl, int t, bool active, int hop, const float *blob, const float *gsrc /* unit's first sample */,
+// In: the sample type (float; int16_t in the *_io_* kernels, converted by load2_unaligned)
+template <class In>
+MS_DEV void six_phase1(int fl, int t, bool active, int hop, const float *blob, const In *gsrc /* unit's first sample */,
                        float *slice) {
     if (!active) return;
-    const float *s = gsrc + fl * hop + 2 * t;
+    const In *s = gsrc + fl * hop + 2 * t;
     cf x[20];
     const float *w = blob + SixBlob::kWin + t * SixBlob::kWinStride;
     // All twenty loads first, and a scheduling barrier behind them.  Left to itself the machine scheduler sometimes sinks them into the
@@ -289,9 +291,12 @@ struct alignas(8) SixI2 { int x, y; };
 // KEYS (mel-major stores feeding the TGA quantiser, tga_quant.hpp): *kmin / *kmax = the smallest / largest biased value this lane
 // stored, a zero column counting as 12 (12 * 0.25 - 3 == 0 exactly); lanes that store nothing leave them untouched.
 MS_DEV float six_out(int c) { return six_float(c) * 0.25f - 3.0f; }          // (x + 4) / 4 of the biased value
-template <int NSLOTS, bool LAYOUT = false, bool GUARD = false, bool KEYS = false>
+// Out: the row type (float; _Float16 / __bf16 in the *_io_* kernels): the f32 value rounded to nearest even by the store's conversion, one
+// 16-bit store per lane and value (lane j writes o[i * kSixOwn]: consecutive lanes, consecutive values; rows may start at odd elements).
+// The guard's decision below is taken on the f32 value, so the vote does not depend on Out.
+template <int NSLOTS, bool LAYOUT = false, bool GUARD = false, bool KEYS = false, class Out = float>
 MS_DEV bool six_phase4(int fl, int j, bool store, bool valid, int n_mels, const float *slice, const float (&vals)[NSLOTS],
-                       float *out_tile, long long row_w, int *kmin = nullptr, int *kmax = nullptr) {
+                       Out *out_tile, long long row_w, int *kmin = nullptr, int *kmax = nullptr) {
     if (!LAYOUT) { valid = true; row_w = 0; }
     if (!store || j >= kSixOwn) return false;
     int lo = 0;          // bits of (frame maximum - 8), biased
@@ -303,7 +308,7 @@ MS_DEV bool six_phase4(int fl, int j, bool store, bool valid, int n_mels, const 
         const int m1 = six_imax(six_imax(b.x, b.y), six_imax(b.z, b.w));
         lo = six_bits(six_float(six_imax(six_imax(m0, m1), six_imax(c.x, c.y))) - 8.0f);      // >= -2: negative only when every band sits on the floor
     }
-    float *o = row_w ? out_tile + static_cast<long long>(j) * row_w + fl : out_tile + static_cast<long long>(fl) * n_mels + j;
+    Out *o = row_w ? out_tile + static_cast<long long>(j) * row_w + fl : out_tile + static_cast<long long>(fl) * n_mels + j;
     const long long step = row_w ? kSixOwn * row_w : kSixOwn;
     int cmin = 0x7f000000, cmax = 0;
 #pragma unroll
@@ -312,7 +317,7 @@ MS_DEV bool six_phase4(int fl, int j, bool store, bool valid, int n_mels, const 
         if (m < n_mels) {
             // vals >= 6 > 0: the integer order is the float order, also against a negative lo; a zero column is the value 12
             const int c = valid ? six_imax(six_bits(vals[i]), lo) : 0x41400000;
-            o[i * step] = six_out(c);
+            o[i * step] = static_cast<Out>(six_out(c));
             if (GUARD || KEYS) cmin = six_imin(cmin, c);
             if (KEYS) cmax = six_imax(cmax, c);
         }

@@ -72,9 +72,10 @@ struct Six64Layout {
 static_assert(Six64Layout::slice_doubles() * 2 >= SixLayout::kPmaxOff + kSixFrames * SixLayout::kPmaxStride, "the f32 power rows and maxima alias the head of the slice");
 
 // ---- phase 1: window (f64), DFT-20 over n1 of column t, twiddle W_200^{t k1}: the twenty exchange values of this lane ---------------------
-MS_DEV void six64_phase1(int fl, int t, bool active, int hop, const double *MS_RESTRICT tb, const float *gsrc /* unit's first sample */, cd (&x)[20]) {
+template <class In>
+MS_DEV void six64_phase1(int fl, int t, bool active, int hop, const double *MS_RESTRICT tb, const In *gsrc /* unit's first sample */, cd (&x)[20]) {
     if (!active) return;
-    const float *s = gsrc + fl * hop + 2 * t;
+    const In *s = gsrc + fl * hop + 2 * t;
     f2 sv[20];
 #pragma unroll
     for (int n1 = 0; n1 < 20; ++n1) sv[n1] = load2_unaligned(s + 20 * n1);
@@ -174,8 +175,13 @@ MS_DEV void six64_phase2(int fl, int j, bool active, const double *MS_RESTRICT t
 // kernel's loop body and handed to the step functions one `if (active)` at a time they are phi nodes of the unit loop -- for the lanes
 // without a frame "the value of the previous iteration" -- and 160 VGPRs stay live around the whole loop (the first build spilled 290).
 // LDS operations of a wave execute in program order, divergent or not; the wave barriers only pin the compiler's order.
-MS_DEV void six64_phases12(int fl, int j, bool active, int rofs, int hop, const double *MS_RESTRICT tb, const float *gsrc, double *rows, float *slice) {
+template <class In>
+MS_DEV void six64_phases12(int fl, int j, bool active, int rofs, int hop, const double *MS_RESTRICT tb, const In *gsrc, double *rows, float *slice) {
     if (!active) return;
+    // 16-bit PCM: the lane's frame offsets (fl * hop as a 64-bit element offset ...) are made products of THIS unit.  As loop invariants they
+    // were one register pair too many for the fifteen-slot kernel at 168 VGPRs: spilled in front of the unit loop and reloaded from scratch
+    // inside it, in front of the unit's PCM loads (a scratch reload waits on vmcnt(0)).  The float kernels keep the form they were measured in.
+    if constexpr (!std::is_same_v<In, float>) asm volatile("" : "+v"(fl));
     cd u[10], v[10];
     {
         cd x[20];

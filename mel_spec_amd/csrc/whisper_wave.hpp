@@ -109,6 +109,19 @@ MS_DEV f2 load2_unaligned(const float *p) {
     return f2{p[0], p[1]};
 #endif
 }
+// The same pair from 16-bit PCM (the *_io_* kernels): one 4-byte load from a pointer that is only 2-byte aligned, then sample * 2^-15 --
+// exact (|v| <= 2^15 fits the 24-bit significand, the scale is a power of two), so the pair holds the bits the f32 path reads from a batch
+// converted by `v as f32 / 32768.0`.  The scale stays here, in front of the window multiply: folded into the window table the product
+// rounds differently once it is subnormal.
+MS_DEV f2 load2_unaligned(const int16_t *p) {
+#if defined(__HIPCC__)
+    typedef short s2u __attribute__((ext_vector_type(2), aligned(2)));
+    const s2u v = *reinterpret_cast<const s2u *>(p);
+    return f2{static_cast<float>(v.x) * 0x1p-15f, static_cast<float>(v.y) * 0x1p-15f};
+#else
+    return f2{static_cast<float>(p[0]) * 0x1p-15f, static_cast<float>(p[1]) * 0x1p-15f};
+#endif
+}
 
 // ---- phase 1 -----------------------------------------------------------------------------
 // The frame's samples come straight from global memory (L1/L2 absorb the 2.5x frame overlap).

@@ -52,6 +52,22 @@ def device_count() -> int:
     return n if n > 0 else 0
 
 
+# melspec_hip.h: MELSPEC_PCM_* / MELSPEC_OUT_*
+PCM_F32, PCM_S16 = 0, 1
+OUT_F32, OUT_F16, OUT_BF16 = 0, 1, 2
+_OUT_NUMPY = {OUT_F32: np.float32, OUT_F16: np.float16, OUT_BF16: np.uint16}      # bf16: the bit patterns
+
+
+def _out_code(out_dtype) -> int:
+    if out_dtype is None or out_dtype in (OUT_F32, "f32", np.float32):
+        return OUT_F32
+    if out_dtype in ("f16", np.float16) or (out_dtype == OUT_F16 and not isinstance(out_dtype, bool)):
+        return OUT_F16
+    if out_dtype in ("bf16", "bfloat16") or (out_dtype == OUT_BF16 and not isinstance(out_dtype, bool)):
+        return OUT_BF16
+    raise ValueError(f"out_dtype must be None / 'f32', 'f16' or 'bf16', not {out_dtype!r}")
+
+
 def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
@@ -162,8 +178,23 @@ class HipMelSpectrogram:
             self.set_precision("f64" if env == "1" else "f32")
 
     # -- reference surface --------------------------------------------------------------
-    def compute_mel_spectrogram(self, samples) -> np.ndarray:
-        """&[f32] -> [frames][n_mels] f32 (Vec<Vec<f32>> in the reference)."""
+    def compute_mel_spectrogram(self, samples, out_dtype=None) -> np.ndarray:
+        """&[f32] -> [frames][n_mels] f32 (Vec<Vec<f32>> in the reference).
+        Additive: an np.int16 array is taken as 16-bit PCM (value = sample / 32768, exactly) and crosses the bus as such; out_dtype
+        "f16" (or np.float16) returns np.float16 rows, "bf16" the bfloat16 bit patterns as np.uint16 (numpy has no bfloat16) -- the f32
+        row values rounded to nearest even (melspec_compute_host_io)."""
+        a = np.asarray(samples)
+        pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        out = _out_code(out_dtype)
+        if pcm != PCM_F32 or out != OUT_F32:
+            x = np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1)
+            nf = self.num_frames(x.shape[0])
+            res = np.empty((nf, self.n_mels), _OUT_NUMPY[out])
+            got = C.c_size_t(0)
+            _check(lib().melspec_compute_host_io(self._h, x.ctypes.data_as(C.c_void_p), pcm, x.shape[0], res.ctypes.data_as(C.c_void_p), out,
+                                                 res.size, C.byref(got)))
+            assert got.value == nf
+            return res
         x = _f32(samples).reshape(-1)
         nf = self.num_frames(x.shape[0])
         out = np.empty((nf, self.n_mels), np.float32)
@@ -315,6 +346,27 @@ class HipMelSpectrogram:
         _check(lib().melspec_compute_ragged_device(
             self._h, C.c_void_p(d_pcm), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
             C.c_void_p(d_out), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
+
+    # -- 16-bit ends: int16 PCM in, f16 / bf16 rows out (melspec_hip.h; codes PCM_* / OUT_* of this module) ---------------------------
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(lib().melspec_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
+                                  stream: int = 0) -> None:
+        """compute_uniform_device on int16 samples and / or into f16 / bf16 rows; strides count elements."""
+        _check(lib().melspec_compute_uniform_device_io(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
+                                                       C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
+
+    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
+                                 stream: int = 0) -> None:
+        """compute_ragged_device on int16 samples and / or into f16 / bf16 rows; offsets and lengths count elements."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        _check(lib().melspec_compute_ragged_device_io(
+            self._h, C.c_void_p(d_pcm), int(pcm_dtype), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
+            C.c_void_p(d_out), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
 
     def compute_ragged_device_desc(self, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
                                    max_total_frames: int, stream: int = 0) -> None:

@@ -739,6 +739,14 @@ unsafe extern "C" {
                                      d_out: *mut f32, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
     fn melspec_compute_ragged_device_desc(ctx: *mut Ctx, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
                                           d_out: *mut f32, d_out_offsets: *const u64, max_total_frames: u64, stream: *mut c_void) -> c_int;
+    // int16 PCM in / f16, bf16 rows out
+    fn melspec_supports_io(ctx: *const Ctx, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_compute_uniform_device_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                         d_out: *mut c_void, out_dtype: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_compute_ragged_device_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, h_offsets: *const u64, h_lengths: *const u64,
+                                        n_clips: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
+    fn melspec_compute_host_io(ctx: *mut Ctx, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, out: *mut c_void, out_dtype: c_int,
+                               out_capacity_elems: usize, n_frames: *mut usize) -> c_int;
     fn melspec_interleaved_width(ctx: *const Ctx, n_samples: usize, min_width: usize) -> usize;
     fn melspec_compute_uniform_device_interleaved(ctx: *mut Ctx, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32,
                                                   d_out: *mut f32, major_column_order: c_int, min_width: u64, stream: *mut c_void) -> c_int;
@@ -783,6 +791,11 @@ unsafe extern "C" {
     fn melspec_tga_synchronize(q: *mut Tga) -> c_int;
 }
 
+pub const PCM_F32: c_int = 0; // MELSPEC_PCM_F32
+pub const PCM_S16: c_int = 1; // MELSPEC_PCM_S16
+pub const OUT_F32: c_int = 0; // MELSPEC_OUT_F32
+pub const OUT_F16: c_int = 1; // MELSPEC_OUT_F16
+pub const OUT_BF16: c_int = 2; // MELSPEC_OUT_BF16
 const STFT_F32: c_int = 0; // MELSPEC_STFT_F32
 const STFT_F64: c_int = 1; // MELSPEC_STFT_F64
 
@@ -879,6 +892,48 @@ impl HipMelSpectrogram {
                                           std::ptr::null(), std::ptr::null_mut())
         })?;
         Ok(frames)
+    }
+
+    /// Does this context take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` rows (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?
+    pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_supports_io(self.ctx, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+
+    /// `compute_uniform_device` on int16 samples and / or into f16 / bf16 rows (strides count elements, not bytes).
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device pointers valid for `n_clips * clip_stride` samples of `pcm_dtype` and
+    /// `n_clips * frames * n_mels` values of `out_dtype`.
+    pub unsafe fn compute_uniform_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                            d_out: *mut c_void, out_dtype: i32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_compute_uniform_device_io(self.ctx, d_pcm, pcm_dtype as c_int, clip_stride, clip_len, n_clips, d_out, out_dtype as c_int, stream))
+    }
+
+    /// `compute_ragged_device` on int16 samples and / or into f16 / bf16 rows; the clips' frames are packed back to back.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`, and `d_out` must hold the frames of all clips in `out_dtype`.
+    pub unsafe fn compute_ragged_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, offsets: &[u64], lengths: &[u64], d_out: *mut c_void,
+                                           out_dtype: i32, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        check(melspec_compute_ragged_device_io(self.ctx, d_pcm, pcm_dtype as c_int, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_out,
+                                               out_dtype as c_int, std::ptr::null(), stream))
+    }
+
+    /// `compute_mel_spectrogram` on 16-bit PCM (value = sample / 32768, exactly) into f16 rows, returned as their bit patterns: the
+    /// int16 bytes are what crosses the bus.
+    pub fn compute_mel_spectrogram_s16_f16(&mut self, samples: &[i16]) -> Result<Vec<Vec<u16>>, HipError> {
+        let frames = unsafe { melspec_num_frames(self.ctx, samples.len()) };
+        if frames == 0 {
+            return Ok(Vec::new());
+        }
+        let mut flat = vec![0u16; frames * self.n_mels];
+        let mut got = 0usize;
+        check(unsafe {
+            melspec_compute_host_io(self.ctx, samples.as_ptr() as *const c_void, PCM_S16, samples.len(), flat.as_mut_ptr() as *mut c_void, OUT_F16,
+                                    flat.len(), &mut got)
+        })?;
+        Ok(flat.chunks(self.n_mels).take(got).map(|row| row.to_vec()).collect())
     }
 
     /// The same with the clip table itself in device memory (a segmenter or VAD on the GPU wrote it): nothing is copied back.
