@@ -148,6 +148,10 @@ int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float
         uint32_t *ord = blk + blk_words;
         for (uint32_t c = 0; c < n_clips; ++c) ord[c] = c;
         std::stable_sort(ord, ord + n_clips, [&](uint32_t a, uint32_t b2) { return frames[a] > frames[b2]; });
+        // the order ends at the last clip with a frame: the clips without one sort to the end, and a ticket past the end reads "the batch is
+        // used up" (fbank512_clip_kernel's clip_queue_get) -- a wave that could skip clips without arriving for them would break the bound
+        // its ring of clip ids relies on
+        for (uint32_t i = n_clips; i > 0 && frames[ord[i - 1]] == 0; --i) ord[i - 1] = 0xffffffffu;
         ord[n_clips] = 0;       // the ticket counter
     }
     // the upload is a kernel on the launch stream that reads the pinned slot over the bus: an SDMA copy sits in another

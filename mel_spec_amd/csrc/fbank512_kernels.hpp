@@ -427,8 +427,10 @@ struct ClipCmnShared {
 };
 
 // The workgroup's n-th clip of a ragged batch (0xffffffff: the batch is used up).  Whichever wave asks first takes a ticket from the
-// device counter and publishes the clip in LDS; the others read it there.  No wave is ever more than two clips ahead of another (the
-// subtraction of clip c waits for every wave's run of clip c), so a ring of eight cannot wrap.
+// device counter and publishes the clip in LDS; the others read it there.  A ring of eight cannot wrap: a wave asks for clip n + 1 only
+// after its arrival for clip n, and for clip n + 2 only after the wait for clip n's means, which every wave's arrival for clip n precedes
+// -- so no wave is more than two clips ahead of another.  Every clip the queue hands out goes through that arrival and that wait, the
+// frameless ones included; the host hands out none of those (plan_ragged ends the order at the last clip with a frame).
 template <int WAVES>
 MS_DEV uint32_t clip_queue_get(ClipCmnShared<WAVES> *sh, unsigned n, int lane, const BatchDesc &b) {
     unsigned id = 0xffffffffu;
@@ -565,8 +567,7 @@ __global__ __launch_bounds__(8 * 64, 1) void fbank512_clip_kernel(const FbankCli
         if (RAGGED) {
             clip = clip_queue_get<WAVES>(sh, seq, lane, p.b);
             if (clip == 0xffffffffu) break;
-            frames = scalar64(p.b.d_frames[clip]);
-            if (frames == 0) continue;         // zeros((0, num_mel_bins)), src/fbank.rs:147-149: nothing to write
+            frames = scalar64(p.b.d_frames[clip]);         // never 0: clips without a frame (zeros((0, num_mel_bins)), src/fbank.rs:147-149) are not in the order
             pcm = p.b.pcm + scalar64(p.b.d_off[clip]);
             out = p.b.out + scalar64(p.b.d_out_off[clip]);
         } else {
@@ -623,9 +624,14 @@ __global__ __launch_bounds__(8 * 64, 1) void fbank512_clip_kernel(const FbankCli
         // this wave's share of the previous clip's subtraction (its means were published a whole run ago: the wait does not spin).
         // Spreading it over the units of the run -- two pieces loaded after phase 1, stored at the end of the unit -- was measured
         // and is slower (+0.08 ms against +0.07 ms, profiles/r02_fbank.txt): the cost is the extra traffic, not this wave's stall
-        if (gen > 0 && !(q.lab_skip & 1) && q.d_means == nullptr) {
+        // The wait is also what keeps the waves within two clips of each other, and the parity slots depend on that: the means of clip
+        // c - 1 are published after all eight arrivals of c - 1, each of which came after that wave's wait for clip c - 2 -- so clip c - 2
+        // is folded before any wave writes part[par] or arrives on arrived[par] for clip c.  The split output skips the subtraction only:
+        // without the wait a wave with an empty share ran ahead and arrived for clip c on a count that clip c - 2 had not completed
+        // (tests/test_fbank_tiny_clips.py)
+        if (gen > 0) {
             sub.wait(sh, par ^ 1, prev_turn, lane);
-            sub.finish(wave);
+            if (!(q.lab_skip & 1) && q.d_means == nullptr) sub.finish(wave);
         }
         // the wave's column sums: frame positions (0+1)+(2+3), then lanes of position 0 write them
 #pragma unroll
@@ -658,9 +664,9 @@ __global__ __launch_bounds__(8 * 64, 1) void fbank512_clip_kernel(const FbankCli
         sub.begin(out, frames, nm, wave, lane);        // this clip is the next one to subtract
         ++gen;
     }
-    if (gen > 0 && !(q.lab_skip & 1) && q.d_means == nullptr) {
+    if (gen > 0) {
         sub.wait(sh, (gen - 1) & 1, (gen - 1) / 2 + 1, lane);
-        sub.finish(wave);
+        if (!(q.lab_skip & 1) && q.d_means == nullptr) sub.finish(wave);
     }
 }
 

@@ -47,7 +47,7 @@ struct BatchDesc {
     const uint32_t *d_unit_block;   // ragged: clip that holds unit k * kUnitBlock
     const uint64_t *d_n_units;      // ragged batches planned on the device (plan_ragged_device_kernel): the unit count lives here and
                                     // n_units above is the host's upper bound (grid and scratch sizes)
-    const uint32_t *d_order;        // ragged, host-planned, optional: the clips longest first (whole-clip kernels take them in this order)
+    const uint32_t *d_order;        // ragged, host-planned, optional: the clips with a frame, longest first, then 0xffffffff up to n_clips (whole-clip kernels take them in this order)
     uint32_t *d_ticket;             //   and the counter they take them from (zero when the launch starts)
     uint64_t stat_frames;           // frames of the batch as the planner counted them (host-planned ragged batches: the true total; 0: not set) -- the
                                     //   denominator of the guard statistics (n_units * frames_per_unit over-counts short clips up to 6 x)
