@@ -442,6 +442,32 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
 int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips,
                                    float *out, const uint64_t *out_offsets, size_t out_capacity_floats, uint64_t *total_columns);
 int melspec_blm_release_scratch(melspec_blm *b);   /* as melspec_fbank_release_scratch */
+
+/* ---- 16-bit ends for this frontend: int16 PCM in, f16 / bf16 features out ---------------------------------------------------------
+ * MELSPEC_PCM_* / MELSPEC_OUT_* as above, with the same meaning: a MELSPEC_PCM_S16 sample's value is int16 * 2^-15, exactly -- the
+ * call gives the bits of the f32 call on the batch converted by `v as f32 / 32768.0`, pre-emphasis (src/mel.rs:696-706) applied to the
+ * converted f32 samples with the same two roundings.  MELSPEC_OUT_F16 / _BF16: every element of [n_mels][cols] -- the zero columns
+ * from the valid frames up to cols (pad_to) included, a NaN staying a NaN -- is the f32 element the f32 call writes, rounded to nearest
+ * even ONCE.  With normalize_per_feature the statistics are those of the f32 rows (f32 left-fold mean, unbiased variance, + 1e-5) and
+ * only the final (v - mean) / sd is rounded: the mel kernel writes its f32 rows into a scratch of the context (grow-only,
+ * n_clips * n_mels * cols * 4 bytes, ragged: summed over the clips; given back by melspec_blm_release_scratch) and the normaliser
+ * reads them there and writes the 16-bit rows to the caller.  Without normalisation there is no scratch and no second pass.
+ * Strides, offsets, lengths and capacities count ELEMENTS, never bytes; only natural alignment of the element type is required (a
+ * ragged int16 clip may start at an odd sample, a 16-bit clip output at an odd element; mel rows start at odd elements whenever cols
+ * is odd).  Everything else -- valid / padded frame counts, empty clips, stream ordering, precision modes, error codes -- is that of
+ * melspec_blm_compute_uniform_device / _ragged_device / _host.  (F32, F32) is always supported and is the existing path.  The other
+ * five combinations are computed by the fused geometry (n_fft 512 / win_length 400) with the 80- or 128-mel Slaney bank, in both
+ * arithmetic modes and with any preemphasis, center, log_zero_guard, pad_to, normalize_per_feature (melspec_blm_supports_io == 1);
+ * every other context returns MELSPEC_ERR_UNSUPPORTED and does not touch the output. */
+int melspec_blm_supports_io(const melspec_blm *b, int pcm_dtype, int out_dtype);
+int melspec_blm_compute_uniform_device_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                          uint32_t n_clips, void *d_out, int out_dtype, void *stream);
+int melspec_blm_compute_ragged_device_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                         const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
+                                         const uint64_t *h_out_offsets, void *stream);
+/* melspec_blm_compute_host with 16-bit ends: the int16 bytes are what crosses the bus, and so are the 16-bit features. */
+int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
+                                size_t out_capacity_elems, size_t *rows, size_t *cols);
 /* Arithmetic of the fused kernel (n_fft 512 / win_length 400, 80 or 128 mels).  MELSPEC_PRECISION_F32: f32 window, FFT, power and
  * projection -- the reference's own arithmetic type for this frontend (src/mel.rs:251-252,356-357), as far from the f64 evaluation of
  * its definition as upstream's f32 code is (2.4e-4 on jfk_f32le.wav) at ~0.8 x the time.  AUTO (default) / F64: f64 up to |X|^2, within 1e-4

@@ -211,6 +211,58 @@ private:
     melspec_fbank *fb_ = nullptr;
 };
 
+struct BatchLogMelConfig : melspec_blm_config {
+    BatchLogMelConfig() { melspec_blm_default_config(this); }   // BatchLogMelConfig::default, src/mel.rs:189-208
+};
+
+// BatchLogMelSpectrogram (src/mel.rs:239-396): the NeMo / Parakeet frontend, feature-major (n_mels, cols)
+class BatchLogMelSpectrogram {
+public:
+    explicit BatchLogMelSpectrogram(const BatchLogMelConfig &cfg = BatchLogMelConfig(), int device = -1) : n_mels_(static_cast<std::size_t>(cfg.n_mels)) {
+        detail::check(melspec_blm_create(&b_, device, &cfg), true);
+    }
+    ~BatchLogMelSpectrogram() { melspec_blm_destroy(b_); }
+    BatchLogMelSpectrogram(const BatchLogMelSpectrogram &) = delete;
+    BatchLogMelSpectrogram &operator=(const BatchLogMelSpectrogram &) = delete;
+
+    Array2f compute(const std::vector<float> &samples) {
+        Array2f a;
+        a.rows = n_mels_;
+        a.cols = melspec_blm_padded_frames(b_, samples.size());
+        a.data.assign(a.rows * a.cols, 0.0f);
+        std::size_t rows = 0, cols = 0;
+        detail::check(melspec_blm_compute_host(b_, samples.data(), samples.size(), a.data.data(), a.data.size(), &rows, &cols), false);
+        return a;
+    }
+
+    // additive: 16-bit ends (MELSPEC_PCM_*, MELSPEC_OUT_* of melspec_hip.h); strides, offsets and lengths count elements
+    bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_blm_supports_io(b_, pcm_dtype, out_dtype) != 0; }
+    void compute_uniform_device_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_out,
+                                   int out_dtype, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_uniform_device_io(b_, d_pcm, pcm_dtype, clip_stride, clip_len, n_clips, d_out, out_dtype, stream), false);
+    }
+    void compute_ragged_device_io(const void *d_pcm, int pcm_dtype, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths,
+                                  void *d_out, int out_dtype, const std::uint64_t *out_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_ragged_device_io(b_, d_pcm, pcm_dtype, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), d_out,
+                                                           out_dtype, out_offsets, stream), false);
+    }
+    // compute() on 16-bit PCM (value = sample / 32768, exactly) into out_dtype features (MELSPEC_OUT_F16 / _BF16), returned as their bit
+    // patterns, (n_mels, cols) row-major: the int16 bytes are what crosses the bus
+    std::vector<std::uint16_t> compute_s16(const std::vector<std::int16_t> &samples, int out_dtype, std::size_t *cols = nullptr) {
+        std::vector<std::uint16_t> out(n_mels_ * melspec_blm_padded_frames(b_, samples.size()));
+        std::size_t r = 0, c = 0;
+        detail::check(melspec_blm_compute_host_io(b_, samples.data(), MELSPEC_PCM_S16, samples.size(), out.data(), out_dtype, out.size(), &r, &c), false);
+        if (cols) *cols = c;
+        return out;
+    }
+    void synchronize(void *stream = nullptr) { detail::check(melspec_blm_synchronize(b_, stream), false); }
+    void release_scratch() { detail::check(melspec_blm_release_scratch(b_), false); }
+
+private:
+    melspec_blm *b_ = nullptr;
+    std::size_t n_mels_ = 0;
+};
+
 // src/quant.rs: quantize / dequantize / tga_8bit / parse_tga_8bit, same names and return shapes
 struct QuantizationRange { float min, max; };
 

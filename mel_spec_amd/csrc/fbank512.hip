@@ -2,7 +2,22 @@
 // context (melspec_fbank_*, src/fbank.rs:94-313) and the NeMo / Parakeet frontend (melspec_blm_*, src/mel.rs:239-396); Whisper at n_fft = 512
 // reaches the same kernels through launch_whisper512.
 #include "host_common.hpp"
-#include "fbank512_kernels.hpp"
+#include "fbank512_io_kernels.hpp"
+
+namespace melspec {
+// emitted by fbank512_io.hip: the NeMo frontend with int16 PCM in and / or f16, bf16 rows out
+#define MS_IO_EXTERN(In, Out)                                                                                                       \
+    extern template __global__ void fbank512_nemo_io_kernel<double, 8, kBlmSlots, LensSlaney128, In, Out>(const FbankFastParams);  \
+    extern template __global__ void fbank512_nemo_io_kernel<double, 8, kFbSlots, LensSlaney80, In, Out>(const FbankFastParams);    \
+    extern template __global__ void fbank512_nemo_io_kernel<float, 12, kBlmSlots, LensSlaney128, In, Out>(const FbankFastParams);  \
+    extern template __global__ void fbank512_nemo_io_kernel<float, 12, kFbSlots, LensSlaney80, In, Out>(const FbankFastParams);
+MS_IO_COMBOS(MS_IO_EXTERN)
+#undef MS_IO_EXTERN
+extern template __global__ void blm_normalize_io_kernel<io_f16>(const BlmNormIoParams);
+extern template __global__ void blm_normalize_io_kernel<io_bf16>(const BlmNormIoParams);
+extern template __global__ void blm_normalize_ragged_io_kernel<io_f16>(const BlmNormRaggedIoParams);
+extern template __global__ void blm_normalize_ragged_io_kernel<io_bf16>(const BlmNormRaggedIoParams);
+}  // namespace melspec
 
 namespace {
 // Lens: compile-time slot lengths when the context's filterbank is one of the default banks (8-wave shape only; the
@@ -528,6 +543,9 @@ struct melspec_blm {
     Fused512F32 f32;            // MELSPEC_PRECISION_F32: the reference's own arithmetic type for this frontend (src/mel.rs:251-252,356-357)
     DevBuf h2d, d2h;
     HostPipe pipe;              // melspec_blm_compute_batch_host
+    DevBuf rows32;              // normalize_per_feature with f16 / bf16 rows out: the f32 rows between the mel kernel and the normaliser
+    hipStream_t rows32_stream = nullptr;    //   (n_clips * n_mels * cols * 4 bytes; grow-only, used in stream order like aux)
+    bool rows32_used = false;
 };
 
 namespace {
@@ -540,6 +558,118 @@ uint64_t blm_valid_frames(const melspec_blm *b, uint64_t n) {       // src/mel.r
 uint64_t blm_padded(const melspec_blm *b, uint64_t frames) {         // pad_len, src/mel.rs:751-756
     const uint64_t p = b->cfg.pad_to;
     return p == 0 ? frames : (frames + p - 1) / p * p;
+}
+
+// ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io) ---------------------------------------------------------------------
+// the contexts whose kernels have the instantiations: the fused geometry on eight f64 waves with one of the compile-time Slaney banks
+bool blm_io_ok(const melspec_blm *b) { return b->fast && b->waves == 8 && nemo_f32_bank(b->ft.slots); }
+inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
+inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
+// 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
+int blm_io_args(const melspec_blm *b, int pcm_dtype, int out_dtype, int &io) {
+    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
+    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
+        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    if (io && !blm_io_ok(b)) {
+        g_last_error = "int16 PCM / f16, bf16 rows are computed by the n_fft = 512 / win_length = 400 frontend with the 80- or 128-mel Slaney bank only; this context is n_fft = " +
+                       std::to_string(b->cfg.n_fft) + ", win_length = " + std::to_string(b->cfg.win_length) + ", n_mels = " + std::to_string(b->cfg.n_mels) +
+                       (b->fast ? " (another filterbank)" : "");
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    return MELSPEC_OK;
+}
+
+struct NemoIoKernels {
+    void (*f64_128)(const FbankFastParams);
+    void (*f64_80)(const FbankFastParams);
+    void (*f32_128)(const FbankFastParams);
+    void (*f32_80)(const FbankFastParams);
+};
+template <class In, class Out>
+NemoIoKernels nemo_io_kernels_of() {
+    return NemoIoKernels{&fbank512_nemo_io_kernel<double, 8, kBlmSlots, LensSlaney128, In, Out>, &fbank512_nemo_io_kernel<double, 8, kFbSlots, LensSlaney80, In, Out>,
+                         &fbank512_nemo_io_kernel<float, 12, kBlmSlots, LensSlaney128, In, Out>, &fbank512_nemo_io_kernel<float, 12, kFbSlots, LensSlaney80, In, Out>};
+}
+// the mel kernel of a (sample, row) combination on fp, a batch planned like the f32 call's: launch_fused512's grids and LDS sizes
+int launch_nemo_io(melspec_blm *b, FbankFastParams fp, int io, hipStream_t s) {
+    static const NemoIoKernels table[2][3] = {{NemoIoKernels{}, nemo_io_kernels_of<float, io_f16>(), nemo_io_kernels_of<float, io_bf16>()},
+                                              {nemo_io_kernels_of<io_s16, float>(), nemo_io_kernels_of<io_s16, io_f16>(), nemo_io_kernels_of<io_s16, io_bf16>()}};
+    static std::atomic<uint64_t> attr_done[2][3];
+    const int pcm = io & 15, out = io >> 4;
+    if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || io == 0 || !blm_io_ok(b)) return fail(MELSPEC_ERR_INTERNAL, "launch_nemo_io: no such combination");
+    const NemoIoKernels &k = table[pcm][out];
+    if (!device_done(attr_done[pcm][out])) {
+        int rc = allow_big_lds(k.f64_128, "hipFuncSetAttribute(fbank512_nemo_io_kernel<double, 128 mels>)");
+        if (!rc) rc = allow_big_lds(k.f64_80, "hipFuncSetAttribute(fbank512_nemo_io_kernel<double, 80 mels>)");
+        if (!rc) rc = allow_big_lds(k.f32_128, "hipFuncSetAttribute(fbank512_nemo_io_kernel<float, 128 mels>)");
+        if (!rc) rc = allow_big_lds(k.f32_80, "hipFuncSetAttribute(fbank512_nemo_io_kernel<float, 80 mels>)");
+        if (rc) return rc;
+        mark_device_done(attr_done[pcm][out]);
+    }
+    const bool wide = fb_lens_match<LensSlaney128>(b->ft.slots);
+    if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) {
+        f32_params(b->f32, fp);
+        fp.b.sync_rounds = 0;        // StagedRows instead of RoundSync
+        const unsigned grid = grid_for_xcd((fp.b.n_units + kFused512F32Waves - 1) / kFused512F32Waves, b->dev.cus, 1);
+        hipLaunchKernelGGL(wide ? k.f32_128 : k.f32_80, dim3(grid), dim3(kFused512F32Waves * 64), b->f32.lds, s, fp);
+    } else {
+        static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);
+        const unsigned grid = grid_for_xcd((fp.b.n_units + 7) / 8, b->dev.cus, per_cu);
+        hipLaunchKernelGGL(wide ? k.f64_128 : k.f64_80, dim3(grid), dim3(512), b->fast_lds, s, fp);
+    }
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+// the f32 rows of a normalised call with 16-bit rows out: `floats` of them, on stream s
+int blm_rows32(melspec_blm *b, uint64_t floats, hipStream_t s, float *&rows) {
+    if (b->rows32_used && b->rows32_stream != s) HIP_TRY(hipStreamSynchronize(b->rows32_stream));
+    b->rows32_used = true; b->rows32_stream = s;
+    // + 16: the normaliser reads whole 16-byte granules, the last row's last one included (growing frees the old buffer: hipFree waits for the device)
+    const int rc = b->rows32.ensure(static_cast<size_t>(floats) * sizeof(float) + 16);
+    rows = static_cast<float *>(b->rows32.p);
+    return rc;
+}
+
+// rows staged per workgroup (`per`, 0: a row does not fit), the row stride in LDS and the workgroups per CU of the normalisers.  The
+// number of rows per workgroup decides how many threads share a row's sum of squares, i.e. the order of that sum: the in-place f32
+// passes and the passes that write 16-bit rows take their shape from the same function, whatever else the latter keep in LDS, so that the
+// statistics of a 16-bit call are those of the f32 call bit for bit.
+// uniform batches, rows of `valid` frames: four workgroups of <= 38 KB per CU measured best (1024 x 10 s x 128 mels, ms per call incl. the
+// 0.72 ms mel kernel: 150 KB x 1: 1.72, 76 x 2: 1.45, 50 x 3: 1.34, 38 x 4: 1.28, 25 x 6: 1.68); MELSPEC_NORM_KB / MELSPEC_NORM_PER_CU override
+void blm_norm_shape_uniform(uint64_t valid, size_t &stride, size_t &per, int &per_cu) {
+    stride = (static_cast<size_t>(valid) + 3 + 31) & ~static_cast<size_t>(31);  // whole groups of 32 floats (a row starts up to 3 floats into its first granule) ...
+    if ((stride / 4) % 2 == 0) stride += 4;                                       // ... and 4 * odd
+    static const int norm_kb = lab_int("MELSPEC_NORM_KB", 38, 8, 158);
+    static const int norm_per_cu = lab_int("MELSPEC_NORM_PER_CU", 4, 1, 16);
+    const size_t budget = static_cast<size_t>(norm_kb) * 1024 - (64 * 2 + kBlmNormThreads) * sizeof(float);
+    per = budget / (stride * sizeof(float));
+    per_cu = norm_per_cu;
+    if (per < 4) {                            // long rows (> ~25 s): one workgroup per CU with the whole LDS, up to ~6 min per row
+        per = (static_cast<size_t>(150) * 1024) / (stride * sizeof(float));
+        per_cu = 1;
+    }
+    if (per > 64) per = 64;
+}
+// ragged batches: rows staged whole in LDS like the uniform pass (sized for the longest clip), groups of rows from a counter
+void blm_norm_shape_ragged(uint64_t longest, size_t &stride, size_t &per, int &per_cu) {
+    stride = (static_cast<size_t>(longest) + 3 + 31) & ~static_cast<size_t>(31);
+    if ((stride / 4) % 2 == 0) stride += 4;
+    const size_t fixed = (2 * 64 + kBlmNormThreads + 4 * 64 + 4) * sizeof(float);
+    per = (static_cast<size_t>(38) * 1024 - fixed) / (stride * sizeof(float));
+    per_cu = 4;
+    if (per < 4) { per = (static_cast<size_t>(150) * 1024 - fixed) / (stride * sizeof(float)); per_cu = 1; }
+    if (per > 64) per = 64;
+}
+template <class K>
+int allow_norm_io(K f16, K bf16, std::atomic<uint64_t> &done, const char *name) {
+    if (device_done(done)) return MELSPEC_OK;
+    int rc = allow_big_lds(f16, name);
+    if (!rc) rc = allow_big_lds(bf16, name);
+    if (!rc) mark_device_done(done);
+    return rc;
 }
 }  // namespace
 
@@ -619,7 +749,7 @@ void melspec_blm_destroy(melspec_blm *b) {
     if (!b) return;
     if (b->dev.device >= 0) (void)hipSetDevice(b->dev.device);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-    b->d_blob.release(); b->f32.d_blob.release(); b->h2d.release(); b->d2h.release(); b->gt.release(); b->ragged.release(); b->aux.release(); b->pipe.release();
+    b->d_blob.release(); b->f32.d_blob.release(); b->h2d.release(); b->d2h.release(); b->gt.release(); b->ragged.release(); b->aux.release(); b->pipe.release(); b->rows32.release();
     delete b;
 }
 
@@ -641,17 +771,29 @@ int melspec_blm_precision(const melspec_blm *b) {       // the arithmetic the ne
 size_t melspec_blm_num_frames(const melspec_blm *b, size_t n) { return b ? static_cast<size_t>(blm_valid_frames(b, n)) : 0; }
 size_t melspec_blm_padded_frames(const melspec_blm *b, size_t n) { return b ? static_cast<size_t>(blm_padded(b, blm_valid_frames(b, n))) : 0; }
 
-int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
-                                       uint32_t n_clips, float *d_out, void *stream) {
+// The uniform batch of melspec_blm_compute_uniform_device and of its _io form.  io = pcm_dtype | out_dtype << 4 (blm_io_args): 0 is the
+// f32 call and launches exactly what it always did; otherwise vd_pcm / vd_out are int16 samples / f16, bf16 rows and the plan counts elements.
+static int blm_uniform(melspec_blm *b, const void *vd_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, void *vd_out, void *stream, int io) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     if (n_clips == 0) return MELSPEC_OK;
     const uint64_t valid = blm_valid_frames(b, clip_len), cols = blm_padded(b, valid);
     if (cols == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && ((reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1))))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     HIP_TRY(hipSetDevice(b->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
     const int nm = b->cfg.n_mels;
     int rc;
+    const float *d_pcm = static_cast<const float *>(vd_pcm);
+    float *d_out = static_cast<float *>(vd_out);
+    // 16-bit rows cannot be normalised in place: the mel kernel then writes f32 rows into the context's scratch and the normaliser reads them there
+    const int out_dtype = io >> 4;
+    const bool split = out_dtype != 0 && b->cfg.normalize_per_feature && valid > 0;
+    if (split) {
+        if ((rc = blm_rows32(b, static_cast<uint64_t>(n_clips) * nm * cols, s, d_out))) return rc;
+        io &= 15;
+    }
     if (!b->fast) {
         const BatchPlan pl = plan_uniform(d_pcm, d_out, clip_stride, valid, n_clips, nm, 1, cols, true);
         rc = launch_generic(b->gt, pl.desc, b->cfg.hop_length, 2, 1, 1, static_cast<double>(b->cfg.preemphasis), static_cast<double>(b->cfg.log_zero_guard),
@@ -674,12 +816,32 @@ int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint6
     fp.clip_len = static_cast<long long>(clip_len);
     fp.org0 = b->cfg.center ? -200 : 56;      // tap 0 of the window sits at position (512-400)/2 of the frame
     fp.slots = b->ft.slots;
-    if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
+    if (io) rc = launch_nemo_io(b, fp, io, s);
+    else if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
     else if (fb_lens_match<LensSlaney128>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
     else if (fb_lens_match<LensSlaney80>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
     else rc = b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
                                               : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
     if (rc) return rc;
+    }
+    if (split) {
+        // blm_normalize_kernel's shape (rows per workgroup, workgroups per CU) on rows read from the scratch and written to the caller's
+        BlmNormIoParams np{};
+        np.src = d_out; np.dst = vd_out; np.row_w = cols; np.valid = valid; np.n_clips = n_clips; np.n_mels = nm;
+        const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+        size_t stride, per;
+        int per_cu;
+        blm_norm_shape_uniform(valid, stride, per, per_cu);
+        np.rows_per_group = static_cast<int>(per);
+        np.lds_stride = static_cast<int>(stride);
+        static std::atomic<uint64_t> attr_done{0};
+        if ((rc = allow_norm_io(&blm_normalize_io_kernel<io_f16>, &blm_normalize_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(blm_normalize_io_kernel)"))) return rc;
+        const bool f16 = out_dtype == MELSPEC_OUT_F16;
+        const size_t lds = per == 0 ? 0 : (per * stride + 2 * per + kBlmNormThreads) * sizeof(float);
+        const unsigned g2 = per == 0 ? grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4) : grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
+        hipLaunchKernelGGL(f16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, np);
+        HIP_TRY(hipGetLastError());
+        return MELSPEC_OK;
     }
     if (b->cfg.normalize_per_feature && valid > 0) {
         BlmNormParams np{};
@@ -690,20 +852,9 @@ int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint6
         static const int norm_skip = lab_int("MELSPEC_NORM_SKIP", 0, 0, 7);
         np.lab_skip = norm_skip;
         const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-        // four workgroups of <= 38 KB per CU measured best (1024 x 10 s x 128 mels, ms per call incl. the 0.72 ms mel kernel: 150 KB x 1: 1.72,
-        // 76 x 2: 1.45, 50 x 3: 1.34, 38 x 4: 1.28, 25 x 6: 1.68); MELSPEC_NORM_KB / MELSPEC_NORM_PER_CU override
-        size_t stride = (static_cast<size_t>(valid) + 3 + 31) & ~static_cast<size_t>(31);  // whole groups of 32 floats (a row starts up to 3 floats into its first granule) ...
-        if ((stride / 4) % 2 == 0) stride += 4;                                              // ... and 4 * odd
-        static const int norm_kb = lab_int("MELSPEC_NORM_KB", 38, 8, 158);
-        static const int norm_per_cu = lab_int("MELSPEC_NORM_PER_CU", 4, 1, 16);
-        const size_t budget = static_cast<size_t>(norm_kb) * 1024 - (64 * 2 + kBlmNormThreads) * sizeof(float);
-        size_t per = budget / (stride * sizeof(float));
-        int per_cu = norm_per_cu;
-        if (per < 4) {                            // long rows (> ~25 s): one workgroup per CU with the whole LDS, up to ~6 min per row
-            per = (static_cast<size_t>(150) * 1024) / (stride * sizeof(float));
-            per_cu = 1;
-        }
-        if (per > 64) per = 64;
+        size_t stride, per;
+        int per_cu;
+        blm_norm_shape_uniform(valid, stride, per, per_cu);
         np.rows_per_group = static_cast<int>(per);
         np.lds_stride = static_cast<int>(stride);
         static std::atomic<uint64_t> attr_done{0};
@@ -746,16 +897,30 @@ int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint6
     return MELSPEC_OK;
 }
 
+int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
+                                       uint32_t n_clips, float *d_out, void *stream) {
+    return blm_uniform(b, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, 0);
+}
+
 // BatchLogMelSpectrogram::compute per clip of any length (src/mel.rs:299-385) in one launch: clip c = d_pcm[h_offsets[c] .. + h_lengths[c])
 // -> [n_mels][cols_c] floats at d_out + h_out_offsets[c] (NULL: packed in clip order), cols_c = melspec_blm_padded_frames(len_c).
 // Fused kernel only (n_fft 512 / win_length 400).
-int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
-                                      uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
+// io: as in blm_uniform.
+static int blm_ragged(melspec_blm *b, const void *vd_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips, void *vd_out,
+                      const uint64_t *h_out_offsets, void *stream, int io) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     if (n_clips == 0) return MELSPEC_OK;
     if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
     if (!b->fast) return fail(MELSPEC_ERR_UNSUPPORTED, "ragged batches need the fused kernel (n_fft = 512, win_length = 400)");
-    std::vector<uint64_t> cols(n_clips), aux(2 * static_cast<size_t>(n_clips) + 1);        // lengths, valid frames, the normaliser's group counter (0)
+    const float *d_pcm = static_cast<const float *>(vd_pcm);
+    float *d_out = static_cast<float *>(vd_out);
+    const int out_dtype = io >> 4;
+    // 16-bit rows + normalisation: the mel kernel writes f32 rows, packed in clip order, into the context's scratch (blm_uniform); the
+    // caller's own output offsets then travel behind the group counter
+    const bool split = out_dtype != 0 && b->cfg.normalize_per_feature;
+    const bool own_offsets = split && h_out_offsets != nullptr;
+    // lengths, valid frames, the normaliser's group counter (0) [, the caller's output offsets]
+    std::vector<uint64_t> cols(n_clips), aux(2 * static_cast<size_t>(n_clips) + 1 + (own_offsets ? n_clips : 0));
     uint64_t total = 0, longest = 0;
     for (uint32_t i = 0; i < n_clips; ++i) {
         const uint64_t valid = blm_valid_frames(b, h_lengths[i]);
@@ -767,6 +932,8 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
     }
     if (total == 0) return MELSPEC_OK;
     if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && ((reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(out_dtype) - 1))))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     HIP_TRY(hipSetDevice(b->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
     const int nm = b->cfg.n_mels;
@@ -774,6 +941,12 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
     b->aux_used = true; b->aux_stream = s;
     int rc = b->aux.ensure(aux.size() * sizeof(uint64_t));
     if (rc) return rc;
+    if (split) {
+        if ((rc = blm_rows32(b, total * static_cast<uint64_t>(nm), s, d_out))) return rc;
+        if (own_offsets) std::copy(h_out_offsets, h_out_offsets + n_clips, aux.begin() + 2 * static_cast<size_t>(n_clips) + 1);
+        h_out_offsets = nullptr;
+        io &= 15;
+    }
     HIP_TRY(hipMemcpyAsync(b->aux.p, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
     BatchPlan pl;
     RaggedSlot *slot = nullptr;
@@ -795,21 +968,47 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
         fp.d_len = static_cast<const uint64_t *>(b->aux.p);
         fp.d_valid = fp.d_len + n_clips;
         fp.slots = b->ft.slots;
-        if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
+        if (io) rc = launch_nemo_io(b, fp, io, s);
+        else if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
         else if (fb_lens_match<LensSlaney128>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
         else if (fb_lens_match<LensSlaney80>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
         else rc = b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
                                                   : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-        if (!rc && b->cfg.normalize_per_feature && longest > 0) {
+        if (!rc && split && longest > 0) {
+            // blm_normalize_ragged_kernel's shape; source rows at the plan's packed offsets, destination rows at the caller's
             const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-            // rows staged whole in LDS like the uniform pass (sized for the longest clip), groups of rows from a counter
-            size_t stride = (static_cast<size_t>(longest) + 3 + 31) & ~static_cast<size_t>(31);
-            if ((stride / 4) % 2 == 0) stride += 4;
-            const size_t fixed = (2 * 64 + kBlmNormThreads + 4 * 64 + 4) * sizeof(float);
-            size_t per = (static_cast<size_t>(38) * 1024 - fixed) / (stride * sizeof(float));
-            int per_cu = 4;
-            if (per < 4) { per = (static_cast<size_t>(150) * 1024 - fixed) / (stride * sizeof(float)); per_cu = 1; }
-            if (per > 64) per = 64;
+            const uint64_t *d_dst_off = own_offsets ? static_cast<const uint64_t *>(b->aux.p) + 2 * static_cast<size_t>(n_clips) + 1 : pl.desc.d_out_off;
+            size_t stride, per;
+            int per_cu;
+            blm_norm_shape_ragged(longest, stride, per, per_cu);      // (its rows carry two more words each: <= 512 bytes)
+            const bool f16 = out_dtype == MELSPEC_OUT_F16;
+            if (per >= 1 && longest < (1ull << 31)) {
+                static std::atomic<uint64_t> attr_done{0};
+                rc = allow_norm_io(&blm_normalize_ragged_io_kernel<io_f16>, &blm_normalize_ragged_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(blm_normalize_ragged_io_kernel)");
+                if (!rc) {
+                    BlmNormRaggedIoParams rp{};
+                    rp.src = d_out; rp.dst = vd_out; rp.d_src_off = pl.desc.d_out_off; rp.d_dst_off = d_dst_off; rp.d_cols = pl.desc.d_frames; rp.d_valid = fp.d_valid;
+                    rp.n_clips = n_clips; rp.n_mels = nm; rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
+                    rp.ctr = reinterpret_cast<unsigned *>(static_cast<uint64_t *>(b->aux.p) + 2 * static_cast<size_t>(n_clips));
+                    const size_t lds = (per * stride + 2 * per + kBlmNormThreads + kBlmNormIoInfo * per + 4) * sizeof(float);
+                    const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
+                    hipLaunchKernelGGL(f16 ? blm_normalize_ragged_io_kernel<io_f16> : blm_normalize_ragged_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, rp);
+                    if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_ragged_io_kernel launch failed");
+                }
+            } else {
+                // rows too long for LDS: one thread per row from HBM
+                BlmNormIoParams np{};
+                np.src = d_out; np.dst = vd_out; np.n_clips = n_clips; np.n_mels = nm; np.rows_per_group = 0;
+                np.d_src_off = pl.desc.d_out_off; np.d_dst_off = d_dst_off; np.d_cols = pl.desc.d_frames; np.d_valid = fp.d_valid;
+                hipLaunchKernelGGL(f16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>,
+                                   dim3(grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4)), dim3(kBlmNormThreads), 0, s, np);
+                if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_io_kernel launch failed");
+            }
+        } else if (!rc && b->cfg.normalize_per_feature && longest > 0) {
+            const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+            size_t stride, per;
+            int per_cu;
+            blm_norm_shape_ragged(longest, stride, per, per_cu);
             if (per >= 1 && longest < (1ull << 31)) {
                 static std::atomic<uint64_t> attr_done{0};
                 if (!device_done(attr_done)) {
@@ -842,13 +1041,67 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
     return rc;
 }
 
+int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                      uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
+    return blm_ragged(b, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, 0);
+}
+
+// ---- int16 PCM in / f16, bf16 rows out: see include/melspec_hip.h ----
+int melspec_blm_supports_io(const melspec_blm *b, int pcm_dtype, int out_dtype) {
+    if (!b || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || blm_io_ok(b) ? 1 : 0;
+}
+
+int melspec_blm_compute_uniform_device_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                          uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
+    int io, rc = blm_io_args(b, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return blm_uniform(b, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, io);
+}
+
+int melspec_blm_compute_ragged_device_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                         const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
+                                         const uint64_t *h_out_offsets, void *stream) {
+    int io, rc = blm_io_args(b, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return blm_ragged(b, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, io);
+}
+
+// One clip from host memory: the 16-bit bytes cross the bus, the kernels convert.
+int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
+                                size_t out_capacity_elems, size_t *rows, size_t *cols) {
+    int io, rc = blm_io_args(b, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_blm_compute_host(b, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, rows, cols);
+    if (rows) *rows = static_cast<size_t>(b->cfg.n_mels);
+    if (cols) *cols = 0;
+    const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
+    if (c == 0) return MELSPEC_OK;
+    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+    const uint64_t need = c * static_cast<uint64_t>(b->cfg.n_mels);
+    if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
+    if ((rc = b->h2d.ensure(n_samples * ib))) return rc;
+    if ((rc = b->d2h.ensure(need * ob))) return rc;
+    HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, b->stream));
+    rc = blm_uniform(b, b->h2d.p, n_samples, n_samples, 1, b->d2h.p, b->stream, io);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, b->d2h.p, need * ob, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (cols) *cols = static_cast<size_t>(c);
+    return MELSPEC_OK;
+}
+
 int melspec_blm_release_scratch(melspec_blm *b) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     HIP_TRY(hipSetDevice(b->dev.device));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (b->aux_used && b->aux_stream != b->stream) HIP_TRY(hipStreamSynchronize(b->aux_stream));
-    b->pipe.release(); b->ragged.release(); b->aux.release(); b->h2d.release(); b->d2h.release();
-    b->aux_used = false;
+    if (b->rows32_used && b->rows32_stream != b->stream) HIP_TRY(hipStreamSynchronize(b->rows32_stream));
+    b->pipe.release(); b->ragged.release(); b->aux.release(); b->h2d.release(); b->d2h.release(); b->rows32.release();
+    b->aux_used = false; b->rows32_used = false;
     return MELSPEC_OK;
 }
 

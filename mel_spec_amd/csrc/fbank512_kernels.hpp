@@ -39,13 +39,15 @@ constexpr int kFlavorKaldi = 0, kFlavorNemo = 1, kFlavorWhisper = 2;
 // Rows are kCols + 4 floats apart (13 sixteen-byte pieces at twelve waves): the sixteen lanes of a frame (mels j, j + 15, ...) write
 // sixteen different 4-bank groups, and a lane's NSLOTS stores are one base address + compile-time offsets (an XOR swizzle of unpadded
 // rows costs a VGPR per slot, which the twelve-wave kernel does not have).
-template <int WAVES>
+// Out: the row type in global memory (float; _Float16 / __bf16 in fbank512_nemo_io_kernel).  The image stays f32 whatever it is: a
+// 16-byte piece of four columns is rounded to nearest even by drain and stored as 8 bytes, runs of WAVES x 8 bytes per mel row.
+template <int WAVES, class Out = float>
 struct StagedRows {
     static constexpr int kCols = WAVES * kFbFPW;
     static constexpr int kPitch = kCols + 4;
     struct alignas(16) UnitInfo {
-        float *col;          // &out[mel 0][first column of the unit]
-        long long row_w;     // floats between mel rows
+        Out *col;            // &out[mel 0][first column of the unit]
+        long long row_w;     // elements between mel rows
         int ns;              // columns of the unit that exist in the output (0: no unit this round)
         int pad;
     };
@@ -77,19 +79,34 @@ struct StagedRows {
             const int m = task / WAVES, c = task - m * WAVES;
             const UnitInfo u = ui[c];
             const f4 v = ld4(img + m * kPitch + (c << 2));
-            float *dst = u.col + static_cast<long long>(m) * u.row_w;
-            if (u.ns == kFbFPW) {
-                *reinterpret_cast<v4u *>(dst) = v4u{v.x, v.y, v.z, v.w};
+            Out *dst = u.col + static_cast<long long>(m) * u.row_w;
+            if constexpr (sizeof(Out) == 4) {
+                if (u.ns == kFbFPW) {
+                    *reinterpret_cast<v4u *>(dst) = v4u{v.x, v.y, v.z, v.w};
+                } else {
+                    if (u.ns > 0) dst[0] = v.x;
+                    if (u.ns > 1) dst[1] = v.y;
+                    if (u.ns > 2) dst[2] = v.z;
+                }
             } else {
-                if (u.ns > 0) dst[0] = v.x;
-                if (u.ns > 1) dst[1] = v.y;
-                if (u.ns > 2) dst[2] = v.z;
+                // rows of 16-bit values start at any even address (an odd row width, an odd clip offset): an 8-byte store at 2-byte alignment
+                typedef uint32_t w2u __attribute__((ext_vector_type(2), aligned(2)));
+                const Out h0 = row_value<Out>(v.x), h1 = row_value<Out>(v.y), h2 = row_value<Out>(v.z), h3 = row_value<Out>(v.w);
+                if (u.ns == kFbFPW) {
+                    const uint32_t lo = __builtin_bit_cast(uint16_t, h0) | static_cast<uint32_t>(__builtin_bit_cast(uint16_t, h1)) << 16;
+                    const uint32_t hi = __builtin_bit_cast(uint16_t, h2) | static_cast<uint32_t>(__builtin_bit_cast(uint16_t, h3)) << 16;
+                    *reinterpret_cast<w2u *>(dst) = w2u{lo, hi};
+                } else {
+                    if (u.ns > 0) dst[0] = h0;
+                    if (u.ns > 1) dst[1] = h1;
+                    if (u.ns > 2) dst[2] = h2;
+                }
             }
         }
     }
     // a wave's unit of this round (every lane calls; vals: this lane's mel j + 15 i of frame fl, zero for a column past the valid frames)
     template <int NSLOTS>
-    __device__ __forceinline__ void put(int wave, int lane, const float (&vals)[NSLOTS], float *col, long long row_w, int ns) {
+    __device__ __forceinline__ void put(int wave, int lane, const float (&vals)[NSLOTS], Out *col, long long row_w, int ns) {
         const int l = fresh_lane_value(lane), fl = l / kFbLanes, j = l - fl * kFbLanes;      // derived here, not held across the unit loop
         float *mine = image + (round & 1u) * image_floats(n_mels) + j * kPitch + (wave << 2) + fl;
         if (j < kFbOwn) {
@@ -112,150 +129,11 @@ struct StagedRows {
 // RUNS (frame-major plain output: Kaldi always, Whisper-512 without a layout): a contiguous run of units per wave (ClipRun).
 template <class T, int WAVES, int MINW, int FLAVOR = kFlavorKaldi, int NSLOTS = kFbSlots, class Lens = LensRuntime, bool RUNS = false>
 __global__ __launch_bounds__(WAVES * 64, MINW) void fbank512_wave_kernel(const FbankFastParams p) {
-    using L = FbankLayout<T>;
-    extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < p.blob_words; i += WAVES * 64) ldsw[i] = p.d_blob[i];
-    // NeMo: the feature-major store gives every wave 16 bytes of each mel row per unit; the units are walked in workgroup-uniform
-    // rounds and the waves that hold adjacent units are kept in step before their stores (RoundSync, as in the mel-major Whisper kernels)
-    constexpr bool ROUNDS = FLAVOR == kFlavorNemo;
-    // the f32 NeMo kernel stages its feature-major rows in LDS (StagedRows) instead of keeping pairs of waves in step
-    constexpr bool STAGE = FLAVOR == kFlavorNemo && sizeof(T) == 4;
-    unsigned *arrive = ldsw + p.blob_words + WAVES * L::slice_elems() * (sizeof(T) / 4);     // 16 words: RoundSync counters; [15]: StagedRows
-    if (ROUNDS && tid < 16) arrive[tid] = 0;
-    __syncthreads();
-    const T *tblob = reinterpret_cast<const T *>(ldsw);
-    const float *mel = reinterpret_cast<const float *>(ldsw + p.mel_off_words);
-
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    T *slice = reinterpret_cast<T *>(ldsw + p.blob_words) + wave * L::slice_elems();
-    const int fl = lane / kFbLanes, j = lane - fl * kFbLanes;
-    const bool in = lane < kFbFPW * kFbLanes;
-    // first bin of this lane's interval per slot: held across the unit loop by the compile-time banks; the run-time-lens variants
-    // re-read the ten words in front of phase 3 instead (they sit at the 256-VGPR limit: holding them spilled inside the loop)
-    int st[NSLOTS];
-    const int *starts = reinterpret_cast<const int *>(mel + FbankBlob::kMelStart);
-    // (the twelve-wave f32 NeMo kernel has no registers to hold them either)
-    constexpr bool HOLD_STARTS = Lens::kStatic && !(FLAVOR == kFlavorNemo && sizeof(T) == 4);
-    if (HOLD_STARTS) {
-#pragma unroll
-        for (int i = 0; i < NSLOTS; ++i) st[i] = in ? starts[i * kFbLanes + j] : 0;
-    }
-    const bool use_power = p.use_power != 0, use_log = p.use_log != 0;
-    const T preemph = static_cast<T>(p.preemph);
-
-    static_assert(!(RUNS && FLAVOR == kFlavorNemo), "the feature-major store wants adjacent units in adjacent waves");
-    ClipRun cr;
-    if (RUNS && !cr.init(p.b, (uint64_t)xcd_logical_block() * WAVES + wave, (uint64_t)gridDim.x * WAVES)) return;
-    RoundSync<WAVES> rs((ROUNDS && !STAGE) ? p.b.sync_rounds : 0, wave, arrive);
-    StagedRows<STAGE ? WAVES : 4> staged(arrive + 16, arrive + 15, p.n_mels);
-    // batches planned on the device (plan_ragged_device_kernel) keep the real unit count in d_n_units; n_units is the host's bound
-    const uint64_t n_units = RUNS ? 0 : scalar64(batch_n_units(p.b));
-    // (STAGE with a contiguous range of units per workgroup instead of rounds dealt over the grid -- consecutive rounds extending the same
-    // mel rows, no division per unit -- was measured: +1.4 %, profiles/r05_f32_512.txt)
-    for (uint64_t first = (uint64_t)xcd_logical_block() * WAVES + (ROUNDS ? 0 : wave);; first += (uint64_t)gridDim.x * WAVES) {
-        const uint64_t unit = ROUNDS ? first + rs.slot : first;
-        if (RUNS) {
-            if (cr.unit >= cr.end) break;
-            cr.enter(p.b);
-        } else if (first >= n_units) {
-            break;
-        }
-        const bool have = !ROUNDS || unit < n_units;       // a wave without a unit idles through the round
-        UnitLoc loc = RUNS ? cr.loc() : locate_unit(p.b, have ? unit : first);
-        if (STAGE) loc = scalar_loc(loc);          // this kernel has no VGPRs for them
-        const uint64_t f0 = loc.unit * kFbFPW;
-        // valid frames of the clip (NeMo ragged: loc.frames is the padded width there)
-        const uint64_t vframes = (FLAVOR == kFlavorNemo && p.d_valid) ? p.d_valid[loc.clip] : loc.frames;
-        const uint64_t left = (have && f0 < vframes) ? vframes - f0 : 0;
-        const int nv = left < (uint64_t)kFbFPW ? (int)left : kFbFPW;
-        const bool act = in && fl < nv;
-        MS_PRIO(0);
-        if (FLAVOR == kFlavorKaldi) {
-            const float *frame = loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift;
-            // the frame mean (src/fbank.rs:165-166: the frame's sixteen lanes, a fixed tree over DPP), DC removal, pre-emphasis and the Povey window
-            // from ONE set of loads (fb_kaldi_input)
-            if (act) {
-                cpx<T> x[16];
-                fb_kaldi_input<T>(frame, j, preemph, f0 + fl == 0 && j == 0, tblob, x);
-                fb_column_finish<T>(x, j, tblob, slice + fl * L::kXStride);
-            }
-        } else if (FLAVOR == kFlavorWhisper) {
-            w512_phase1<T>(fl, j, act, loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift, tblob, slice);
-        } else {
-            const long long clip_len = p.d_len ? (long long)p.d_len[loc.clip] : p.clip_len;
-            const long long org = (long long)(f0 + (uint64_t)fl) * p.shift + p.org0;
-            const bool inside = org >= 1 && org + 400 <= clip_len;
-            const bool all_inside = __builtin_amdgcn_ballot_w64(act && !inside) == 0;
-            nemo_phase1<T>(fl, j, act, all_inside, loc.pcm, org, clip_len, static_cast<float>(p.preemph), tblob, slice);
-        }
-        __builtin_amdgcn_wave_barrier();
-        MS_PRIO(1);
-        {
-            cpx<T> own[16], part[8];
-            fb_phase2_dft<T, STAGE>(fl, j, act, slice, own);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) part[i] = {partner16(own[8 + i].re), partner16(own[8 + i].im)};
-            if (FLAVOR == kFlavorWhisper) fb_phase2_split<T, true, sizeof(T) == 8>(fl, j, act, tblob, own, part, slice);      // f32: the amplitude form (fbank_tables.hpp)
-            // NeMo: power spectra always (src/mel.rs:356-357) -- the magnitude form stays out of its unit loop (742 -> ~400 instructions in phase 2)
-            else if (FLAVOR == kFlavorNemo || use_power) fb_phase2_split<T, true>(fl, j, act, tblob, own, part, slice);
-            else fb_phase2_split<T, false>(fl, j, act, tblob, own, part, slice);
-        }
-        __builtin_amdgcn_wave_barrier();
-        MS_PRIO(2);
-        float rise[NSLOTS], fprev[NSLOTS], fnext[NSLOTS];
-        if (!HOLD_STARTS) {
-            const int *mine = starts + (STAGE ? fresh_lane_value(j) : j);
-#pragma unroll
-            for (int i = 0; i < NSLOTS; ++i) st[i] = in ? mine[i * kFbLanes] : 0;
-        }
-        fb_phase3_sums<T, NSLOTS, Lens>(fl, j, act, p.slots, mel, slice, st, rise, fprev);
-#pragma unroll
-        for (int i = 0; i < NSLOTS; ++i) fnext[i] = wave_shift_down1(fprev[i]);
-        if (FLAVOR == kFlavorKaldi) {
-            fb_phase3_store<NSLOTS>(fl, j, act, p.n_mels, p.floor_v, use_log, rise, fnext, loc.out + f0 * (uint64_t)p.n_mels);
-        } else if (FLAVOR == kFlavorWhisper) {
-            float vals[NSLOTS];
-            float *slice_f = reinterpret_cast<float *>(slice);
-            w512_phase3_log<NSLOTS>(fl, j, act, p.n_mels, rise, fnext, slice_f, vals);
-            __builtin_amdgcn_wave_barrier();
-            // columns this unit stores: the clip's frames plus, for padded layouts, zero columns up to out_width
-            const uint64_t width = p.b.d_unit_prefix == nullptr ? p.b.out_width : loc.frames;
-            const uint64_t wleft = width - f0;
-            const int ns = wleft < (uint64_t)kFbFPW ? (int)wleft : kFbFPW;
-            if (p.b.mel_major)
-                w512_phase4<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, slice_f, vals, loc.out + f0, (long long)width);
-            else
-                w512_phase4<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, slice_f, vals, loc.out + f0 * (uint64_t)p.n_mels, 0);
-        } else {
-            const uint64_t row_w = p.b.d_unit_prefix == nullptr ? p.b.out_width : loc.frames;
-            const uint64_t wleft = have ? row_w - f0 : 0;
-            const int ns = wleft < (uint64_t)kFbFPW ? (int)wleft : kFbFPW;
-            if (STAGE) {
-                float vals[NSLOTS];
-#pragma unroll
-                for (int i = 0; i < NSLOTS; ++i) vals[i] = act ? fast_ln((rise[i] + fnext[i]) + p.floor_v) : 0.0f;     // nemo_phase3_store's value
-                if (staged.round > 0) {
-                    int dtid = tid;
-                    asm volatile("" : "+v"(dtid));          // see StagedRows::drain
-                    staged.wait_staged(staged.round, lane);
-                    staged.drain(staged.round - 1, dtid);
-                }
-                staged.template put<NSLOTS>(wave, lane, vals, loc.out + f0, (long long)row_w, ns);
-            } else {
-                rs.template before_stores<2>(lane);
-                nemo_phase3_store<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, p.floor_v, rise, fnext, loc.out + f0, (long long)row_w);
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (ROUNDS) rs.after_round();
-        if (RUNS) ++cr.unit;
-    }
-    if (STAGE && staged.round > 0) {
-        staged.wait_staged(staged.round, lane);
-        staged.drain(staged.round - 1, tid);
-    }
+#define MS_FB512_IN float
+#define MS_FB512_OUT float
+#include "fbank512_wave_body.inc"
+#undef MS_FB512_OUT
+#undef MS_FB512_IN
 }
 
 // ------------------------------------------------------------------------------------
@@ -775,6 +653,11 @@ __device__ __forceinline__ void blm_row_stats_slow(const float *r, uint64_t vali
     sd = __builtin_sqrtf(f32_div_rn(q, denom)) + 1e-5f;
 }
 
+// (the two kernels that are not templates are defined once: fbank512_io.hip, which includes this header for everything around them, leaves them out)
+// KEEP IN STEP with blm_normalize_io_kernel (fbank512_io_kernels.hpp), the copy that reads the rows from a scratch and writes 16-bit rows: its
+// staging, mean fold and sum-of-squares tree must stay the ones below, operation for operation -- a 16-bit call gives the rounding of
+// this kernel's bits (tests/test_blm_io_dtypes.py).  It is a copy because this kernel's instructions were not to change.
+#ifndef MS_FBANK512_NO_PLAIN_KERNELS
 __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_kernel(const BlmNormParams p) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
@@ -942,6 +825,8 @@ __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normali
     }
 }
 
+#endif
+
 // The same pass for ragged batches (clips of different lengths in one launch): rows are described per clip (first output float, row
 // width, valid frames), a group of R rows is taken from a device counter (rows of long and short clips cost differently, so a static
 // split would leave workgroups idle), its rows' descriptions are put in LDS once per round, and every row is staged at ITS alignment.
@@ -956,6 +841,8 @@ struct BlmNormRaggedParams {
     unsigned *ctr;          // zero at launch
 };
 
+// KEEP IN STEP with blm_normalize_ragged_io_kernel (fbank512_io_kernels.hpp): see blm_normalize_kernel
+#ifndef MS_FBANK512_NO_PLAIN_KERNELS
 __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_ragged_kernel(const BlmNormRaggedParams p) {
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
@@ -1088,6 +975,8 @@ __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normali
         __syncthreads();
     }
 }
+
+#endif
 
 // CMN (src/fbank.rs:224-233): per clip and mel column subtract the f32 mean over the clip's frames.  The reference's
 // `column(m).mean()` (ndarray on a strided view) is a left fold in f32 followed by one division; its rounding error is ~1e-5 of a

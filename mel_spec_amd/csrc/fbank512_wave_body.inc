@@ -1,0 +1,147 @@
+// fbank512_wave_body.inc -- the body of fbank512_wave_kernel (fbank512_kernels.hpp), included once per kernel that has it: the kernel itself
+// (MS_FB512_IN = MS_FB512_OUT = float) and fbank512_nemo_io_kernel (fbank512_io_kernels.hpp: int16 samples in, f16 / bf16 rows out, NeMo
+// flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
+    using L = FbankLayout<T>;
+    extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < p.blob_words; i += WAVES * 64) ldsw[i] = p.d_blob[i];
+    // NeMo: the feature-major store gives every wave 16 bytes of each mel row per unit; the units are walked in workgroup-uniform
+    // rounds and the waves that hold adjacent units are kept in step before their stores (RoundSync, as in the mel-major Whisper kernels)
+    constexpr bool ROUNDS = FLAVOR == kFlavorNemo;
+    // the f32 NeMo kernel stages its feature-major rows in LDS (StagedRows) instead of keeping pairs of waves in step
+    constexpr bool STAGE = FLAVOR == kFlavorNemo && sizeof(T) == 4;
+    unsigned *arrive = ldsw + p.blob_words + WAVES * L::slice_elems() * (sizeof(T) / 4);     // 16 words: RoundSync counters; [15]: StagedRows
+    if (ROUNDS && tid < 16) arrive[tid] = 0;
+    __syncthreads();
+    const T *tblob = reinterpret_cast<const T *>(ldsw);
+    const float *mel = reinterpret_cast<const float *>(ldsw + p.mel_off_words);
+
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    T *slice = reinterpret_cast<T *>(ldsw + p.blob_words) + wave * L::slice_elems();
+    const int fl = lane / kFbLanes, j = lane - fl * kFbLanes;
+    const bool in = lane < kFbFPW * kFbLanes;
+    // first bin of this lane's interval per slot: held across the unit loop by the compile-time banks; the run-time-lens variants
+    // re-read the ten words in front of phase 3 instead (they sit at the 256-VGPR limit: holding them spilled inside the loop)
+    int st[NSLOTS];
+    const int *starts = reinterpret_cast<const int *>(mel + FbankBlob::kMelStart);
+    // (the twelve-wave f32 NeMo kernel has no registers to hold them either)
+    constexpr bool HOLD_STARTS = Lens::kStatic && !(FLAVOR == kFlavorNemo && sizeof(T) == 4);
+    if (HOLD_STARTS) {
+#pragma unroll
+        for (int i = 0; i < NSLOTS; ++i) st[i] = in ? starts[i * kFbLanes + j] : 0;
+    }
+    const bool use_power = p.use_power != 0, use_log = p.use_log != 0;
+    const T preemph = static_cast<T>(p.preemph);
+
+    static_assert(!(RUNS && FLAVOR == kFlavorNemo), "the feature-major store wants adjacent units in adjacent waves");
+    ClipRunT<MS_FB512_IN, MS_FB512_OUT> cr;
+    if (RUNS && !cr.init(p.b, (uint64_t)xcd_logical_block() * WAVES + wave, (uint64_t)gridDim.x * WAVES)) return;
+    RoundSync<WAVES> rs((ROUNDS && !STAGE) ? p.b.sync_rounds : 0, wave, arrive);
+    StagedRows<STAGE ? WAVES : 4, MS_FB512_OUT> staged(arrive + 16, arrive + 15, p.n_mels);
+    // batches planned on the device (plan_ragged_device_kernel) keep the real unit count in d_n_units; n_units is the host's bound
+    const uint64_t n_units = RUNS ? 0 : scalar64(batch_n_units(p.b));
+    // (STAGE with a contiguous range of units per workgroup instead of rounds dealt over the grid -- consecutive rounds extending the same
+    // mel rows, no division per unit -- was measured: +1.4 %, profiles/r05_f32_512.txt)
+    for (uint64_t first = (uint64_t)xcd_logical_block() * WAVES + (ROUNDS ? 0 : wave);; first += (uint64_t)gridDim.x * WAVES) {
+        const uint64_t unit = ROUNDS ? first + rs.slot : first;
+        if (RUNS) {
+            if (cr.unit >= cr.end) break;
+            cr.enter(p.b);
+        } else if (first >= n_units) {
+            break;
+        }
+        const bool have = !ROUNDS || unit < n_units;       // a wave without a unit idles through the round
+        UnitLocT<MS_FB512_IN, MS_FB512_OUT> loc = RUNS ? cr.loc() : locate_unit<MS_FB512_IN, MS_FB512_OUT>(p.b, have ? unit : first);
+        if (STAGE) loc = scalar_loc(loc);          // this kernel has no VGPRs for them
+        const uint64_t f0 = loc.unit * kFbFPW;
+        // valid frames of the clip (NeMo ragged: loc.frames is the padded width there)
+        const uint64_t vframes = (FLAVOR == kFlavorNemo && p.d_valid) ? p.d_valid[loc.clip] : loc.frames;
+        const uint64_t left = (have && f0 < vframes) ? vframes - f0 : 0;
+        const int nv = left < (uint64_t)kFbFPW ? (int)left : kFbFPW;
+        const bool act = in && fl < nv;
+        MS_PRIO(0);
+        if constexpr (FLAVOR == kFlavorKaldi) {
+            const float *frame = loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift;
+            // the frame mean (src/fbank.rs:165-166: the frame's sixteen lanes, a fixed tree over DPP), DC removal, pre-emphasis and the Povey window
+            // from ONE set of loads (fb_kaldi_input)
+            if (act) {
+                cpx<T> x[16];
+                fb_kaldi_input<T>(frame, j, preemph, f0 + fl == 0 && j == 0, tblob, x);
+                fb_column_finish<T>(x, j, tblob, slice + fl * L::kXStride);
+            }
+        } else if constexpr (FLAVOR == kFlavorWhisper) {
+            w512_phase1<T>(fl, j, act, loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift, tblob, slice);
+        } else {
+            const long long clip_len = p.d_len ? (long long)p.d_len[loc.clip] : p.clip_len;
+            const long long org = (long long)(f0 + (uint64_t)fl) * p.shift + p.org0;
+            const bool inside = org >= 1 && org + 400 <= clip_len;
+            const bool all_inside = __builtin_amdgcn_ballot_w64(act && !inside) == 0;
+            nemo_phase1<T>(fl, j, act, all_inside, loc.pcm, org, clip_len, static_cast<float>(p.preemph), tblob, slice);
+        }
+        __builtin_amdgcn_wave_barrier();
+        MS_PRIO(1);
+        {
+            cpx<T> own[16], part[8];
+            fb_phase2_dft<T, STAGE>(fl, j, act, slice, own);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) part[i] = {partner16(own[8 + i].re), partner16(own[8 + i].im)};
+            if (FLAVOR == kFlavorWhisper) fb_phase2_split<T, true, sizeof(T) == 8>(fl, j, act, tblob, own, part, slice);      // f32: the amplitude form (fbank_tables.hpp)
+            // NeMo: power spectra always (src/mel.rs:356-357) -- the magnitude form stays out of its unit loop (742 -> ~400 instructions in phase 2)
+            else if (FLAVOR == kFlavorNemo || use_power) fb_phase2_split<T, true>(fl, j, act, tblob, own, part, slice);
+            else fb_phase2_split<T, false>(fl, j, act, tblob, own, part, slice);
+        }
+        __builtin_amdgcn_wave_barrier();
+        MS_PRIO(2);
+        float rise[NSLOTS], fprev[NSLOTS], fnext[NSLOTS];
+        if (!HOLD_STARTS) {
+            const int *mine = starts + (STAGE ? fresh_lane_value(j) : j);
+#pragma unroll
+            for (int i = 0; i < NSLOTS; ++i) st[i] = in ? mine[i * kFbLanes] : 0;
+        }
+        fb_phase3_sums<T, NSLOTS, Lens>(fl, j, act, p.slots, mel, slice, st, rise, fprev);
+#pragma unroll
+        for (int i = 0; i < NSLOTS; ++i) fnext[i] = wave_shift_down1(fprev[i]);
+        if constexpr (FLAVOR == kFlavorKaldi) {
+            fb_phase3_store<NSLOTS>(fl, j, act, p.n_mels, p.floor_v, use_log, rise, fnext, loc.out + f0 * (uint64_t)p.n_mels);
+        } else if constexpr (FLAVOR == kFlavorWhisper) {
+            float vals[NSLOTS];
+            float *slice_f = reinterpret_cast<float *>(slice);
+            w512_phase3_log<NSLOTS>(fl, j, act, p.n_mels, rise, fnext, slice_f, vals);
+            __builtin_amdgcn_wave_barrier();
+            // columns this unit stores: the clip's frames plus, for padded layouts, zero columns up to out_width
+            const uint64_t width = p.b.d_unit_prefix == nullptr ? p.b.out_width : loc.frames;
+            const uint64_t wleft = width - f0;
+            const int ns = wleft < (uint64_t)kFbFPW ? (int)wleft : kFbFPW;
+            if (p.b.mel_major)
+                w512_phase4<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, slice_f, vals, loc.out + f0, (long long)width);
+            else
+                w512_phase4<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, slice_f, vals, loc.out + f0 * (uint64_t)p.n_mels, 0);
+        } else {
+            const uint64_t row_w = p.b.d_unit_prefix == nullptr ? p.b.out_width : loc.frames;
+            const uint64_t wleft = have ? row_w - f0 : 0;
+            const int ns = wleft < (uint64_t)kFbFPW ? (int)wleft : kFbFPW;
+            if (STAGE) {
+                float vals[NSLOTS];
+#pragma unroll
+                for (int i = 0; i < NSLOTS; ++i) vals[i] = act ? fast_ln((rise[i] + fnext[i]) + p.floor_v) : 0.0f;     // nemo_phase3_store's value
+                if (staged.round > 0) {
+                    int dtid = tid;
+                    asm volatile("" : "+v"(dtid));          // see StagedRows::drain
+                    staged.wait_staged(staged.round, lane);
+                    staged.drain(staged.round - 1, dtid);
+                }
+                staged.template put<NSLOTS>(wave, lane, vals, loc.out + f0, (long long)row_w, ns);
+            } else {
+                rs.template before_stores<2>(lane);
+                nemo_phase3_store<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, p.floor_v, rise, fnext, loc.out + f0, (long long)row_w);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (ROUNDS) rs.after_round();
+        if (RUNS) ++cr.unit;
+    }
+    if (STAGE && staged.round > 0) {
+        staged.wait_staged(staged.round, lane);
+        staged.drain(staged.round - 1, tid);
+    }

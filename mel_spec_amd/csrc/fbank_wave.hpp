@@ -210,8 +210,9 @@ MS_DEV void w512_phase1(int fl, int t, bool active, const float *frame, const T 
 // INSIDE / PRE are wave-uniform and resolved outside the unrolled loop: a data-dependent `coeff == 0 ? a : b` around the
 // opaque rounding barrier of f32_mul_rn becomes a branch per sample with an s_waitcnt vmcnt(0) in front of it, i.e. 26
 // serialised memory round trips per unit (measured: 1.51 ms per launch against 0.95 ms for this form).
-template <class T, bool INSIDE, bool PRE>
-MS_DEV void nemo_column(const float *clip, long long org, long long len, int n2, float coeff, const T *tblob, T *xo) {
+// In: the sample type (float; int16_t in fbank512_nemo_io_kernel: sample * 2^-15, exact, load2_unaligned / pcm_value in whisper_wave.hpp)
+template <class T, bool INSIDE, bool PRE, class In = float>
+MS_DEV void nemo_column(const In *clip, long long org, long long len, int n2, float coeff, const T *tblob, T *xo) {
     cpx<T> x[16];
     f2 c[13];
     float prev[13];
@@ -227,9 +228,9 @@ MS_DEV void nemo_column(const float *clip, long long org, long long len, int n2,
             c[n1] = {0.0f, 0.0f};
             prev[n1] = 0.0f;
             if (n1 < 12 || n2 < 8) {
-                const float *s = clip + org + 32 * n1 + 2 * n2;
+                const In *s = clip + org + 32 * n1 + 2 * n2;
                 c[n1] = load2_unaligned(s);
-                if (PRE) prev[n1] = s[-1];
+                if (PRE) prev[n1] = pcm_value(s[-1]);
             }
         }
     } else {
@@ -241,8 +242,9 @@ MS_DEV void nemo_column(const float *clip, long long org, long long len, int n2,
         for (int n1 = 0; n1 < 13; ++n1) {
             const int i = 32 * n1 + 2 * n2;
             auto at = [&](int k) { return clip[org + (k < lo ? lo : (k >= hi ? hi - 1 : k))]; };
-            prev[n1] = at(i - 1);
-            c[n1] = {at(i), at(i + 1)};
+            const In r0 = at(i - 1), r1 = at(i), r2 = at(i + 1);       // (the conversion of 16-bit samples after the three loads)
+            prev[n1] = pcm_value(r0);
+            c[n1] = {pcm_value(r1), pcm_value(r2)};
         }
     }
 #pragma unroll
@@ -270,18 +272,18 @@ MS_DEV void nemo_column(const float *clip, long long org, long long len, int n2,
 
 // all_inside: wave-uniform -- every active frame of the wave is an interior frame (the guarded form runs only for the
 // units at the two ends of a clip)
-template <class T>
-MS_DEV void nemo_phase1(int fl, int t, bool active, bool all_inside, const float *clip, long long org, long long len, float coeff,
+template <class T, class In = float>
+MS_DEV void nemo_phase1(int fl, int t, bool active, bool all_inside, const In *clip, long long org, long long len, float coeff,
                         const T *tblob, T *slice) {
     T *xo = slice + fl * FbankLayout<T>::kXStride;
     if (all_inside) {
         if (coeff != 0.0f) {
-            if (active) nemo_column<T, true, true>(clip, org, len, t, coeff, tblob, xo);
+            if (active) nemo_column<T, true, true, In>(clip, org, len, t, coeff, tblob, xo);
         } else {
-            if (active) nemo_column<T, true, false>(clip, org, len, t, coeff, tblob, xo);
+            if (active) nemo_column<T, true, false, In>(clip, org, len, t, coeff, tblob, xo);
         }
     } else {
-        if (active) nemo_column<T, false, true>(clip, org, len, t, coeff, tblob, xo);
+        if (active) nemo_column<T, false, true, In>(clip, org, len, t, coeff, tblob, xo);
     }
 }
 
@@ -534,19 +536,20 @@ MS_DEV void fb_phase3_store(int fl, int j, bool active, int n_mels, float floor_
 
 // NeMo epilogue: ln(E + guard) (src/mel.rs:365-368), feature-major rows of `row_w` columns
 // (src/mel.rs:366); columns past the valid frames are zero (the reference zero-initialises `features`).
-template <int NSLOTS>
+// Out: the row type (float; _Float16 / __bf16 in fbank512_nemo_io_kernel: the f32 value rounded to nearest even by the store's conversion)
+template <int NSLOTS, class Out = float>
 MS_DEV void nemo_phase3_store(int fl, int j, bool store, bool valid, int n_mels, float guard, const float (&rise)[NSLOTS],
-                              const float (&fnext)[NSLOTS], float *out_col /* &out[0][first frame of the tile] */,
+                              const float (&fnext)[NSLOTS], Out *out_col /* &out[0][first frame of the tile] */,
                               long long row_w) {
     if (!store || j >= kFbOwn) return;
-    float *o = out_col + static_cast<long long>(j) * row_w + fl;
+    Out *o = out_col + static_cast<long long>(j) * row_w + fl;
 #pragma unroll
     for (int i = 0; i < NSLOTS; ++i) {
         const int m = j + kFbOwn * i;
 #ifdef MS_NEMO_NO_STORE      // timing ablation (tools/ab_build.sh): the value is computed and dropped -- what the feature-major stores cost
         if (m < n_mels) { float v = valid ? fast_ln((rise[i] + fnext[i]) + guard) : 0.0f; asm volatile("" :: "v"(v)); (void)o; }
 #else
-        if (m < n_mels) o[static_cast<long long>(kFbOwn * i) * row_w] = valid ? fast_ln((rise[i] + fnext[i]) + guard) : 0.0f;
+        if (m < n_mels) o[static_cast<long long>(kFbOwn * i) * row_w] = row_value<Out>(valid ? fast_ln((rise[i] + fnext[i]) + guard) : 0.0f);
 #endif
     }
 }

@@ -164,10 +164,11 @@ __device__ __forceinline__ uint64_t scalar64(uint64_t v) {
 // moves them into SGPRs.  Only where the registers are missing (the twelve-wave f32 NeMo kernel: spills gone, -1.1 %): on the other
 // round-robin kernels the readfirstlanes put the division's latency in front of everything that follows -- mel-major +1.7 %, mel-major
 // F64 +1.5 %, f64 NeMo +5.2 / +6.5 % (128 / 80 mels), same box (profiles/r05_f32_512.txt)
-__device__ __forceinline__ UnitLoc scalar_loc(UnitLoc r) {
+template <class In, class Out>
+__device__ __forceinline__ UnitLocT<In, Out> scalar_loc(UnitLocT<In, Out> r) {
     r.unit = scalar64(r.unit); r.frames = scalar64(r.frames); r.clip = __builtin_amdgcn_readfirstlane(r.clip);
-    r.pcm = reinterpret_cast<const float *>(scalar64(reinterpret_cast<uint64_t>(r.pcm)));
-    r.out = reinterpret_cast<float *>(scalar64(reinterpret_cast<uint64_t>(r.out)));
+    r.pcm = reinterpret_cast<const In *>(scalar64(reinterpret_cast<uint64_t>(r.pcm)));
+    r.out = reinterpret_cast<Out *>(scalar64(reinterpret_cast<uint64_t>(r.out)));
     return r;
 }
 constexpr int kStatShift = 40;

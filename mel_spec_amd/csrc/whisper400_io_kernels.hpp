@@ -7,12 +7,9 @@
 // that are already there (melspec_runs.hip).
 #pragma once
 #include "whisper400_kernels.hpp"
+#include "io_types.hpp"
 
 namespace melspec {
-
-using io_s16 = int16_t;       // MELSPEC_PCM_S16
-using io_f16 = _Float16;      // MELSPEC_OUT_F16: v_cvt_f16_f32, round to nearest even
-using io_bf16 = __bf16;       // MELSPEC_OUT_BF16: v_cvt_pk_bf16_f32, round to nearest even, a NaN stays a NaN
 
 template <int NSLOTS, class Lens, class In, class Out>
 __global__ __launch_bounds__(kSixWaves * 64, 4) void whisper400_six_runs_io_kernel(const FastParams p) {
@@ -44,8 +41,5 @@ __global__ __launch_bounds__(kSix64Waves * 64, 3) void whisper400_six64_io_kerne
 #undef MS_SIX64_OUT
 #undef MS_SIX64_IN
 }
-
-// the five (sample, row) combinations beside (float, float), which is the existing kernels'
-#define MS_IO_COMBOS(X) X(io_s16, float) X(float, io_f16) X(float, io_bf16) X(io_s16, io_f16) X(io_s16, io_bf16)
 
 }  // namespace melspec

@@ -122,6 +122,17 @@ MS_DEV f2 load2_unaligned(const int16_t *p) {
     return f2{static_cast<float>(p[0]) * 0x1p-15f, static_cast<float>(p[1]) * 0x1p-15f};
 #endif
 }
+// one sample as the pairs above hold it
+MS_DEV float pcm_value(float v) { return v; }
+MS_DEV float pcm_value(int16_t v) { return static_cast<float>(v) * 0x1p-15f; }
+// an f32 value as an element of the row type Out.  For a 16-bit Out the f32 value is made opaque first: a multiply or an fma in front of
+// the conversion is otherwise selected as v_fma_mixlo_f16, which rounds the exact product once, to f16 -- not the f32 element rounded to
+// nearest even (one element in some 2^14 lies on the other side of an f16 tie)
+template <class Out>
+MS_DEV Out row_value(float v) {
+    if constexpr (sizeof(Out) != 4) asm("" : "+v"(v));
+    return static_cast<Out>(v);
+}
 
 // ---- phase 1 -----------------------------------------------------------------------------
 // The frame's samples come straight from global memory (L1/L2 absorb the 2.5x frame overlap).

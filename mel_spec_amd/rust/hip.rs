@@ -79,6 +79,13 @@ unsafe extern "C" {
     fn melspec_blm_padded_frames(b: *const BlmHandle, n: usize) -> usize;
     fn melspec_blm_num_frames(b: *const BlmHandle, n: usize) -> usize;
     fn melspec_blm_compute_host(b: *mut BlmHandle, samples: *const f32, n: usize, out: *mut f32, cap: usize, rows: *mut usize, cols: *mut usize) -> c_int;
+    fn melspec_blm_supports_io(b: *const BlmHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_blm_compute_uniform_device_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                             d_out: *mut c_void, out_dtype: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_ragged_device_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, h_offsets: *const u64, h_lengths: *const u64,
+                                            n_clips: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_host_io(b: *mut BlmHandle, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, out: *mut c_void, out_dtype: c_int,
+                                   cap: usize, rows: *mut usize, cols: *mut usize) -> c_int;
     fn melspec_blm_compute_batch_host(b: *mut BlmHandle, samples: *const f32, offsets: *const u64, lengths: *const u64, n_clips: u32,
                                       out: *mut f32, out_offsets: *const u64, cap: usize, total_columns: *mut u64) -> c_int;
     // vad_boundaries (src/vad.rs:251-340)
@@ -640,6 +647,46 @@ impl HipBatchLogMel {
             return Err(HipError::Runtime(last_error()));
         }
         Ok((ndarray::Array2::from_shape_vec((self.n_mels, got_cols), flat).expect("shape"), valid))
+    }
+    /// Additive: does this frontend take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` features (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?
+    pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_blm_supports_io(self.b, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+    /// Additive: equal-length clips resident in device memory, int16 samples and / or f16 / bf16 features (strides count elements).
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device pointers valid for `n_clips * clip_stride` samples of `pcm_dtype` and
+    /// `n_clips * n_mels * cols` values of `out_dtype`.
+    pub unsafe fn compute_uniform_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                            d_out: *mut c_void, out_dtype: i32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_blm_compute_uniform_device_io(self.b, d_pcm, pcm_dtype as c_int, clip_stride, clip_len, n_clips, d_out, out_dtype as c_int, stream))
+    }
+    /// Additive: clips of any lengths in one launch; clip `i`'s `[n_mels][cols]` block starts at element `out_offsets[i]` of `d_out`
+    /// (`None`: the blocks packed back to back in clip order).  Offsets and lengths count elements of their type.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`, and `d_out` must hold the blocks of all clips in `out_dtype` where the
+    /// offsets put them.
+    pub unsafe fn compute_ragged_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, offsets: &[u64], lengths: &[u64], d_out: *mut c_void,
+                                           out_dtype: i32, out_offsets: Option<&[u64]>, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        if let Some(o) = out_offsets {
+            assert_eq!(o.len(), offsets.len());
+        }
+        check(melspec_blm_compute_ragged_device_io(self.b, d_pcm, pcm_dtype as c_int, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_out,
+                                                   out_dtype as c_int, out_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), stream))
+    }
+    /// Additive: `compute` on 16-bit PCM (value = sample / 32768, exactly) into bf16 features, returned flat as their bit patterns
+    /// with `(n_mels, cols)`: the int16 bytes are what crosses the bus.
+    pub fn compute_s16_bf16(&mut self, samples: &[i16]) -> Result<(Vec<u16>, usize, usize), HipError> {
+        let cols = unsafe { melspec_blm_padded_frames(self.b, samples.len()) };
+        let mut flat = vec![0u16; self.n_mels * cols];
+        let (mut rows, mut got_cols) = (0usize, 0usize);
+        check(unsafe {
+            melspec_blm_compute_host_io(self.b, samples.as_ptr() as *const c_void, PCM_S16, samples.len(), flat.as_mut_ptr() as *mut c_void, OUT_BF16,
+                                        flat.len(), &mut rows, &mut got_cols)
+        })?;
+        Ok((flat, rows, got_cols))
     }
     /// Additive: `compute` for many clips in one call; every clip comes back as its `(n_mels, cols)` array and valid frame count.
     pub fn compute_batch(&mut self, clips: &[&[f32]]) -> Result<Vec<(ndarray::Array2<f32>, usize)>, HipError> {
