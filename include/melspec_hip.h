@@ -396,6 +396,40 @@ int melspec_fbank_compute_batch_host(melspec_fbank *fb, const float *samples, co
 int melspec_fbank_release_scratch(melspec_fbank *fb);
 int melspec_fbank_synchronize(melspec_fbank *fb, void *stream);
 
+/* ---- 16-bit ends for the Kaldi fbank: int16 PCM in, f16 / bf16 features out --------------------------------------------------------
+ * MELSPEC_PCM_* / MELSPEC_OUT_* as above, with the same meaning: a MELSPEC_PCM_S16 sample's value is int16 * 2^-15, exactly -- the
+ * call gives the bits of the f32 call on the batch converted by `v as f32 / 32768.0`; DC removal, pre-emphasis and the Povey window
+ * (src/fbank.rs:164-190) are applied to the converted samples with the roundings the f32 kernel has, the first-sample patch of
+ * src/fbank.rs:172 included.  MELSPEC_OUT_F16 / _BF16: every element of [frame][num_mel_bins] is the f32 element the f32 call writes,
+ * rounded to nearest even ONCE; a NaN stays a NaN, a value beyond the f16 range (possible with use_log_fbank = 0) becomes an infinity.
+ * With apply_cmn the means are those of the f32 rows, from the fixed summation tree of the fused path, and only row - mean is rounded:
+ * the fbank kernel writes its f32 rows into a scratch of the object (grow-only, frames * num_mel_bins * 4 bytes summed over the clips;
+ * given back by melspec_fbank_release_scratch) and the CMN pass reads them there and writes the 16-bit rows to the caller.  Without
+ * CMN there is no scratch and no second pass; (S16, F32) with CMN normalises the caller's f32 rows in place like the f32 call.
+ * Strides, offsets, lengths and capacities count ELEMENTS, never bytes; only natural alignment of the element type is required (a
+ * ragged int16 clip may start at an odd sample, a 16-bit clip output at an odd element).  Everything else -- frame count, clips
+ * without a frame, stream ordering, error codes -- is that of melspec_fbank_compute_uniform_device / _ragged_device / _host.
+ * (F32, F32) is always supported and is routed to the existing calls unchanged.  The other five combinations are computed by the
+ * fused path with the compile-time 80-bin Kaldi bank (melspec_fbank_uses_fast_path == 1 and that bank: 16 kHz, 25 ms frames, 80 bins,
+ * low_freq 20, high_freq Nyquist -- the default geometry; the frame shift, 10 ms by default, is a run-time value of the kernel and not
+ * part of the condition) with any preemphasis, use_log_fbank, use_power, energy_floor and apply_cmn (melspec_fbank_supports_io == 1);
+ * every other object -- other banks, other geometries, an object after melspec_fbank_use_generic(fb, on != 0) -- returns
+ * MELSPEC_ERR_UNSUPPORTED, names its geometry in melspec_last_error and does not touch the output.  These calls always run the
+ * two-kernel path (the wave-owned fbank kernel, then the CMN), never the workgroup-per-clip kernel the f32 call picks for large
+ * uniform batches; the two paths give the same bits.
+ * Measured on an MI355X at config 3 (1024 x 10 s, 80 bins, CMN on; tools/fbank_io_bench.py, profiles/fbank_io_dtypes.txt): (S16, F16)
+ * 0.769 ms per call against 1.354 ms for the status quo it replaces (int16 -> f32 cast, the f32 call, f32 -> f16 cast): 1.76 x.  It does
+ * not beat the f32 call itself (0.662 ms in the same run), which runs the single workgroup-per-clip kernel on that batch. */
+int melspec_fbank_supports_io(const melspec_fbank *fb, int pcm_dtype, int out_dtype);
+int melspec_fbank_compute_uniform_device_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                            uint32_t n_clips, void *d_out, int out_dtype, void *stream);
+int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                           const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
+                                           const uint64_t *h_out_offsets, void *stream);
+/* melspec_fbank_compute_host with 16-bit ends: the int16 bytes are what crosses the bus, and so are the 16-bit features. */
+int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples,
+                                  void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames);
+
 /* ---- NeMo/Parakeet log-mel frontend: replaces BatchLogMelSpectrogram (src/mel.rs:171-418) ------- */
 
 /* BatchLogMelConfig (src/mel.rs:171-208). */

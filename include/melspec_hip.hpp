@@ -207,6 +207,31 @@ public:
         return res;
     }
 
+    // additive: 16-bit ends (MELSPEC_PCM_*, MELSPEC_OUT_* of melspec_hip.h); strides, offsets and lengths count elements
+    bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_fbank_supports_io(fb_, pcm_dtype, out_dtype) != 0; }
+    void compute_uniform_device_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_out,
+                                   int out_dtype, void *stream = nullptr) {
+        detail::check(melspec_fbank_compute_uniform_device_io(fb_, d_pcm, pcm_dtype, clip_stride, clip_len, n_clips, d_out, out_dtype, stream), false);
+    }
+    void compute_ragged_device_io(const void *d_pcm, int pcm_dtype, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths,
+                                  void *d_out, int out_dtype, const std::uint64_t *out_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_fbank_compute_ragged_device_io(fb_, d_pcm, pcm_dtype, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), d_out,
+                                                             out_dtype, out_offsets, stream), false);
+    }
+    // compute() on 16-bit PCM (value = sample / 32768, exactly) into out_dtype features (MELSPEC_OUT_F16 / _BF16), returned as their bit
+    // patterns, (frames, num_mel_bins) row-major: the int16 bytes are what crosses the bus
+    std::vector<std::uint16_t> compute_s16(const std::vector<std::int16_t> &samples, int out_dtype, std::size_t *frames = nullptr) {
+        std::vector<std::uint16_t> out(melspec_fbank_num_frames(fb_, samples.size()) * static_cast<std::size_t>(melspec_fbank_num_mel_bins(fb_)));
+        std::size_t got = 0;
+        detail::check(melspec_fbank_compute_host_io(fb_, samples.data(), MELSPEC_PCM_S16, samples.size(), out.data(), out_dtype, out.size(), &got), false);
+        if (frames) *frames = got;
+        return out;
+    }
+    // what the device calls above need from a class that does not hand out its handle: wait for a call that ran on the object's own
+    // stream (stream == nullptr), and give back the scratch a 16-bit CMN call grows
+    void synchronize(void *stream = nullptr) { detail::check(melspec_fbank_synchronize(fb_, stream), false); }
+    void release_scratch() { detail::check(melspec_fbank_release_scratch(fb_), false); }
+
 private:
     melspec_fbank *fb_ = nullptr;
 };

@@ -3,6 +3,7 @@
 // reaches the same kernels through launch_whisper512.
 #include "host_common.hpp"
 #include "fbank512_io_kernels.hpp"
+#include "fbank512_kaldi_io_kernels.hpp"
 
 namespace melspec {
 // emitted by fbank512_io.hip: the NeMo frontend with int16 PCM in and / or f16, bf16 rows out
@@ -17,6 +18,12 @@ extern template __global__ void blm_normalize_io_kernel<io_f16>(const BlmNormIoP
 extern template __global__ void blm_normalize_io_kernel<io_bf16>(const BlmNormIoParams);
 extern template __global__ void blm_normalize_ragged_io_kernel<io_f16>(const BlmNormRaggedIoParams);
 extern template __global__ void blm_normalize_ragged_io_kernel<io_bf16>(const BlmNormRaggedIoParams);
+// emitted by fbank512_kaldi_io.hip: the Kaldi fbank with the same 16-bit ends
+#define MS_IO_EXTERN(In, Out) extern template __global__ void fbank512_kaldi_io_kernel<double, 8, kFbSlots, LensKaldi80, In, Out>(const FbankFastParams);
+MS_IO_COMBOS(MS_IO_EXTERN)
+#undef MS_IO_EXTERN
+extern template __global__ void cmn_io_kernel<io_f16>(const CmnIoParams);
+extern template __global__ void cmn_io_kernel<io_bf16>(const CmnIoParams);
 }  // namespace melspec
 
 namespace {
@@ -181,6 +188,9 @@ struct melspec_fbank {
     int waves = 4;
     GenericTables gt;
     DevBuf h2d, d2h;
+    DevBuf rows32;              // apply_cmn with f16 / bf16 rows out: the f32 rows between the fbank kernel and the CMN, then the caller's
+    hipStream_t rows32_stream = nullptr;    //   output offsets of a ragged batch (frames * num_mel_bins * 4 + n_clips * 8 bytes; grow-only,
+    bool rows32_used = false;               //   used in stream order: a call on another stream first waits for the stream that used it last)
 };
 
 
@@ -247,6 +257,7 @@ void melspec_fbank_destroy(melspec_fbank *fb) {
     if (fb->dev.device >= 0) (void)hipSetDevice(fb->dev.device);
     if (fb->stream) { (void)hipStreamSynchronize(fb->stream); (void)hipStreamDestroy(fb->stream); }
     fb->gt.release(); fb->d_blob.release(); fb->h2d.release(); fb->d2h.release(); fb->ragged.release(); fb->dplan.release(); fb->pipe.release();
+    fb->rows32.release();
     delete fb;
 }
 
@@ -263,6 +274,60 @@ int melspec_fbank_use_generic(melspec_fbank *fb, int on) {
 }
 
 static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, float *d_means = nullptr);
+
+static double fbank_floor(const melspec_fbank *fb) { return fb->cfg.energy_floor > 0.0 ? fb->cfg.energy_floor : static_cast<double>(FLT_EPSILON); }
+
+// the fused kernels' parameters of a batch of this object
+static FbankFastParams fbank_fast_params(const melspec_fbank *fb, const BatchDesc &desc) {
+    FbankFastParams fp{};
+    fp.b = desc;
+    fp.d_blob = static_cast<const uint32_t *>(fb->d_blob.p);
+    fp.blob_words = static_cast<int>(fb->ft.blob.size());
+    fp.mel_off_words = fb->ft.mel_off_words;
+    fp.shift = fb->frame_shift;
+    fp.n_mels = fb->cfg.num_mel_bins;
+    fp.preemph = fb->cfg.preemphasis > 0.0 ? fb->cfg.preemphasis : 0.0;   // src/fbank.rs:172
+    fp.floor_v = static_cast<float>(fbank_floor(fb));
+    fp.use_log = fb->cfg.use_log_fbank;
+    fp.use_power = fb->cfg.use_power;
+    fp.slots = fb->ft.slots;
+    return fp;
+}
+
+// cmn_kernel's and cmn_io_kernel's shape: rows staged per chunk (0: the column form) and the dynamic LDS of a workgroup
+static void cmn_shape(int nm, uint64_t fpc /* frames of the longest clip */, int &rows_per_chunk, size_t &lds) {
+    // rows staged per chunk (a multiple of 4: the fold works on units of 4 frames): what fits one workgroup's LDS next to the means and
+    // the run sums; two workgroups per CU when a whole clip fits half of it
+    const size_t head = static_cast<size_t>((nm + 3) & ~3) * 9 * sizeof(float);
+    const bool staged = nm <= 512;
+    size_t budget = kLdsLimit - head - 256;
+    if (fpc * static_cast<uint64_t>(nm) * sizeof(float) + head <= kLdsLimit / 2 - 256) budget = kLdsLimit / 2 - head - 256;
+    uint64_t rows = (budget / (static_cast<size_t>(nm) * sizeof(float))) & ~3ull;
+    if (rows > ((fpc + 3) & ~3ull)) rows = (fpc + 3) & ~3ull;
+    rows_per_chunk = staged ? static_cast<int>(rows) : 0;
+    lds = staged ? head + static_cast<size_t>(rows_per_chunk) * nm * sizeof(float)
+                 : (static_cast<size_t>((nm + 3) & ~3) + 8 * 512 + 512) * sizeof(float);
+}
+
+// the CMN pass of a batch, in place on the f32 rows (d_means: the split output, see fbank_launch): walks clips, not units
+static int fbank_cmn(melspec_fbank *fb, const BatchDesc &desc, uint32_t n_clips, uint64_t fpc, hipStream_t s, float *d_means) {
+    const int nm = fb->cfg.num_mel_bins;
+    CmnParams cp{};
+    cp.b = desc;
+    cp.n_mels = nm;
+    size_t lds;
+    cmn_shape(nm, fpc, cp.rows_per_chunk, lds);
+    cp.d_means = d_means;
+    static std::atomic<uint64_t> cmn_attr{0};
+    if (!device_done(cmn_attr)) {
+        if (int rc = allow_big_lds(&cmn_kernel<512>, "hipFuncSetAttribute(cmn_kernel)")) return rc;
+        mark_device_done(cmn_attr);
+    }
+    const unsigned grid = grid_for(n_clips, fb->dev.cus, 8);
+    hipLaunchKernelGGL(cmn_kernel<512>, dim3(grid), dim3(512), lds, s, cp);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
 
 int melspec_fbank_compute_uniform_device(melspec_fbank *fb, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
                                          uint32_t n_clips, float *d_out, void *stream) {
@@ -304,21 +369,10 @@ static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips
                         float *d_means /* not nullptr: the split output -- un-normalised rows + the clips' column means */) {
     const int nm = fb->cfg.num_mel_bins;
     const bool fused = fb->fast && !fb->use_generic;
-    const double floor_v = fb->cfg.energy_floor > 0.0 ? fb->cfg.energy_floor : static_cast<double>(FLT_EPSILON);
+    const double floor_v = fbank_floor(fb);
     int rc = MELSPEC_OK;
     if (fused) {
-        FbankFastParams fp{};
-        fp.b = pl.desc;
-        fp.d_blob = static_cast<const uint32_t *>(fb->d_blob.p);
-        fp.blob_words = static_cast<int>(fb->ft.blob.size());
-        fp.mel_off_words = fb->ft.mel_off_words;
-        fp.shift = fb->frame_shift;
-        fp.n_mels = nm;
-        fp.preemph = fb->cfg.preemphasis > 0.0 ? fb->cfg.preemphasis : 0.0;   // src/fbank.rs:172
-        fp.floor_v = static_cast<float>(floor_v);
-        fp.use_log = fb->cfg.use_log_fbank;
-        fp.use_power = fb->cfg.use_power;
-        fp.slots = fb->ft.slots;
+        const FbankFastParams fp = fbank_fast_params(fb, pl.desc);
         // many clips of one length + CMN: the workgroup-per-clip kernel with the normalisation inside (fbank512_clip_kernel) when the
         // clips fill the CUs evenly enough to beat the two-kernel path's 1.29 x (lab builds: MELSPEC_FB_CLIP=0 keeps the two kernels)
         static const bool clip_on = lab_int("MELSPEC_FB_CLIP", 1, 0, 1) != 0;
@@ -373,31 +427,7 @@ static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips
                             fb->cfg.preemphasis, floor_v, fb->dev.cus, s);
     }
     if (rc) return rc;
-    if (fb->cfg.apply_cmn) {
-        CmnParams cp{};
-        cp.b = pl.desc;
-        cp.n_mels = nm;
-        // rows staged per chunk (a multiple of 4: the fold works on units of 4 frames): what fits one workgroup's LDS next to the means and
-        // the run sums; two workgroups per CU when a whole clip fits half of it
-        const size_t head = static_cast<size_t>((nm + 3) & ~3) * 9 * sizeof(float);
-        const bool staged = nm <= 512;
-        size_t budget = kLdsLimit - head - 256;
-        if (fpc * static_cast<uint64_t>(nm) * sizeof(float) + head <= kLdsLimit / 2 - 256) budget = kLdsLimit / 2 - head - 256;
-        uint64_t rows = (budget / (static_cast<size_t>(nm) * sizeof(float))) & ~3ull;
-        if (rows > ((fpc + 3) & ~3ull)) rows = (fpc + 3) & ~3ull;
-        cp.rows_per_chunk = staged ? static_cast<int>(rows) : 0;
-        cp.d_means = d_means;
-        static std::atomic<uint64_t> cmn_attr{0};
-        if (!device_done(cmn_attr)) {
-            if ((rc = allow_big_lds(&cmn_kernel<512>, "hipFuncSetAttribute(cmn_kernel)"))) return rc;
-            mark_device_done(cmn_attr);
-        }
-        const size_t lds = staged ? head + static_cast<size_t>(cp.rows_per_chunk) * nm * sizeof(float)
-                                  : (static_cast<size_t>((nm + 3) & ~3) + 8 * 512 + 512) * sizeof(float);
-        const unsigned grid = grid_for(n_clips, fb->dev.cus, 8);
-        hipLaunchKernelGGL(cmn_kernel<512>, dim3(grid), dim3(512), lds, s, cp);
-        HIP_TRY(hipGetLastError());
-    }
+    if (fb->cfg.apply_cmn) return fbank_cmn(fb, pl.desc, n_clips, fpc, s, d_means);
     return MELSPEC_OK;
 }
 
@@ -453,7 +483,9 @@ int melspec_fbank_release_scratch(melspec_fbank *fb) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     HIP_TRY(hipSetDevice(fb->dev.device));
     HIP_TRY(hipStreamSynchronize(fb->stream));
-    fb->pipe.release(); fb->ragged.release(); fb->dplan.release(); fb->h2d.release(); fb->d2h.release();
+    if (fb->rows32_used && fb->rows32_stream != fb->stream) HIP_TRY(hipStreamSynchronize(fb->rows32_stream));
+    fb->pipe.release(); fb->ragged.release(); fb->dplan.release(); fb->h2d.release(); fb->d2h.release(); fb->rows32.release();
+    fb->rows32_used = false;
     return MELSPEC_OK;
 }
 
@@ -1177,5 +1209,199 @@ int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const u
     return rc;
 }
 
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------
+// Kaldi fbank with int16 PCM in / f16, bf16 rows out (melspec_fbank_compute_*_io): see include/melspec_hip.h
+// ------------------------------------------------------------------------------------
+namespace {
+// the objects whose kernels have the instantiations: the fused path on eight f64 waves with the compile-time 80-bin Kaldi bank.  The
+// frame shift is not part of the condition: it is a run-time value of the kernel (FbankFastParams::shift), the default 10 ms or not.
+bool fbank_io_ok(const melspec_fbank *fb) { return fb->fast && !fb->use_generic && fb->waves == 8 && fb_lens_match<LensKaldi80>(fb->ft.slots); }
+
+// 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
+int fbank_io_args(const melspec_fbank *fb, int pcm_dtype, int out_dtype, int &io) {
+    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
+    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
+        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    if (io && !fbank_io_ok(fb)) {
+        char geo[256];
+        std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d, low_freq = %g, high_freq = %g",
+                      fb->cfg.sample_rate, fb->frame_len, fb->frame_shift, fb->cfg.num_mel_bins, fb->cfg.low_freq, fb->cfg.high_freq);
+        g_last_error = std::string("int16 PCM / f16, bf16 rows are computed by the fused fbank path with the compile-time 80-bin Kaldi bank only (16 kHz, "
+                                   "400-sample frames, any frame shift, 80 bins, low_freq 20, high_freq Nyquist); this object is ") + geo +
+                       (fb->use_generic ? " on the generic path (melspec_fbank_use_generic)" : (fb->fast ? " (another filterbank)" : ""));
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    return MELSPEC_OK;
+}
+
+// the wave-owned kernel of a (sample, row) combination on fp, a batch planned like the f32 call's: launch_fused512's grid and LDS size
+int launch_kaldi_io(melspec_fbank *fb, const FbankFastParams &fp, int pcm, int out, hipStream_t s) {
+    typedef void (*Kernel)(const FbankFastParams);
+#define MS_KALDI_IO(In, Out) &fbank512_kaldi_io_kernel<double, 8, kFbSlots, LensKaldi80, In, Out>
+    static const Kernel table[2][3] = {{nullptr, MS_KALDI_IO(float, io_f16), MS_KALDI_IO(float, io_bf16)},
+                                       {MS_KALDI_IO(io_s16, float), MS_KALDI_IO(io_s16, io_f16), MS_KALDI_IO(io_s16, io_bf16)}};
+#undef MS_KALDI_IO
+    static std::atomic<uint64_t> attr_done[2][3];
+    if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || (pcm | out) == 0 || !fbank_io_ok(fb)) return fail(MELSPEC_ERR_INTERNAL, "launch_kaldi_io: no such combination");
+    const Kernel k = table[pcm][out];
+    if (!device_done(attr_done[pcm][out])) {
+        if (int rc = allow_big_lds(k, "hipFuncSetAttribute(fbank512_kaldi_io_kernel)")) return rc;
+        mark_device_done(attr_done[pcm][out]);
+    }
+    static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);
+    const unsigned grid = grid_for_xcd((fp.b.n_units + 7) / 8, fb->dev.cus, per_cu);
+    hipLaunchKernelGGL(k, dim3(grid), dim3(512), fb->fast_lds, s, fp);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+// the scratch of a CMN call with 16-bit rows out on stream s: `floats` f32 rows and, behind them, `tail` 64-bit words
+int fbank_rows32(melspec_fbank *fb, uint64_t floats, size_t tail, hipStream_t s, float *&rows, uint64_t *&words) {
+    if (fb->rows32_used && fb->rows32_stream != s) HIP_TRY(hipStreamSynchronize(fb->rows32_stream));
+    fb->rows32_used = true; fb->rows32_stream = s;
+    const size_t row_bytes = (static_cast<size_t>(floats) * sizeof(float) + 15) & ~static_cast<size_t>(15);
+    const int rc = fb->rows32.ensure(row_bytes + tail * sizeof(uint64_t) + 16);     // (growing frees the old buffer: hipFree waits for the device)
+    rows = static_cast<float *>(fb->rows32.p);
+    words = reinterpret_cast<uint64_t *>(static_cast<char *>(fb->rows32.p) + row_bytes);
+    return rc;
+}
+
+// The kernels of one batch of an _io call (io != 0) on an object that fbank_io_ok.  pl: the plan of the f32 call, sample offsets and
+// strides in elements; pl.desc.out is where the f32 or 16-bit rows of the wave kernel go: the caller's buffer, or -- split: CMN with
+// 16-bit rows out -- the scratch, from where cmn_io_kernel writes them to vd_out (ragged: at d_dst_off).
+int fbank_launch_io(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, int io, bool split, void *vd_out, const uint64_t *d_dst_off) {
+    const int pcm = io & 15, out_dtype = io >> 4;
+    const int kout = split ? 0 : out_dtype;           // the row type the wave kernel writes
+    const FbankFastParams fp = fbank_fast_params(fb, pl.desc);
+    // (F32 samples, f32 rows into the scratch): the existing kernel, as the f32 call's two-kernel path launches it
+    int rc = (pcm | kout) == 0 ? launch_fused512<double, kFlavorKaldi, kFbSlots, LensKaldi80>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s)
+                               : launch_kaldi_io(fb, fp, pcm, kout, s);
+    if (rc || !fb->cfg.apply_cmn) return rc;
+    if (!split) return fbank_cmn(fb, pl.desc, n_clips, fpc, s, nullptr);        // (S16, F32): the f32 rows are the caller's, in place
+    CmnIoParams cp{};
+    cp.b = pl.desc;
+    cp.dst = vd_out;
+    cp.d_dst_off = d_dst_off;
+    cp.n_mels = fb->cfg.num_mel_bins;
+    size_t lds;
+    cmn_shape(cp.n_mels, fpc, cp.rows_per_chunk, lds);
+    static std::atomic<uint64_t> attr_done{0};
+    if ((rc = allow_norm_io(&cmn_io_kernel<io_f16>, &cmn_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(cmn_io_kernel)"))) return rc;
+    const unsigned grid = grid_for(n_clips, fb->dev.cus, 8);
+    hipLaunchKernelGGL(out_dtype == MELSPEC_OUT_F16 ? cmn_io_kernel<io_f16> : cmn_io_kernel<io_bf16>, dim3(grid), dim3(kCmnThreads), lds, s, cp);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
+    return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
+}
+
+// melspec_fbank_compute_uniform_device with io = pcm_dtype | out_dtype << 4 != 0 (fbank_io_args): int16 samples and / or f16, bf16 rows
+int fbank_uniform_io(melspec_fbank *fb, const void *vd_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, void *vd_out, void *stream, int io) {
+    if (n_clips == 0) return MELSPEC_OK;
+    const uint64_t fpc = fbank_frames(fb, clip_len);
+    if (fpc == 0) return MELSPEC_OK;   // zeros((0, num_mel_bins)), src/fbank.rs:147-149
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    const int nm = fb->cfg.num_mel_bins;
+    float *d_rows = static_cast<float *>(vd_out);
+    // 16-bit rows cannot have their means subtracted in place: the wave kernel then writes f32 rows into the object's scratch
+    const bool split = (io >> 4) != 0 && fb->cfg.apply_cmn;
+    if (split) {
+        uint64_t *words;
+        if (int rc = fbank_rows32(fb, static_cast<uint64_t>(n_clips) * fpc * nm, 0, s, d_rows, words)) return rc;
+    }
+    const BatchPlan pl = plan_uniform(static_cast<const float *>(vd_pcm), d_rows, clip_stride, fpc, n_clips, nm, kFbFPW);
+    return fbank_launch_io(fb, pl, n_clips, fpc, s, io, split, vd_out, nullptr);
+}
+}  // namespace
+
+extern "C" {
+
+int melspec_fbank_supports_io(const melspec_fbank *fb, int pcm_dtype, int out_dtype) {
+    if (!fb || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || fbank_io_ok(fb) ? 1 : 0;
+}
+
+int melspec_fbank_compute_uniform_device_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                            uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
+    int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_fbank_compute_uniform_device(fb, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_out), stream);
+    return fbank_uniform_io(fb, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, io);
+}
+
+// The ragged batch on the two-kernel path (the wave-owned kernel, then the CMN per clip), whatever the batch's shape.
+int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                           const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
+                                           const uint64_t *h_out_offsets, void *stream) {
+    int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_fbank_compute_ragged_device(fb, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_out), h_out_offsets, stream);
+    if (n_clips == 0) return MELSPEC_OK;
+    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
+    std::vector<uint64_t> frames(n_clips);
+    uint64_t total = 0, longest = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) { frames[i] = fbank_frames(fb, h_lengths[i]); total += frames[i]; longest = std::max(longest, frames[i]); }
+    if (total == 0) return MELSPEC_OK;
+    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io_misaligned(d_pcm, d_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    const int nm = fb->cfg.num_mel_bins;
+    float *d_rows = static_cast<float *>(d_out);
+    // CMN with 16-bit rows: the wave kernel writes f32 rows, packed in clip order, into the scratch (fbank_uniform_io); the caller's own
+    // output offsets travel behind them
+    const bool split = out_dtype != MELSPEC_OUT_F32 && fb->cfg.apply_cmn;
+    const uint64_t *d_own = nullptr;
+    if (split) {
+        uint64_t *words;
+        if ((rc = fbank_rows32(fb, total * static_cast<uint64_t>(nm), h_out_offsets ? n_clips : 0, s, d_rows, words))) return rc;
+        if (h_out_offsets) {
+            HIP_TRY(hipMemcpyAsync(words, h_out_offsets, static_cast<size_t>(n_clips) * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
+            d_own = words;
+        }
+    }
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    rc = plan_ragged(fb->ragged, s, static_cast<const float *>(d_pcm), d_rows, h_offsets, frames, split ? nullptr : h_out_offsets, n_clips, nm, kFbFPW, pl, slot);
+    if (!rc) rc = fbank_launch_io(fb, pl, n_clips, longest, s, io, split, d_out, d_own ? d_own : pl.desc.d_out_off);
+    plan_ragged_done(slot, s);
+    return rc;
+}
+
+// One clip from host memory: the 16-bit bytes cross the bus, the kernels convert.
+int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples,
+                                  void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames) {
+    int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_fbank_compute_host(fb, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, n_frames);
+    if (n_frames) *n_frames = 0;
+    const uint64_t frames = fbank_frames(fb, n_samples);
+    if (frames == 0) return MELSPEC_OK;
+    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+    const uint64_t need = frames * static_cast<uint64_t>(fb->cfg.num_mel_bins);
+    if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
+    if ((rc = fb->h2d.ensure(n_samples * ib))) return rc;
+    if ((rc = fb->d2h.ensure(need * ob))) return rc;
+    HIP_TRY(hipMemcpyAsync(fb->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, fb->stream));
+    rc = fbank_uniform_io(fb, fb->h2d.p, n_samples, n_samples, 1, fb->d2h.p, fb->stream, io);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out, fb->d2h.p, need * ob, hipMemcpyDeviceToHost, fb->stream));
+    HIP_TRY(hipStreamSynchronize(fb->stream));
+    if (n_frames) *n_frames = static_cast<size_t>(frames);
+    return MELSPEC_OK;
+}
 
 }  // extern "C"

@@ -1025,6 +1025,10 @@ struct CmnParams {
     float *d_means; // not nullptr: write the clip's column means there ([clip][n_mels]) and leave the rows as they are (the split output)
 };
 
+// KEEP IN STEP with cmn_io_kernel (fbank512_kaldi_io_kernels.hpp), the copy that reads the rows from a scratch and writes 16-bit rows: its
+// staging, its fold of the chunks and its tree (CmnTree, above) are this kernel's operation for operation, and the host sizes both with
+// cmn_shape (fbank512.hip).  melspec_fbank_compute_*_io promises that the means of a 16-bit call are those of the f32 rows: a change to
+// the staging, the chunk fold, CmnTree or cmn_shape here is a change there too.
 template <int NT>
 __global__ __launch_bounds__(NT) void cmn_kernel(const CmnParams p) {
     extern __shared__ __attribute__((aligned(16))) float cmn_lds[];

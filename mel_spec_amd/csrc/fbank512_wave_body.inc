@@ -1,6 +1,6 @@
 // fbank512_wave_body.inc -- the body of fbank512_wave_kernel (fbank512_kernels.hpp), included once per kernel that has it: the kernel itself
-// (MS_FB512_IN = MS_FB512_OUT = float) and fbank512_nemo_io_kernel (fbank512_io_kernels.hpp: int16 samples in, f16 / bf16 rows out, NeMo
-// flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
+// (MS_FB512_IN = MS_FB512_OUT = float), fbank512_nemo_io_kernel (fbank512_io_kernels.hpp: int16 samples in, f16 / bf16 rows out, NeMo
+// flavour) and fbank512_kaldi_io_kernel (fbank512_kaldi_io_kernels.hpp: the same ends, Kaldi flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
     using L = FbankLayout<T>;
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
     const int tid = threadIdx.x;
@@ -62,7 +62,7 @@
         const bool act = in && fl < nv;
         MS_PRIO(0);
         if constexpr (FLAVOR == kFlavorKaldi) {
-            const float *frame = loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift;
+            const MS_FB512_IN *frame = loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift;
             // the frame mean (src/fbank.rs:165-166: the frame's sixteen lanes, a fixed tree over DPP), DC removal, pre-emphasis and the Povey window
             // from ONE set of loads (fb_kaldi_input)
             if (act) {

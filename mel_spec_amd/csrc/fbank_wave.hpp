@@ -332,15 +332,17 @@ template <class T> MS_DEV T row_sum16(T v) { return v; }      // host pass of th
 // in f32 registers (39) for both the frame sum and the column, so the column does not start with a second memory round trip behind the
 // mean.  Same operations in the same order as the two functions (bit-identical).  Every load unconditional and branch-free: the 13th pair of lanes
 // n2 >= 8 re-reads pair 0 and is dropped by selects (a guarded load is a memory round trip of its own).
-template <class T>
-MS_DEV void fb_kaldi_input(const float *frame, int n2, T preemph, bool patch_first, const T *tblob, cpx<T> (&x)[16]) {
+// In: the sample type (float; int16_t in fbank512_kaldi_io_kernel: one 4-byte load per pair at 2-byte alignment and a 2-byte load for the
+// sample in front of it, times 2^-15, exact -- load2_unaligned / pcm_value in whisper_wave.hpp; the same sample indices as the f32 loads)
+template <class T, class In = float>
+MS_DEV void fb_kaldi_input(const In *frame, int n2, T preemph, bool patch_first, const T *tblob, cpx<T> (&x)[16]) {
     f2 c[13];
     float prev[13];
 #pragma unroll
     for (int n1 = 0; n1 < 13; ++n1) {
         const int i = (n1 < 12 || n2 < 8) ? 32 * n1 + 2 * n2 : 2;       // (not 0: its predecessor would be frame[-1], which for the first frame of a buffer is not mapped)
         c[n1] = load2_unaligned(frame + i);
-        prev[n1] = frame[(n1 == 0 && patch_first) ? 0 : i - 1];
+        prev[n1] = pcm_value(frame[(n1 == 0 && patch_first) ? 0 : i - 1]);
     }
 #if defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_sched_barrier(MS_SCHED_LOADS_FIRST);
@@ -516,11 +518,12 @@ MS_DEV float fast_ln(float x) { return fast_log2(x) * 0.69314718055994531f; }
 
 // floor, ln, store (src/fbank.rs:207-221).  out_tile = &out[first frame of the tile][0].  vals (optional): the stored
 // features of this lane, mel j + 15 i of frame fl (for the in-order column sums of the CMN, fbank512_clip_kernel).
-template <int NSLOTS = kFbSlots>
+// Out: the row type (float; _Float16 / __bf16 in fbank512_kaldi_io_kernel: the f32 value rounded to nearest even by the store's conversion)
+template <int NSLOTS = kFbSlots, class Out = float>
 MS_DEV void fb_phase3_store(int fl, int j, bool active, int n_mels, float floor_v, bool use_log,
-                            const float (&rise)[NSLOTS], const float (&fnext)[NSLOTS], float *out_tile, float *vals = nullptr) {
+                            const float (&rise)[NSLOTS], const float (&fnext)[NSLOTS], Out *out_tile, float *vals = nullptr) {
     if (!active || j >= kFbOwn) return;
-    float *o = out_tile + static_cast<long long>(fl) * n_mels + j;
+    Out *o = out_tile + static_cast<long long>(fl) * n_mels + j;
 #pragma unroll
     for (int i = 0; i < NSLOTS; ++i) {
         const int m = j + kFbOwn * i;
@@ -528,7 +531,7 @@ MS_DEV void fb_phase3_store(int fl, int j, bool active, int n_mels, float floor_
             float e = rise[i] + fnext[i];
             e = __builtin_fmaxf(e, floor_v);
             const float v = use_log ? fast_ln(e) : e;
-            o[kFbOwn * i] = v;
+            o[kFbOwn * i] = row_value<Out>(v);
             if (vals) vals[i] = v;
         }
     }

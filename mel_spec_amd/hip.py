@@ -596,6 +596,42 @@ class Fbank:
         _check(lib().melspec_fbank_compute_uniform_device_split(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
                                                                 C.c_void_p(d_rows), C.c_void_p(d_means), C.c_void_p(stream)))
 
+    # -- 16-bit ends: int16 PCM in, f16 / bf16 features out (melspec_hip.h; codes PCM_* / OUT_* of this module) ------------------------
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(lib().melspec_fbank_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
+                                  stream: int = 0) -> None:
+        """compute_uniform_device on int16 samples and / or into f16 / bf16 features; strides count elements."""
+        _check(lib().melspec_fbank_compute_uniform_device_io(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
+                                                             C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
+
+    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
+                                 stream: int = 0) -> None:
+        """compute_ragged_device on int16 samples and / or into f16 / bf16 features; offsets and lengths count elements."""
+        off = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
+        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
+        u64p = C.POINTER(C.c_uint64)
+        _check(lib().melspec_fbank_compute_ragged_device_io(
+            self._h, C.c_void_p(d_pcm), int(pcm_dtype), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
+            C.c_void_p(d_out), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
+
+    def compute_host_io(self, samples, out_dtype=None) -> np.ndarray:
+        """compute on one host clip with 16-bit ends: an np.int16 array is taken as 16-bit PCM (value = sample / 32768, exactly);
+        out_dtype "f16" (or np.float16) returns np.float16 features, "bf16" the bfloat16 bit patterns as np.uint16."""
+        a = np.asarray(samples)
+        pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        out = _out_code(out_dtype)
+        x = np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1)
+        nf = self.num_frames(x.shape[0])
+        res = np.zeros((nf, self.num_mel_bins), _OUT_NUMPY[out])
+        got = C.c_size_t(0)
+        _check(lib().melspec_fbank_compute_host_io(self._h, x.ctypes.data_as(C.c_void_p), pcm, x.shape[0], res.ctypes.data_as(C.c_void_p), out,
+                                                   res.size, C.byref(got)))
+        assert got.value == nf
+        return res
+
     def synchronize(self, stream: int = 0) -> None:
         _check(lib().melspec_fbank_synchronize(self._h, C.c_void_p(stream)))
 

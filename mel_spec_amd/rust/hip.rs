@@ -69,6 +69,13 @@ unsafe extern "C" {
     fn melspec_fbank_destroy(fb: *mut FbankHandle);
     fn melspec_fbank_num_frames(fb: *const FbankHandle, n: usize) -> usize;
     fn melspec_fbank_compute_host(fb: *mut FbankHandle, samples: *const f32, n: usize, out: *mut f32, cap: usize, frames: *mut usize) -> c_int;
+    fn melspec_fbank_supports_io(fb: *const FbankHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_fbank_compute_uniform_device_io(fb: *mut FbankHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                               d_out: *mut c_void, out_dtype: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_fbank_compute_ragged_device_io(fb: *mut FbankHandle, d_pcm: *const c_void, pcm_dtype: c_int, h_offsets: *const u64, h_lengths: *const u64,
+                                              n_clips: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
+    fn melspec_fbank_compute_host_io(fb: *mut FbankHandle, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, out: *mut c_void, out_dtype: c_int,
+                                     out_capacity_elems: usize, n_frames: *mut usize) -> c_int;
     fn melspec_fbank_compute_batch_host(fb: *mut FbankHandle, samples: *const f32, offsets: *const u64, lengths: *const u64, n_clips: u32,
                                         out: *mut f32, out_offsets: *const u64, cap: usize, total_frames: *mut u64) -> c_int;
     // BatchLogMelSpectrogram (src/mel.rs:171-418)
@@ -588,6 +595,46 @@ impl HipFbank {
             cur += n;
         }
         Ok(out)
+    }
+    /// Additive: does this object take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` features (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?
+    pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_fbank_supports_io(self.fb, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+    /// Additive: equal-length clips resident in device memory, int16 samples and / or f16 / bf16 features (strides count elements).
+    ///
+    /// # Safety
+    /// `d_pcm` / `d_out` must be device pointers valid for `n_clips * clip_stride` samples of `pcm_dtype` and
+    /// `n_clips * frames * num_mel_bins` values of `out_dtype`.
+    pub unsafe fn compute_uniform_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                            d_out: *mut c_void, out_dtype: i32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_fbank_compute_uniform_device_io(self.fb, d_pcm, pcm_dtype as c_int, clip_stride, clip_len, n_clips, d_out, out_dtype as c_int, stream))
+    }
+    /// Additive: clips of any lengths in one call; clip `i`'s `[frames][num_mel_bins]` rows start at element `out_offsets[i]` of `d_out`
+    /// (`None`: packed back to back in clip order).  Offsets and lengths count elements of their type.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`, and `d_out` must hold the rows of all clips in `out_dtype` where the
+    /// offsets put them.
+    pub unsafe fn compute_ragged_device_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, offsets: &[u64], lengths: &[u64], d_out: *mut c_void,
+                                           out_dtype: i32, out_offsets: Option<&[u64]>, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        if let Some(o) = out_offsets {
+            assert_eq!(o.len(), offsets.len());
+        }
+        check(melspec_fbank_compute_ragged_device_io(self.fb, d_pcm, pcm_dtype as c_int, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_out,
+                                                     out_dtype as c_int, out_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), stream))
+    }
+    /// Additive: `compute` on 16-bit PCM (value = sample / 32768, exactly) into bf16 features, returned flat as their bit patterns
+    /// with the frame count: the int16 bytes are what crosses the bus.
+    pub fn compute_s16_bf16(&mut self, samples: &[i16]) -> Result<(Vec<u16>, usize), HipError> {
+        let frames = unsafe { melspec_fbank_num_frames(self.fb, samples.len()) };
+        let mut flat = vec![0u16; frames * self.num_mel_bins];
+        let mut got = 0usize;
+        check(unsafe {
+            melspec_fbank_compute_host_io(self.fb, samples.as_ptr() as *const c_void, PCM_S16, samples.len(), flat.as_mut_ptr() as *mut c_void, OUT_BF16,
+                                          flat.len(), &mut got)
+        })?;
+        Ok((flat, got))
     }
 }
 impl Drop for HipFbank {
