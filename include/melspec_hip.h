@@ -550,6 +550,30 @@ float *melspec_stream_input_ptr(melspec_stream *st, uint32_t id);
 int melspec_stream_push_device(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, float *d_out,
                                const uint64_t *out_offsets, uint32_t *frames_out, void *stream);
 
+/* int16 PCM chunks in, f16 / bf16 rows out: the pushes above with typed ends (MELSPEC_PCM_* / MELSPEC_OUT_* as for the batch calls).
+ * The bank's state stays f32.  A MELSPEC_PCM_S16 sample's value is int16 * 2^-15, exactly, converted where the chunk is copied into the
+ * state: carry, history and every later frame are the bits the f32 bank holds after the same pushes of the converted chunks, for every
+ * geometry a bank runs.  Rows of a MELSPEC_OUT_F16 / _BF16 push are the f32 rows the f32 push would emit for the same history, rounded
+ * to nearest even once (a NaN stays a NaN), written by the frame kernels' own stores; they need melspec_supports_io(ctx,
+ * MELSPEC_PCM_F32, out_dtype) -- the n_fft = 400 contexts with Whisper's 80- or 128-mel bank -- and the detector stage off (it reads
+ * f32 rows): otherwise MELSPEC_ERR_UNSUPPORTED, melspec_last_error naming the geometry, nothing queued, the bank as it was.
+ * Frame counts, first-frame alignment, flush, reset, error codes and "the launches have completed on return" are those of the f32
+ * calls; capacities and offsets count elements of the row type, buffers need their element type's alignment only.  (F32, F32) is the
+ * existing call.  Checked in this order: NULL bank, dtype codes, support, then what the f32 call checks.
+ * melspec_stream_supports_io: 1 for any valid pcm_dtype with MELSPEC_OUT_F32; for _F16 / _BF16 what melspec_supports_io says of the ctx. */
+int melspec_stream_supports_io(const melspec_stream *st, int pcm_dtype, int out_dtype);
+int melspec_stream_push_host_io(melspec_stream *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                void *out, int out_dtype, size_t out_capacity_elems, uint32_t *frames_out);
+int melspec_stream_flush_host_io(melspec_stream *st, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems,
+                                 uint32_t *frames_out);
+/* d_chunks != NULL: chunk i is d_chunks[h_src_offsets[i] .. + lens[i]) in elements of pcm_dtype, anywhere in device memory
+ * (h_src_offsets == NULL: back to back in entry order; an int16 chunk may start at an odd element); it is copied into the bank on
+ * `stream`.  d_chunks == NULL: the chunks are already at melspec_stream_input_ptr, in f32 -- pcm_dtype must be MELSPEC_PCM_F32.
+ * Rows go to d_out + out_offsets[i] elements of out_dtype (a 16-bit output may start at an odd element). */
+int melspec_stream_push_device_io(melspec_stream *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                  const uint32_t *lens, uint32_t n, void *d_out, int out_dtype, const uint64_t *out_offsets,
+                                  uint32_t *frames_out, void *stream);
+
 /* ---- 8-bit quantisation + TGA container: replaces src/quant.rs ------------------------ */
 /* The reference's wire/disk format right after the mel path: a mel-major interleaved image
  * ([n_mels][width] f32, what melspec_compute_uniform_device_interleaved(.., major_column_order = 0, ..)

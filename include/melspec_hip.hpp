@@ -369,6 +369,38 @@ public:
         return col;
     }
 
+    // additive: 16-bit ends (melspec_stream_*_io; MELSPEC_PCM_*, MELSPEC_OUT_* of melspec_hip.h).  These push at once: feed a stream
+    // either through them or through add_frame() / maybe_mel(), not both (samples add_frame() still holds would come after theirs).
+    bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_stream_supports_io(st_, pcm_dtype, out_dtype) != 0; }
+    // a block of 16-bit PCM (value = sample / 32768, exactly; at most the capacity) -> the rows it completes as out_dtype
+    // (MELSPEC_OUT_F16 / _BF16) bit patterns, [frames][n_mels]: the int16 bytes are what crosses the bus
+    std::vector<std::uint16_t> push_s16(const std::vector<std::int16_t> &samples, int out_dtype, std::size_t *frames = nullptr) {
+        const std::uint32_t id = 0, len = static_cast<std::uint32_t>(samples.size());
+        std::uint32_t got = 0;
+        std::vector<std::uint16_t> out(melspec_stream_frames_after(st_, 0, len) * n_mels_);
+        detail::check(melspec_stream_push_host_io(st_, &id, samples.data(), MELSPEC_PCM_S16, &len, 1, out.data(), out_dtype, out.size(), &got), false);
+        out.resize(static_cast<std::size_t>(got) * n_mels_);
+        if (frames) *frames = got;
+        return out;
+    }
+    // the pending (< hop) samples zero-padded to a hop: at most one more row, as out_dtype (MELSPEC_OUT_F16 / _BF16) bit patterns
+    std::vector<std::uint16_t> flush_io(int out_dtype) {
+        const std::uint32_t id = 0;
+        std::uint32_t got = 0;
+        std::vector<std::uint16_t> out(n_mels_);
+        detail::check(melspec_stream_flush_host_io(st_, &id, 1, out.data(), out_dtype, out.size(), &got), false);
+        out.resize(static_cast<std::size_t>(got) * n_mels_);
+        return out;
+    }
+    // a chunk of pcm_dtype elements that lies in device memory (d_chunk == nullptr: f32 at the stream's input slot) -> rows of out_dtype
+    // at d_out; returns the frames emitted, after the launches have completed
+    std::uint32_t push_device_io(const void *d_chunk, int pcm_dtype, std::uint32_t len, void *d_out, int out_dtype, void *stream = nullptr) {
+        const std::uint32_t id = 0;
+        std::uint32_t got = 0;
+        detail::check(melspec_stream_push_device_io(st_, &id, d_chunk, pcm_dtype, nullptr, &len, 1, d_out, out_dtype, nullptr, &got, stream), false);
+        return got;
+    }
+
 private:
     melspec_stream *st_ = nullptr;
     std::size_t n_mels_, cap_, next_ = 0;

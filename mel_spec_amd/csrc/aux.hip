@@ -522,9 +522,11 @@ struct melspec_stream {
         bool valid = false;
         uint32_t n = 0;
         int fpu = 0;
+        int io = 0;                          // pcm | out << 4 of the push (the frame launch is the one of its row type)
         const void *d_out = nullptr;
         std::vector<uint32_t> ids, lens, pend;
         std::vector<uint64_t> out_off;       // the caller's row offsets (empty: packed)
+        std::vector<uint64_t> src_off;       // a device producer's chunk offsets (empty: back to back -- they follow from lens)
         StreamPlan pl;
         const StreamEntry *d_e = nullptr;    // the entries in the ring slot of the push that filled the cache
         BatchPlan plan;
@@ -553,20 +555,28 @@ struct StreamEmit {
 // scatter (optional) -> frames -> carry update, all on one stream
 // does this push repeat the cached one?  (ids / lens / pending before the push; every stream was past its first window when the cache
 // was filled and idx only grows, resets invalidate)
-bool stream_cache_hit(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, const void *d_out, const uint64_t *h_out_off) {
+// io / h_src_off: the element types of the push and a device producer's chunk offsets (the _io pushes) -- the cached entries hold the
+// chunk offsets, the cached plan the row offsets in elements of its row type
+bool stream_cache_hit(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, const void *d_out, const uint64_t *h_out_off,
+                      int io = 0, const uint64_t *h_src_off = nullptr) {
     const melspec_stream::PushCache &k = st->cache;
     if (!k.valid || k.n != n || k.d_out != d_out || k.out_off.empty() != (h_out_off == nullptr)) return false;
+    if (k.io != io || k.src_off.empty() != (h_src_off == nullptr)) return false;
     if (k.fpu != ctx_frames_per_unit(st->ctx)) return false;            // AUTO changed its regime: another unit size
     for (uint32_t i = 0; i < n; ++i)
         if (ids[i] != k.ids[i] || lens[i] != k.lens[i] || st->book.pending[ids[i]] != k.pend[i]) return false;
+    if (h_src_off && std::memcmp(h_src_off, k.src_off.data(), static_cast<size_t>(n) * sizeof(uint64_t)) != 0) return false;
     return h_out_off == nullptr || std::memcmp(h_out_off, k.out_off.data(), static_cast<size_t>(n) * sizeof(uint64_t)) == 0;
 }
 
 // reuse: `pl` is st->cache.pl and the device still holds its entries and plan (stream_cache_hit); ids / lens: the push's arguments,
 // for filling the cache (NULL: do not, e.g. a flush)
-int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const float *d_src, void *d_out, const uint64_t *h_out_off,
+// io = pcm_dtype | out_dtype << 4 (stream_io_args): d_src holds elements of the sample type, the scatter converts them into the f32 state;
+// the frame kernels read that state, so only the out half of the code reaches launch_ctx.  h_src_off: where a device producer's chunks
+// start in d_src, in elements (NULL: back to back, the plan's own offsets)
+int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const void *d_src, void *d_out, const uint64_t *h_out_off,
                hipStream_t s, const StreamEmit &emit = StreamEmit(), melspec_vad_activity *d_acts = nullptr, bool reuse = false,
-               const uint32_t *ids = nullptr, const uint32_t *lens = nullptr) {
+               const uint32_t *ids = nullptr, const uint32_t *lens = nullptr, int io = 0, const uint64_t *h_src_off = nullptr) {
     melspec_ctx *c = st->ctx;
     HIP_TRY(hipSetDevice(c->dev.device));
     if (pl.total_frames && !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");      // before anything is queued
@@ -592,6 +602,8 @@ int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const float
         std::memcpy(sl.host, pl.entries.data(), static_cast<size_t>(n) * sizeof(StreamEntry));
         if (h_out_off)                                   // caller-placed rows: the detector stage reads them where they are
             for (uint32_t i = 0; i < n; ++i) static_cast<StreamEntry *>(sl.host)[i].out_off = h_out_off[i];
+        if (h_src_off)
+            for (uint32_t i = 0; i < n; ++i) static_cast<StreamEntry *>(sl.host)[i].src_off = h_src_off[i];
         // from here on the slot is in use by queued work: every exit records its event (the next user of the slot waits for it)
         slot_guard.sl = &sl;
         const size_t n16 = ebytes / 16;
@@ -605,7 +617,12 @@ int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const float
     bool any_fill = d_src != nullptr;
     for (uint32_t i = 0; i < n && !any_fill; ++i) any_fill = pl.entries[i].zero_fill != 0;
     if (any_fill) {
-        hipLaunchKernelGGL(stream_scatter_kernel, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e, d_src);
+        if ((io & 15) == MELSPEC_PCM_S16)
+            hipLaunchKernelGGL(stream_scatter_kernel<io_s16>, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e,
+                               static_cast<const io_s16 *>(d_src));
+        else
+            hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e,
+                               static_cast<const float *>(d_src));
         HIP_TRY(hipGetLastError());
     }
     if (pl.total_frames && emit.stft) {
@@ -616,8 +633,9 @@ int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const float
         rc = melspec_stft_ragged_device(c, state, pl.off.data(), pl.len.data(), n, d_out, h_out_off ? h_out_off : oo.data(), emit.dtype, emit.full, s);
         if (rc) return rc;
     } else if (pl.total_frames) {
+        const int out_only_io = io & ~15;       // the frame kernel's PCM is the f32 state whatever the chunks were
         if (reuse) {
-            rc = launch_ctx(c, st->cache.plan.desc, s);
+            rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
         } else {
             // melspec_compute_ragged_device with the plan kept: frames per entry are the plan's, the ring is the bank's own
             std::vector<uint64_t> fr(n);
@@ -626,18 +644,19 @@ int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const float
             const int fpu = ctx_frames_per_unit(c);
             rc = plan_ragged(st->plan_ring, s, state, static_cast<float *>(d_out), pl.off.data(), fr, h_out_off ? h_out_off : pl.out_off.data(), n,
                              c->n_mels, fpu, st->cache.plan, pslot);
-            if (!rc) rc = launch_ctx(c, st->cache.plan.desc, s);
+            if (!rc) rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
             plan_ragged_done(pslot, s);
             // a push that can come again: every stream past its first window (no skipped hops), not a flush
             bool steady = !rc && ids != nullptr && lens != nullptr;
             for (uint32_t i = 0; i < n && steady; ++i) steady = st->book.idx[ids[i]] >= st->geom.n_fft;
             if (steady) {
                 melspec_stream::PushCache &k = st->cache;
-                k.n = n; k.fpu = fpu; k.d_out = d_out; k.d_e = d_e;
+                k.n = n; k.fpu = fpu; k.io = io; k.d_out = d_out; k.d_e = d_e;
                 k.ids.assign(ids, ids + n); k.lens.assign(lens, lens + n);
                 k.pend.resize(n);
                 for (uint32_t i = 0; i < n; ++i) k.pend[i] = st->book.pending[ids[i]];
                 if (h_out_off) k.out_off.assign(h_out_off, h_out_off + n); else k.out_off.clear();
+                if (h_src_off) k.src_off.assign(h_src_off, h_src_off + n); else k.src_off.clear();
                 k.pl = pl;
                 k.valid = true;
             }
@@ -737,21 +756,24 @@ static void stream_vad_commit(melspec_stream *st, const uint32_t *ids, const Str
     for (uint32_t i = 0; i < n; ++i) st->vad_count[ids[i]] += pl.frames[i];
 }
 
-static int stream_push_device_impl(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, float *d_out,
+// io / d_chunks / h_src_offsets: melspec_stream_push_device_io -- the element types, and chunks that lie in the caller's own device
+// buffer (NULL: already in the slots, at melspec_stream_input_ptr)
+static int stream_push_device_impl(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, void *d_out,
                                    const uint64_t *h_out_offsets, uint32_t *h_frames, melspec_vad_activity *d_acts, bool want_acts,
-                                   void *stream) {
+                                   void *stream, int io = 0, const void *d_chunks = nullptr, const uint64_t *h_src_offsets = nullptr) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
     if (want_acts && !st->vad_on) return fail(MELSPEC_ERR_INVALID_ARG, "the detector stage is off (melspec_stream_enable_vad)");
     if (n == 0) return MELSPEC_OK;
     if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
     StreamPlan fresh;
-    const bool reuse = stream_cache_hit(st, ids, lens, n, d_out, h_out_offsets);
+    if (!d_chunks) h_src_offsets = nullptr;
+    const bool reuse = stream_cache_hit(st, ids, lens, n, d_out, h_out_offsets, io, h_src_offsets);
     int rc = reuse ? MELSPEC_OK : stream_plan(st, ids, lens, n, false, fresh);
     if (rc) return rc;
     const StreamPlan &pl = reuse ? st->cache.pl : fresh;
     if (want_acts && pl.total_frames && !d_acts) return fail(MELSPEC_ERR_INVALID_ARG, "d_acts is NULL");
-    rc = stream_run(st, pl, n, nullptr, d_out, h_out_offsets, stream ? static_cast<hipStream_t>(stream) : st->ctx->stream, StreamEmit(), d_acts,
-                    reuse, ids, lens);
+    rc = stream_run(st, pl, n, d_chunks, d_out, h_out_offsets, stream ? static_cast<hipStream_t>(stream) : st->ctx->stream, StreamEmit(), d_acts,
+                    reuse, ids, lens, io, h_src_offsets);
     if (rc) return rc;
     stream_commit(st, ids, lens, n, false);
     stream_vad_commit(st, ids, pl, n);
@@ -793,21 +815,23 @@ uint64_t melspec_stream_vad_frames(const melspec_stream *st, uint32_t id) {
     return st->vad_count[id];
 }
 
-static int stream_push_host_impl(melspec_stream *st, const uint32_t *ids, const float *samples, const uint32_t *lens, uint32_t n,
+// io (melspec_stream_push_host_io / _flush_host_io): samples holds elements of the sample type, out receives elements of the row type
+static int stream_push_host_impl(melspec_stream *st, const uint32_t *ids, const void *samples, const uint32_t *lens, uint32_t n,
                                  bool flush, void *out, size_t out_capacity, uint32_t *h_frames, const StreamEmit &emit = StreamEmit(),
-                                 melspec_vad_activity *acts = nullptr, size_t acts_capacity = 0, bool want_acts = false) {
+                                 melspec_vad_activity *acts = nullptr, size_t acts_capacity = 0, bool want_acts = false, int io = 0) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
     if (want_acts && !st->vad_on) return fail(MELSPEC_ERR_INVALID_ARG, "the detector stage is off (melspec_stream_enable_vad)");
     if (n == 0) return MELSPEC_OK;
     if (!ids || (!flush && !lens)) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
     StreamPlan fresh;
-    const bool reuse = !flush && !emit.stft && stream_cache_hit(st, ids, lens, n, st->out.p, nullptr);
+    const bool reuse = !flush && !emit.stft && stream_cache_hit(st, ids, lens, n, st->out.p, nullptr, io);
     int rc = reuse ? MELSPEC_OK : stream_plan(st, ids, lens, n, flush, fresh);
     if (rc) return rc;
     const StreamPlan &pl = reuse ? st->cache.pl : fresh;
     // elements the caller receives: floats (mel rows) or complex values (spectra)
     const uint64_t need = pl.total_frames * (emit.stft ? melspec_stft_bins(st->ctx, emit.full) : static_cast<uint64_t>(st->ctx->n_mels));
-    const size_t esz = emit.stft ? (emit.dtype == MELSPEC_STFT_F64 ? 16 : 8) : sizeof(float);
+    const size_t esz = emit.stft ? (emit.dtype == MELSPEC_STFT_F64 ? 16 : 8) : (io >> 4) == MELSPEC_OUT_F32 ? sizeof(float) : 2;
+    const size_t ssz = (io & 15) == MELSPEC_PCM_S16 ? sizeof(io_s16) : sizeof(float);
     if (need > out_capacity) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
     if (need && !out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
     if (want_acts && pl.total_frames > acts_capacity) return fail(MELSPEC_ERR_CAPACITY, "activity buffer too small");
@@ -817,14 +841,14 @@ static int stream_push_host_impl(melspec_stream *st, const uint32_t *ids, const 
     if (total && !samples) return fail(MELSPEC_ERR_INVALID_ARG, "samples is NULL");
     hipStream_t s = st->ctx->stream;
     HIP_TRY(hipSetDevice(st->ctx->dev.device));
-    if ((rc = st->staging.ensure(total * sizeof(float) + 16))) return rc;
+    if ((rc = st->staging.ensure(total * ssz + 16))) return rc;
     if ((rc = st->out.ensure(need * esz + 16))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(st->staging.p, samples, total * sizeof(float), hipMemcpyHostToDevice, s));
+    if (total) HIP_TRY(hipMemcpyAsync(st->staging.p, samples, total * ssz, hipMemcpyHostToDevice, s));
     if (st->vad_on && pl.total_frames && (rc = st->vad_acts.ensure(pl.total_frames * sizeof(melspec_vad_activity)))) return rc;
     // (st->out may have been re-allocated by the ensure above: the cache is keyed on its address, a stale one simply misses next time)
-    rc = stream_run(st, pl, n, total ? static_cast<const float *>(st->staging.p) : nullptr, st->out.p, nullptr, s, emit,
+    rc = stream_run(st, pl, n, total ? st->staging.p : nullptr, st->out.p, nullptr, s, emit,
                     static_cast<melspec_vad_activity *>(st->vad_acts.p), reuse && st->cache.d_out == st->out.p, flush || emit.stft ? nullptr : ids,
-                    flush || emit.stft ? nullptr : lens);
+                    flush || emit.stft ? nullptr : lens, io);
     if (rc) return rc;
     if (need) {
         HIP_TRY(hipMemcpyAsync(out, st->out.p, need * esz, hipMemcpyDeviceToHost, s));
@@ -862,6 +886,63 @@ int melspec_stream_push_host_vad(melspec_stream *st, const uint32_t *ids, const 
 int melspec_stream_flush_host_vad(melspec_stream *st, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats,
                                   uint32_t *h_frames, melspec_vad_activity *acts, size_t acts_capacity) {
     return stream_push_host_impl(st, ids, nullptr, nullptr, n, true, out, out_capacity_floats, h_frames, StreamEmit(), acts, acts_capacity, true);
+}
+
+// ---- int16 PCM chunks in / f16, bf16 rows out -------------------------------------------------------------------------------------
+// The state stays f32: int16 samples are converted where the chunk is scattered into it (stream_scatter_kernel<io_s16>), so every
+// geometry takes them; 16-bit rows are the six-frame n_fft = 400 kernels' typed stores (launch_ctx with the out half of the code).
+// 0: go on (io = pcm_dtype | out_dtype << 4); otherwise the status to return.  Nothing is queued and the bank is untouched on a refusal.
+static int stream_io_args(const melspec_stream *st, int pcm_dtype, int out_dtype, int &io) {
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
+    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
+        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    if (out_dtype == MELSPEC_OUT_F32) return MELSPEC_OK;
+    const melspec_ctx *c = st->ctx;
+    if (!ctx_supports_io(c)) {
+        g_last_error = "f16, bf16 rows are computed by the n_fft = 400 contexts with Whisper's 80- or 128-mel bank only; this bank's context is n_fft = " +
+                       std::to_string(c->fft_size) + ", hop = " + std::to_string(c->hop_size) + ", n_mels = " + std::to_string(c->n_mels) +
+                       (c->fast ? " (another filterbank)" : "");
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    if (st->vad_on) return fail(MELSPEC_ERR_UNSUPPORTED, "the detector stage is on: it reads f32 rows (out_dtype must be MELSPEC_OUT_F32)");
+    return MELSPEC_OK;
+}
+
+int melspec_stream_supports_io(const melspec_stream *st, int pcm_dtype, int out_dtype) {
+    if (!st || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
+    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    return out_dtype == MELSPEC_OUT_F32 || ctx_supports_io(st->ctx) ? 1 : 0;
+}
+
+int melspec_stream_push_host_io(melspec_stream *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                void *out, int out_dtype, size_t out_capacity_elems, uint32_t *h_frames) {
+    int io, rc = stream_io_args(st, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_stream_push_host(st, ids, static_cast<const float *>(samples), lens, n, static_cast<float *>(out), out_capacity_elems, h_frames);
+    return stream_push_host_impl(st, ids, samples, lens, n, false, out, out_capacity_elems, h_frames, StreamEmit(), nullptr, 0, false, io);
+}
+
+int melspec_stream_flush_host_io(melspec_stream *st, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems,
+                                 uint32_t *h_frames) {
+    int io, rc = stream_io_args(st, MELSPEC_PCM_F32, out_dtype, io);
+    if (rc) return rc;
+    if (!io) return melspec_stream_flush_host(st, ids, n, static_cast<float *>(out), out_capacity_elems, h_frames);
+    return stream_push_host_impl(st, ids, nullptr, nullptr, n, true, out, out_capacity_elems, h_frames, StreamEmit(), nullptr, 0, false, io);
+}
+
+int melspec_stream_push_device_io(melspec_stream *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                  const uint32_t *lens, uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets,
+                                  uint32_t *h_frames, void *stream) {
+    int io, rc = stream_io_args(st, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
+        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
+    if (!io && !d_chunks) return melspec_stream_push_device(st, ids, lens, n, static_cast<float *>(d_out), h_out_offsets, h_frames, stream);
+    if ((reinterpret_cast<uintptr_t>(d_chunks) & (pcm_dtype == MELSPEC_PCM_S16 ? 1 : 3)) || (reinterpret_cast<uintptr_t>(d_out) & (out_dtype == MELSPEC_OUT_F32 ? 3 : 1)))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    return stream_push_device_impl(st, ids, lens, n, d_out, h_out_offsets, h_frames, nullptr, false, stream, io, d_chunks, h_src_offsets);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #include "kernels_common.hpp"
 #include "stream_plan.hpp"
 #include "pow2_wave.hpp"
+#include "io_types.hpp"
 
 namespace melspec {
 
@@ -12,13 +13,21 @@ namespace melspec {
 // [the next chunk, always at in_off].  The carry is the reference's hop_buf history (n_fft - hop samples)
 // plus the samples RingBuffer has accumulated towards the next hop (< hop).  Frames are computed in place
 // by the batch kernels on carry ++ chunk; afterwards the tail of that span becomes the new carry.
-// copies host-pushed chunks (one flat staging buffer) into the slots; optionally zero-pads (flush)
+// copies pushed chunks (one flat buffer: the host pushes' staging, or a device producer's own) into the slots; optionally zero-pads (flush)
+// S = float, or io_s16 (MELSPEC_PCM_S16): the sample's value is int16 * 2^-15, exact in f32, converted here so that the state -- carry,
+// history, every later frame -- holds the bits the f32 push of the converted chunk leaves.  src_off counts elements of S; chunks lie back
+// to back with odd lengths and device callers pass odd offsets, so an int16 chunk may start at any element: one element per lane and
+// load, nothing wider than S is ever read (the 256 lanes' 2-byte loads still coalesce into whole lines).
+MS_HD float stream_sample(float v) { return v; }
+MS_HD float stream_sample(io_s16 v) { return static_cast<float>(v) * 0x1p-15f; }
+
+template <class S>
 __global__ __launch_bounds__(256) void stream_scatter_kernel(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *entries,
-                                                             const float *src) {
+                                                             const S *src) {
     const StreamEntry e = entries[blockIdx.x];
     float *dst = state + e.stream * stride + in_off;
     if (src)
-        for (uint32_t i = threadIdx.x; i < e.len; i += 256) dst[i] = src[e.src_off + i];
+        for (uint32_t i = threadIdx.x; i < e.len; i += 256) dst[i] = stream_sample(src[e.src_off + i]);
     for (uint32_t i = threadIdx.x; i < e.zero_fill; i += 256) dst[e.len + i] = 0.0f;
 }
 

@@ -116,6 +116,15 @@ unsafe extern "C" {
                                     out_capacity_floats: usize, frames_out: *mut u32, acts: *mut VadActivityC, acts_capacity: usize) -> c_int;
     fn melspec_stream_push_host(st: *mut Stream, ids: *const u32, samples: *const f32, lens: *const u32, n: u32,
                                 out: *mut f32, cap: usize, frames_out: *mut u32) -> c_int;
+    // the pushes with 16-bit ends: int16 PCM chunks in, f16 / bf16 rows out
+    fn melspec_stream_supports_io(st: *const Stream, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_stream_push_host_io(st: *mut Stream, ids: *const u32, samples: *const c_void, pcm_dtype: c_int, lens: *const u32, n: u32,
+                                   out: *mut c_void, out_dtype: c_int, out_capacity_elems: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_stream_flush_host_io(st: *mut Stream, ids: *const u32, n: u32, out: *mut c_void, out_dtype: c_int, out_capacity_elems: usize,
+                                    frames_out: *mut u32) -> c_int;
+    fn melspec_stream_push_device_io(st: *mut Stream, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
+                                     lens: *const u32, n: u32, d_out: *mut c_void, out_dtype: c_int, out_offsets: *const u64,
+                                     frames_out: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 #[repr(C)]
@@ -483,6 +492,46 @@ impl<'a> HipStream<'a> {
     }
 }
 impl HipStream<'_> {
+    /// Which (sample, row) type pairs the `_io` pushes take (`PCM_*`, `OUT_*`): int16 chunks always, f16 / bf16 rows on the n_fft = 400
+    /// contexts with Whisper's 80- or 128-mel bank.
+    pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_stream_supports_io(self.st, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+    /// `add_frame` on 16-bit PCM (value = sample / 32768, exactly) into rows of `out_dtype` (`OUT_F16` / `OUT_BF16`), returned as their
+    /// bit patterns: the int16 bytes are what crosses the bus.
+    pub fn add_frame_s16(&mut self, samples: &[i16], out_dtype: i32) -> Result<Vec<Vec<u16>>, HipError> {
+        let (id, len) = (0u32, samples.len() as u32);
+        let cap = unsafe { melspec_stream_frames_after(self.st, 0, len) } * self.n_mels;
+        let mut flat = vec![0u16; cap];
+        let mut frames = 0u32;
+        check(unsafe {
+            melspec_stream_push_host_io(self.st, &id, samples.as_ptr() as *const c_void, PCM_S16, &len, 1, flat.as_mut_ptr() as *mut c_void,
+                                        out_dtype as c_int, cap, &mut frames)
+        })?;
+        Ok(flat.chunks(self.n_mels).take(frames as usize).map(|c| c.to_vec()).collect())
+    }
+    /// The pending (< hop) samples zero-padded to a hop: at most one more row, as `out_dtype` (`OUT_F16` / `OUT_BF16`) bit patterns.
+    pub fn flush_io(&mut self, out_dtype: i32) -> Result<Vec<Vec<u16>>, HipError> {
+        let id = 0u32;
+        let mut flat = vec![0u16; self.n_mels];
+        let mut frames = 0u32;
+        check(unsafe { melspec_stream_flush_host_io(self.st, &id, 1, flat.as_mut_ptr() as *mut c_void, out_dtype as c_int, flat.len(), &mut frames) })?;
+        Ok(flat.chunks(self.n_mels).take(frames as usize).map(|c| c.to_vec()).collect())
+    }
+    /// A chunk of `len` elements of `pcm_dtype` in device memory (null: f32 already at the stream's input slot) into rows of `out_dtype`
+    /// at `d_out`; returns the frames emitted, after the launches have completed.
+    ///
+    /// # Safety
+    /// `d_chunk` must hold `len` elements of `pcm_dtype` on the device and `d_out` room for the rows the push emits, both aligned to
+    /// their element type.
+    pub unsafe fn push_device_io(&mut self, d_chunk: *const c_void, pcm_dtype: i32, len: u32, d_out: *mut c_void, out_dtype: i32,
+                                 stream: *mut c_void) -> Result<u32, HipError> {
+        let id = 0u32;
+        let mut frames = 0u32;
+        check(melspec_stream_push_device_io(self.st, &id, d_chunk, pcm_dtype as c_int, std::ptr::null(), &len, 1, d_out, out_dtype as c_int,
+                                            std::ptr::null(), &mut frames, stream))?;
+        Ok(frames)
+    }
     /// Turns the detector stage on: from now on `add_frame_activity` also returns what
     /// `VoiceActivityDetector::add_activity` (src/vad.rs:155-205) gives for every frame, computed on the device from the rows
     /// the push has just written.

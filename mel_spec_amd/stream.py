@@ -8,7 +8,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from ._lib import lib
-from .hip import HipMelSpectrogram, _check, _f32, _fp
+from .hip import PCM_F32, PCM_S16, _OUT_NUMPY, HipMelSpectrogram, _check, _f32, _fp, _out_code
 from .vad import DetectionSettings, VadFrameTiming, VoiceActivity
 
 # melspec_vad_activity (include/melspec_hip.h): one 8-byte record per emitted frame
@@ -96,6 +96,44 @@ class StreamBank:
         _check(lib().melspec_stream_flush_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
         return self._collect(out, frames)
 
+    # ---- int16 PCM chunks in, f16 / bf16 rows out (melspec_stream_*_io) ----
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(lib().melspec_stream_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def push_io(self, ids: Sequence[int], chunks: Sequence, out_dtype=None) -> List[np.ndarray]:
+        """push() with typed ends: np.int16 chunks are 16-bit PCM (value = sample / 32768, exactly) and cross the bus as such -- all
+        chunks of one call have the same dtype; out_dtype "f16" (or np.float16) returns np.float16 rows, "bf16" the bfloat16 bit
+        patterns as np.uint16 (numpy has no bfloat16): the f32 rows of push() rounded to nearest even."""
+        a = _u32(ids)
+        arrs = [np.asarray(c) for c in chunks]
+        assert len(arrs) == a.shape[0]
+        s16 = [x.dtype == np.int16 for x in arrs]
+        if any(s16) and not all(s16):
+            raise ValueError("all chunks of one push must have the same dtype (np.int16, or float)")
+        pcm = PCM_S16 if arrs and all(s16) else PCM_F32
+        xs = [np.ascontiguousarray(x).ravel() if pcm == PCM_S16 else _f32(x).ravel() for x in arrs]
+        out_code = _out_code(out_dtype)
+        lens = _u32([x.shape[0] for x in xs])
+        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
+        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        out = np.empty((cap, self.n_mels), _OUT_NUMPY[out_code])
+        frames = np.zeros(a.shape[0], np.uint32)
+        _check(lib().melspec_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm,
+                                                 lens.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size,
+                                                 frames.ctypes.data_as(_u32p)))
+        assert int(frames.sum()) == cap
+        return self._collect(out, frames)
+
+    def flush_io(self, ids: Sequence[int], out_dtype) -> List[np.ndarray]:
+        """flush() whose rows have the type of push_io's out_dtype"""
+        a = _u32(ids)
+        out_code = _out_code(out_dtype)
+        out = np.empty((a.shape[0], self.n_mels), _OUT_NUMPY[out_code])
+        frames = np.zeros(a.shape[0], np.uint32)
+        _check(lib().melspec_stream_flush_host_io(self._h, a.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code,
+                                                  out.size, frames.ctypes.data_as(_u32p)))
+        return self._collect(out, frames)
+
     # ---- the detector stage: VoiceActivityDetector::add_activity per stream, inside the push (src/vad.rs:155-205) ----
     def enable_vad(self, settings: Optional[DetectionSettings], timing: Optional[VadFrameTiming] = None) -> None:
         """Every push / flush from now on also feeds each stream's detector on the device; None turns the stage off.
@@ -166,6 +204,22 @@ class StreamBank:
         _check(lib().melspec_stream_push_device(self._h, a.ctypes.data_as(_u32p), ln.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_out),
                                                 None if oo is None else oo.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                 frames.ctypes.data_as(_u32p), C.c_void_p(stream)))
+        return frames
+
+    def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
+                       src_offsets=None, out_offsets=None, stream: int = 0) -> np.ndarray:
+        """push_device with typed ends.  d_chunks != 0: chunk i is lens[i] elements of pcm_dtype (PCM_F32 / PCM_S16) at d_chunks +
+        src_offsets[i] elements (None: back to back), anywhere in device memory; d_chunks == 0: the chunks are at input_ptr, in f32.
+        Rows of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back)."""
+        a, ln = _u32(ids), _u32(lens)
+        frames = np.zeros(a.shape[0], np.uint32)
+        u64p = C.POINTER(C.c_uint64)
+        so = None if src_offsets is None else np.ascontiguousarray(src_offsets, np.uint64)
+        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
+        _check(lib().melspec_stream_push_device_io(self._h, a.ctypes.data_as(_u32p), C.c_void_p(d_chunks or None), int(pcm_dtype),
+                                                   None if so is None else so.ctypes.data_as(u64p), ln.ctypes.data_as(_u32p), a.shape[0],
+                                                   C.c_void_p(d_out or None), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p),
+                                                   frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
         return frames
 
     def push_device_vad(self, ids: Sequence[int], lens: Sequence[int], d_out: int, d_acts: int, out_offsets=None, stream: int = 0) -> np.ndarray:
