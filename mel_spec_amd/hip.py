@@ -946,6 +946,29 @@ class SparseMelFilterbank:
         _check(lib().melspec_bank_norm_mel_host(self._h, a.ctypes.data_as(C.c_void_p), f64, a.size, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # ---- device API: pointers in, pointers out, asynchronous on `stream` (None: the bank's own) ---------------------------------
+    @staticmethod
+    def _code(dtype) -> int:
+        """MELSPEC_STFT_F32 / MELSPEC_STFT_F64 for the element type of the arrays (a complex dtype names its component type)"""
+        dt = np.dtype(dtype)
+        if dt in (np.dtype(np.float32), np.dtype(np.complex64)):
+            return 0
+        if dt in (np.dtype(np.float64), np.dtype(np.complex128)):
+            return 1
+        raise ValueError(f"dtype must be float32 / float64 (complex64 / complex128), not {dt}")
+
+    def project_power_device(self, d_power: int, dtype, n_frames: int, d_out: int, stream: int = None) -> None:
+        """melspec_bank_project_power_device: power [n_frames][fft_bins] -> [n_frames][n_mels], both of `dtype`"""
+        _check(lib().melspec_bank_project_power_device(self._h, C.c_void_p(d_power), self._code(dtype), n_frames, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def log_mel_device(self, d_stft: int, dtype, n_fft: int, n_frames: int, d_out: int, stream: int = None) -> None:
+        """melspec_bank_log_mel_device: complex frames [n_frames][n_fft] of `dtype` components -> [n_frames][n_mels] f64"""
+        _check(lib().melspec_bank_log_mel_device(self._h, C.c_void_p(d_stft), self._code(dtype), n_fft, n_frames, C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def norm_mel_device(self, d_in: int, dtype, n_values: int, d_out: int, stream: int = None) -> None:
+        """melspec_bank_norm_mel_device: one maximum over the n_values of `dtype` at d_in, the normalised values to d_out"""
+        _check(lib().melspec_bank_norm_mel_device(self._h, C.c_void_p(d_in), self._code(dtype), n_values, C.c_void_p(d_out), C.c_void_p(stream)))
+
     def close(self) -> None:
         if self._h is not None:
             lib().melspec_bank_destroy(self._h)

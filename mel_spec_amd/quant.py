@@ -117,6 +117,15 @@ class TgaCodec:
         _check(lib().melspec_tga_decode_device(self._h, C.c_void_p(d_blobs), blob_stride, n_mels, width, n_images,
                                                C.c_void_p(d_images), image_stride, C.c_void_p(stream)))
 
+    def quantize_device(self, d_frame: int, n: int, d_out: int, d_range: int, stream: int = None) -> None:
+        """melspec_quantize_device: n floats at d_frame -> n bytes at d_out (room for n rounded up to a multiple of 4) and
+        {min, max} as two floats at d_range.  Asynchronous on `stream` (None: the codec's)."""
+        _check(lib().melspec_quantize_device(self._h, C.c_void_p(d_frame), n, C.c_void_p(d_out), C.c_void_p(d_range), C.c_void_p(stream)))
+
+    def dequantize_device(self, d_data: int, n: int, d_range: int, d_out: int, stream: int = None) -> None:
+        """melspec_dequantize_device: n bytes at d_data and the {min, max} at d_range -> n floats at d_out."""
+        _check(lib().melspec_dequantize_device(self._h, C.c_void_p(d_data), n, C.c_void_p(d_range), C.c_void_p(d_out), C.c_void_p(stream)))
+
     def synchronize(self) -> None:
         _check(lib().melspec_tga_synchronize(self._h))
 

@@ -56,6 +56,22 @@ def vad_boundaries(frames: Sequence, settings: DetectionSettings, device: int = 
     return EdgeInfo(sm.astype(bool), raw.astype(bool), run.value)
 
 
+def vad_mask_len(n_mels: int, width: int) -> int:
+    """width - 2, or 0 when n_mels < 3 or width < 3 (melspec_vad_mask_len)."""
+    return int(lib().melspec_vad_mask_len(int(n_mels), int(width)))
+
+
+def vad_boundaries_device(d_images: int, image_stride: int, n_mels: int, width: int, n_images: int, settings: DetectionSettings,
+                          d_raw: int, d_smoothed: int, mask_stride: int, d_longest_run: Optional[int] = None,
+                          stream: Optional[int] = None) -> None:
+    """melspec_vad_boundaries_device: n_images [n_mels][width] f32 images at d_images + i * image_stride floats -> byte masks at
+    d_raw / d_smoothed + i * mask_stride (vad_mask_len entries each) and, if d_longest_run is given, one u32 run length per image.
+    Asynchronous on `stream` (None: the null stream) of the current device."""
+    s = settings._c()
+    _check(lib().melspec_vad_boundaries_device(C.c_void_p(d_images), image_stride, n_mels, width, n_images, C.byref(s), C.c_void_p(d_raw),
+                                               C.c_void_p(d_smoothed), mask_stride, C.c_void_p(d_longest_run), C.c_void_p(stream)))
+
+
 def vad_on(edge_info: EdgeInfo, n: int) -> bool:
     """vad_on (src/vad.rs:229-254): the counter is only tested from the second intersected column on."""
     if n <= 1:

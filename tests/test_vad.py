@@ -15,6 +15,9 @@ import pytest
 from conftest import GOLDEN, ROOT
 
 REF_SETTINGS = dict(min_energy=1.0, min_y=10, min_x=10, min_mel=0)      # src/vad.rs:624-629
+# N(0, 1) images of 80 rows and more have an all-ones raw mask under the small thresholds below; these two leave a quarter to a half
+# of the columns set at 80 rows (tests/test_aux_whole_batch.py measures the shares), so the Sobel count decides
+MIXED_SETTINGS = (dict(min_energy=6.0, min_y=20, min_mel=0), dict(min_energy=7.0, min_y=12, min_mel=2))
 
 
 def fixtures(oracle):
@@ -77,7 +80,7 @@ def test_emulated_kernels_match_oracle_masks(vemu, oracle):
     rng = np.random.default_rng(5)
     for shape in ((3, 3), (3, 9), (80, 3), (128, 700), (5, 1000)):
         img = rng.standard_normal(shape).astype(np.float32)
-        for kw in (dict(min_energy=2.0, min_y=1, min_mel=0), dict(min_energy=1.0, min_y=2, min_mel=1)):
+        for kw in (dict(min_energy=2.0, min_y=1, min_mel=0), dict(min_energy=1.0, min_y=2, min_mel=1)) + MIXED_SETTINGS:
             r0, s0 = oracle.vad_boundaries(img, **kw)
             r1, s1 = vemu(img, **kw)
             assert np.array_equal(r0, r1) and np.array_equal(s0, s1), (shape, kw)
@@ -102,10 +105,11 @@ def test_gpu_masks_on_random_images_and_edges(gpu, oracle):
     rng = np.random.default_rng(5)
     for shape in ((3, 3), (3, 9), (80, 3), (128, 700), (5, 1000), (80, 3000)):
         img = rng.standard_normal(shape).astype(np.float32)
-        for kw in (dict(min_energy=2.0, min_y=1, min_mel=0), dict(min_energy=1.0, min_y=2, min_mel=1), dict(min_y=0)):
+        for kw in (dict(min_energy=2.0, min_y=1, min_mel=0), dict(min_energy=1.0, min_y=2, min_mel=1), dict(min_y=0)) + MIXED_SETTINGS:
             e = gpu.vad_boundaries([img[:, :shape[1] // 2], img[:, shape[1] // 2:]], gpu.DetectionSettings(**kw))   # frames are concatenated
             raw, sm = oracle.vad_boundaries(img, **{"min_energy": 0.98, "min_y": 11, "min_mel": 2, **kw})
             assert np.array_equal(e.raw, raw) and np.array_equal(e.smoothed, sm), (shape, kw)
+            assert e.longest_run == max(len(r) for r in "".join("1" if b else "0" for b in sm).split("0")), (shape, kw)
             for n in (1, 2, 5, 40):
                 assert gpu.vad_on(e, n) == oracle.vad_on(sm, n)
     assert gpu.vad_boundaries([np.zeros((2, 50), np.float32)], gpu.DetectionSettings()).smoothed.shape == (0,)
