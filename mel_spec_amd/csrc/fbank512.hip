@@ -169,6 +169,33 @@ int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream)
 }  // namespace host
 }  // namespace melspec
 
+namespace {
+// ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io, melspec_fbank_compute_*_io): what the two objects share ----
+inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
+inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
+inline bool io_pcm_known(int t) { return t == MELSPEC_PCM_F32 || t == MELSPEC_PCM_S16; }
+inline bool io_out_known(int t) { return t == MELSPEC_OUT_F32 || t == MELSPEC_OUT_F16 || t == MELSPEC_OUT_BF16; }
+// 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
+int io_dtypes(int pcm_dtype, int out_dtype, int &io) {
+    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (!io_out_known(out_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    return MELSPEC_OK;
+}
+bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
+    return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
+}
+// the LDS attribute of the kernels of a pass, once per device
+template <class... K>
+int allow_big_lds_once(std::atomic<uint64_t> &done, const char *name, K... kernels) {
+    if (device_done(done)) return MELSPEC_OK;
+    int rc = MELSPEC_OK;
+    ((rc = rc ? rc : allow_big_lds(kernels, name)), ...);
+    if (!rc) mark_device_done(done);
+    return rc;
+}
+}  // namespace
+
 // ------------------------------------------------------------------------------------
 // Kaldi fbank context
 // ------------------------------------------------------------------------------------
@@ -188,9 +215,8 @@ struct melspec_fbank {
     int waves = 4;
     GenericTables gt;
     DevBuf h2d, d2h;
-    DevBuf rows32;              // apply_cmn with f16 / bf16 rows out: the f32 rows between the fbank kernel and the CMN, then the caller's
-    hipStream_t rows32_stream = nullptr;    //   output offsets of a ragged batch (frames * num_mel_bins * 4 + n_clips * 8 bytes; grow-only,
-    bool rows32_used = false;               //   used in stream order: a call on another stream first waits for the stream that used it last)
+    StreamBuf rows32;           // apply_cmn with f16 / bf16 rows out: the f32 rows between the fbank kernel and the CMN, then the caller's
+                                //   output offsets of a ragged batch (frames * num_mel_bins * 4 + n_clips * 8 bytes)
 };
 
 
@@ -309,22 +335,27 @@ static void cmn_shape(int nm, uint64_t fpc /* frames of the longest clip */, int
                  : (static_cast<size_t>((nm + 3) & ~3) + 8 * 512 + 512) * sizeof(float);
 }
 
-// the CMN pass of a batch, in place on the f32 rows (d_means: the split output, see fbank_launch): walks clips, not units
-static int fbank_cmn(melspec_fbank *fb, const BatchDesc &desc, uint32_t n_clips, uint64_t fpc, hipStream_t s, float *d_means) {
+// The CMN pass of a batch (walks clips, not units) on the f32 rows of desc.out: in place (d_means: the split output, see fbank_launch) or --
+// out_dtype f16 / bf16, the rows being a scratch -- from there to the caller's rows at dst (ragged batches: clip c at d_dst_off[c]).
+static int launch_cmn(melspec_fbank *fb, const BatchDesc &desc, uint32_t n_clips, uint64_t fpc, hipStream_t s, float *d_means,
+                      void *dst = nullptr, int out_dtype = MELSPEC_OUT_F32, const uint64_t *d_dst_off = nullptr) {
     const int nm = fb->cfg.num_mel_bins;
-    CmnParams cp{};
-    cp.b = desc;
-    cp.n_mels = nm;
+    int rows_per_chunk;
     size_t lds;
-    cmn_shape(nm, fpc, cp.rows_per_chunk, lds);
-    cp.d_means = d_means;
-    static std::atomic<uint64_t> cmn_attr{0};
-    if (!device_done(cmn_attr)) {
-        if (int rc = allow_big_lds(&cmn_kernel<512>, "hipFuncSetAttribute(cmn_kernel)")) return rc;
-        mark_device_done(cmn_attr);
-    }
+    cmn_shape(nm, fpc, rows_per_chunk, lds);
     const unsigned grid = grid_for(n_clips, fb->dev.cus, 8);
-    hipLaunchKernelGGL(cmn_kernel<512>, dim3(grid), dim3(512), lds, s, cp);
+    static std::atomic<uint64_t> attr_done[2];
+    if (out_dtype == MELSPEC_OUT_F32) {
+        CmnParams cp{};
+        cp.b = desc; cp.n_mels = nm; cp.rows_per_chunk = rows_per_chunk; cp.d_means = d_means;
+        if (int rc = allow_big_lds_once(attr_done[0], "hipFuncSetAttribute(cmn_kernel)", &cmn_kernel<512>)) return rc;
+        hipLaunchKernelGGL(cmn_kernel<512>, dim3(grid), dim3(512), lds, s, cp);
+    } else {
+        CmnIoParams cp{};
+        cp.b = desc; cp.dst = dst; cp.d_dst_off = d_dst_off; cp.n_mels = nm; cp.rows_per_chunk = rows_per_chunk;
+        if (int rc = allow_big_lds_once(attr_done[1], "hipFuncSetAttribute(cmn_io_kernel)", &cmn_io_kernel<io_f16>, &cmn_io_kernel<io_bf16>)) return rc;
+        hipLaunchKernelGGL(out_dtype == MELSPEC_OUT_F16 ? cmn_io_kernel<io_f16> : cmn_io_kernel<io_bf16>, dim3(grid), dim3(kCmnThreads), lds, s, cp);
+    }
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
 }
@@ -427,7 +458,30 @@ static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips
                             fb->cfg.preemphasis, floor_v, fb->dev.cus, s);
     }
     if (rc) return rc;
-    if (fb->cfg.apply_cmn) return fbank_cmn(fb, pl.desc, n_clips, fpc, s, d_means);
+    if (fb->cfg.apply_cmn) return launch_cmn(fb, pl.desc, n_clips, fpc, s, d_means);
+    return MELSPEC_OK;
+}
+
+// What a ragged call (io = 0: the f32 one) begins with: the checks of its arguments, every clip's frames, the device and the stream.
+// `go` is false when the call ends here, with the status returned (MELSPEC_OK: a batch without frames).
+struct FbankRagged {
+    std::vector<uint64_t> frames;
+    uint64_t total = 0, longest = 0;
+    hipStream_t s = nullptr;
+};
+static int fbank_ragged_begin(melspec_fbank *fb, const void *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
+                              const void *d_out, void *stream, int io, FbankRagged &r, bool &go) {
+    go = false;
+    if (n_clips == 0) return MELSPEC_OK;
+    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
+    r.frames.resize(n_clips);
+    for (uint32_t i = 0; i < n_clips; ++i) { r.frames[i] = fbank_frames(fb, h_lengths[i]); r.total += r.frames[i]; r.longest = std::max(r.longest, r.frames[i]); }
+    if (r.total == 0) return MELSPEC_OK;
+    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && io_misaligned(d_pcm, d_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    r.s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    go = true;
     return MELSPEC_OK;
 }
 
@@ -436,15 +490,13 @@ static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips
 int melspec_fbank_compute_ragged_device(melspec_fbank *fb, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                         uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    std::vector<uint64_t> frames(n_clips);
-    uint64_t total = 0, longest = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) { frames[i] = fbank_frames(fb, h_lengths[i]); total += frames[i]; longest = std::max(longest, frames[i]); }
-    if (total == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    FbankRagged r;
+    bool go;
+    int rc = fbank_ragged_begin(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, stream, 0, r, go);
+    if (!go) return rc;
+    const std::vector<uint64_t> &frames = r.frames;
+    const uint64_t total = r.total, longest = r.longest;
+    hipStream_t s = r.s;
     const bool fused = fb->fast && !fb->use_generic;
     BatchPlan pl;
     RaggedSlot *slot = nullptr;
@@ -455,7 +507,7 @@ int melspec_fbank_compute_ragged_device(melspec_fbank *fb, const float *d_pcm, c
                    n_clips >= 2u * static_cast<uint32_t>(fb->dev.cus) && longest * 2 * static_cast<uint64_t>(fb->dev.cus) <= total && longest < (1ull << 31);
     if (by_clip && h_out_offsets)
         for (uint32_t i = 0; i < n_clips && by_clip; ++i) by_clip = h_out_offsets[i] % 4 == 0;
-    int rc = plan_ragged(fb->ragged, s, d_pcm, d_out, h_offsets, frames, h_out_offsets, n_clips, nm, fused ? kFbFPW : 1, pl, slot, by_clip);
+    rc = plan_ragged(fb->ragged, s, d_pcm, d_out, h_offsets, frames, h_out_offsets, n_clips, nm, fused ? kFbFPW : 1, pl, slot, by_clip);
     if (!rc) rc = fbank_launch(fb, pl, n_clips, longest, s);
     plan_ragged_done(slot, s);
     return rc;
@@ -483,9 +535,8 @@ int melspec_fbank_release_scratch(melspec_fbank *fb) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     HIP_TRY(hipSetDevice(fb->dev.device));
     HIP_TRY(hipStreamSynchronize(fb->stream));
-    if (fb->rows32_used && fb->rows32_stream != fb->stream) HIP_TRY(hipStreamSynchronize(fb->rows32_stream));
-    fb->pipe.release(); fb->ragged.release(); fb->dplan.release(); fb->h2d.release(); fb->d2h.release(); fb->rows32.release();
-    fb->rows32_used = false;
+    if (int rc = fb->rows32.release_after(fb->stream)) return rc;
+    fb->pipe.release(); fb->ragged.release(); fb->dplan.release(); fb->h2d.release(); fb->d2h.release();
     return MELSPEC_OK;
 }
 
@@ -493,29 +544,6 @@ int melspec_fbank_synchronize(melspec_fbank *fb, void *stream) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     HIP_TRY(hipSetDevice(fb->dev.device));
     HIP_TRY(hipStreamSynchronize(stream ? static_cast<hipStream_t>(stream) : fb->stream));
-    return MELSPEC_OK;
-}
-
-int melspec_fbank_compute_host(melspec_fbank *fb, const float *samples, size_t n_samples, float *out,
-                               size_t out_capacity_floats, size_t *n_frames) {
-    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    if (n_frames) *n_frames = 0;
-    const uint64_t frames = fbank_frames(fb, n_samples);
-    if (frames == 0) return MELSPEC_OK;
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    const uint64_t need = frames * static_cast<uint64_t>(fb->cfg.num_mel_bins);
-    if (out_capacity_floats < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    int rc;
-    if ((rc = fb->h2d.ensure(n_samples * sizeof(float)))) return rc;
-    if ((rc = fb->d2h.ensure(need * sizeof(float)))) return rc;
-    HIP_TRY(hipMemcpyAsync(fb->h2d.p, samples, n_samples * sizeof(float), hipMemcpyHostToDevice, fb->stream));
-    rc = melspec_fbank_compute_uniform_device(fb, static_cast<const float *>(fb->h2d.p), n_samples, n_samples, 1,
-                                              static_cast<float *>(fb->d2h.p), fb->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, fb->d2h.p, need * sizeof(float), hipMemcpyDeviceToHost, fb->stream));
-    HIP_TRY(hipStreamSynchronize(fb->stream));
-    if (n_frames) *n_frames = static_cast<size_t>(frames);
     return MELSPEC_OK;
 }
 
@@ -564,9 +592,7 @@ struct melspec_blm {
     bool fast = false;          // fused 512-point kernel (n_fft 512 / win_length 400) vs the generic f64 kernel (any validated config)
     GenericTables gt;
     RaggedScratch ragged;
-    DevBuf aux;                 // ragged batches: per-clip sample counts and valid frames, the normaliser's group counter; used in
-    hipStream_t aux_stream = nullptr;   //   stream order (a call on another stream first waits for the stream that used it last)
-    bool aux_used = false;
+    StreamBuf aux;              // ragged batches: per-clip sample counts and valid frames, the normaliser's group counter
     FbankFastTables ft;
     DevBuf d_blob;
     size_t fast_lds = 0;
@@ -575,9 +601,8 @@ struct melspec_blm {
     Fused512F32 f32;            // MELSPEC_PRECISION_F32: the reference's own arithmetic type for this frontend (src/mel.rs:251-252,356-357)
     DevBuf h2d, d2h;
     HostPipe pipe;              // melspec_blm_compute_batch_host
-    DevBuf rows32;              // normalize_per_feature with f16 / bf16 rows out: the f32 rows between the mel kernel and the normaliser
-    hipStream_t rows32_stream = nullptr;    //   (n_clips * n_mels * cols * 4 bytes; grow-only, used in stream order like aux)
-    bool rows32_used = false;
+    StreamBuf rows32;           // normalize_per_feature with f16 / bf16 rows out: the f32 rows between the mel kernel and the normaliser
+                                //   (n_clips * n_mels * cols * 4 bytes)
 };
 
 namespace {
@@ -595,15 +620,10 @@ uint64_t blm_padded(const melspec_blm *b, uint64_t frames) {         // pad_len,
 // ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io) ---------------------------------------------------------------------
 // the contexts whose kernels have the instantiations: the fused geometry on eight f64 waves with one of the compile-time Slaney banks
 bool blm_io_ok(const melspec_blm *b) { return b->fast && b->waves == 8 && nemo_f32_bank(b->ft.slots); }
-inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
-inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
 // 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
 int blm_io_args(const melspec_blm *b, int pcm_dtype, int out_dtype, int &io) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
-    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
-        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
-    io = pcm_dtype | out_dtype << 4;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     if (io && !blm_io_ok(b)) {
         g_last_error = "int16 PCM / f16, bf16 rows are computed by the n_fft = 512 / win_length = 400 frontend with the 80- or 128-mel Slaney bank only; this context is n_fft = " +
                        std::to_string(b->cfg.n_fft) + ", win_length = " + std::to_string(b->cfg.win_length) + ", n_mels = " + std::to_string(b->cfg.n_mels) +
@@ -657,11 +677,9 @@ int launch_nemo_io(melspec_blm *b, FbankFastParams fp, int io, hipStream_t s) {
 
 // the f32 rows of a normalised call with 16-bit rows out: `floats` of them, on stream s
 int blm_rows32(melspec_blm *b, uint64_t floats, hipStream_t s, float *&rows) {
-    if (b->rows32_used && b->rows32_stream != s) HIP_TRY(hipStreamSynchronize(b->rows32_stream));
-    b->rows32_used = true; b->rows32_stream = s;
-    // + 16: the normaliser reads whole 16-byte granules, the last row's last one included (growing frees the old buffer: hipFree waits for the device)
-    const int rc = b->rows32.ensure(static_cast<size_t>(floats) * sizeof(float) + 16);
-    rows = static_cast<float *>(b->rows32.p);
+    // + 16: the normaliser reads whole 16-byte granules, the last row's last one included
+    const int rc = b->rows32.ensure(static_cast<size_t>(floats) * sizeof(float) + 16, s);
+    rows = static_cast<float *>(b->rows32.p());
     return rc;
 }
 
@@ -695,13 +713,164 @@ void blm_norm_shape_ragged(uint64_t longest, size_t &stride, size_t &per, int &p
     if (per < 4) { per = (static_cast<size_t>(150) * 1024 - fixed) / (stride * sizeof(float)); per_cu = 1; }
     if (per > 64) per = 64;
 }
-template <class K>
-int allow_norm_io(K f16, K bf16, std::atomic<uint64_t> &done, const char *name) {
-    if (device_done(done)) return MELSPEC_OK;
-    int rc = allow_big_lds(f16, name);
-    if (!rc) rc = allow_big_lds(bf16, name);
-    if (!rc) mark_device_done(done);
-    return rc;
+
+// the fused kernels' parameters of a batch of this context (fbank_fast_params' counterpart); the caller adds what its kind of batch has
+FbankFastParams blm_fast_params(const melspec_blm *b, const BatchDesc &desc) {
+    FbankFastParams fp{};
+    fp.b = desc;
+    fp.d_blob = static_cast<const uint32_t *>(b->d_blob.p);
+    fp.blob_words = static_cast<int>(b->ft.blob.size());
+    fp.mel_off_words = b->ft.mel_off_words;
+    fp.shift = b->cfg.hop_length;
+    fp.n_mels = b->cfg.n_mels;
+    fp.preemph = b->cfg.preemphasis;
+    fp.floor_v = b->cfg.log_zero_guard;
+    fp.use_log = 1; fp.use_power = 1;
+    fp.org0 = b->cfg.center ? -200 : 56;      // tap 0 of the window sits at position (512-400)/2 of the frame
+    fp.slots = b->ft.slots;
+    return fp;
+}
+
+// the mel kernel of a batch: the (sample, row) combination io, the f32 kernel, the f64 kernel of a compile-time bank or of any bank
+int launch_nemo_mel(melspec_blm *b, const FbankFastParams &fp, int io, hipStream_t s) {
+    if (io) return launch_nemo_io(b, fp, io, s);
+    if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) return launch_nemo_f32(b->f32, fp, b->dev.cus, s);
+    if (fb_lens_match<LensSlaney128>(b->ft.slots)) return launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
+    if (fb_lens_match<LensSlaney80>(b->ft.slots)) return launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
+    return b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
+                                           : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
+}
+
+// The rows a normaliser works on: f32 rows read at src and written at dst as out_dtype -- MELSPEC_OUT_F32: in place (dst == src), f16 / bf16:
+// split, src being the context's scratch.  Ragged batches: clip c at d_src_off[c] / d_dst_off[c] (in place: the same), its row width and
+// valid frames in d_cols / d_valid.
+struct BlmNormRows {
+    const float *src;
+    void *dst;
+    int out_dtype;
+    uint32_t n_clips;
+    const uint64_t *d_src_off, *d_dst_off, *d_cols, *d_valid;
+};
+
+// rows too long for LDS: one thread per row from HBM (blm_normalize_kernel / blm_normalize_io_kernel with rows_per_group == 0); uniform
+// batches: rows of `valid` frames in `cols` columns.  The caller looks at hipGetLastError.
+void launch_blm_norm_slow(melspec_blm *b, const BlmNormRows &r, uint64_t cols, uint64_t valid, hipStream_t s) {
+    const int nm = b->cfg.n_mels;
+    const uint64_t rows = static_cast<uint64_t>(r.n_clips) * nm;
+    const dim3 grid(grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4));
+    if (r.out_dtype == MELSPEC_OUT_F32) {
+        BlmNormParams np{};
+        np.out = static_cast<float *>(r.dst); np.clip_stride = cols * static_cast<uint64_t>(nm); np.row_w = cols; np.valid = valid;
+        np.n_clips = r.n_clips; np.n_mels = nm; np.rows_per_group = 0; np.fold_sel = -1;
+        np.d_out_off = r.d_dst_off; np.d_cols = r.d_cols; np.d_valid = r.d_valid;
+        hipLaunchKernelGGL(blm_normalize_kernel, grid, dim3(kBlmNormThreads), 0, s, np);
+    } else {
+        BlmNormIoParams np{};
+        np.src = r.src; np.dst = r.dst; np.row_w = cols; np.valid = valid; np.n_clips = r.n_clips; np.n_mels = nm; np.rows_per_group = 0;
+        np.d_src_off = r.d_src_off; np.d_dst_off = r.d_dst_off; np.d_cols = r.d_cols; np.d_valid = r.d_valid;
+        hipLaunchKernelGGL(r.out_dtype == MELSPEC_OUT_F16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>, grid, dim3(kBlmNormThreads), 0, s, np);
+    }
+}
+
+// normalize_per_feature over a uniform batch: rows of `valid` frames in `cols` columns
+int launch_blm_norm(melspec_blm *b, const BlmNormRows &r, uint64_t cols, uint64_t valid, hipStream_t s) {
+    const int nm = b->cfg.n_mels;
+    const uint64_t rows = static_cast<uint64_t>(r.n_clips) * nm;
+    const bool split = r.out_dtype != MELSPEC_OUT_F32;
+    size_t stride, per;
+    int per_cu;
+    blm_norm_shape_uniform(valid, stride, per, per_cu);
+    static std::atomic<uint64_t> attr_done[2];
+    if (int rc = split ? allow_big_lds_once(attr_done[1], "hipFuncSetAttribute(blm_normalize_io_kernel)", &blm_normalize_io_kernel<io_f16>, &blm_normalize_io_kernel<io_bf16>)
+                       : allow_big_lds_once(attr_done[0], "hipFuncSetAttribute(blm_normalize_kernel)", &blm_normalize_kernel))
+        return rc;
+    if (per == 0) {
+        launch_blm_norm_slow(b, r, cols, valid, s);
+        HIP_TRY(hipGetLastError());
+        return MELSPEC_OK;
+    }
+    const size_t lds = (per * stride + 2 * per + kBlmNormThreads) * sizeof(float);
+    const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
+    if (split) {
+        BlmNormIoParams np{};
+        np.src = r.src; np.dst = r.dst; np.row_w = cols; np.valid = valid; np.n_clips = r.n_clips; np.n_mels = nm;
+        np.rows_per_group = static_cast<int>(per);
+        np.lds_stride = static_cast<int>(stride);
+        hipLaunchKernelGGL(r.out_dtype == MELSPEC_OUT_F16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, np);
+        HIP_TRY(hipGetLastError());
+        return MELSPEC_OK;
+    }
+    BlmNormParams np{};
+    np.out = static_cast<float *>(r.dst); np.clip_stride = cols * static_cast<uint64_t>(nm); np.row_w = cols; np.valid = valid;
+    np.n_clips = r.n_clips; np.n_mels = nm;
+    static const int fold_sel = lab_int("MELSPEC_NORM_FOLD", -1, -1, 12);
+    np.fold_sel = fold_sel;
+    static const int norm_skip = lab_int("MELSPEC_NORM_SKIP", 0, 0, 7);
+    np.lab_skip = norm_skip;
+    np.rows_per_group = static_cast<int>(per);
+    np.lds_stride = static_cast<int>(stride);
+#ifdef MELSPEC_LAB
+    static const int norm_dbg = lab_int("MELSPEC_NORM_DBG", 0, 0, 1);
+    static uint64_t *d_dbg = nullptr;
+    static int dbg_calls = 0;
+    if (norm_dbg) {
+        if (!d_dbg) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_dbg), 64 * 8 * 8));
+        HIP_TRY(hipMemsetAsync(d_dbg, 0, 64 * 8 * 8, s));
+        np.dbg = d_dbg;
+    }
+#endif
+    hipLaunchKernelGGL(blm_normalize_kernel, dim3(g2), dim3(kBlmNormThreads), lds, s, np);
+#ifdef MELSPEC_LAB
+    if (norm_dbg && ++dbg_calls == 20) {
+        uint64_t h[64 * 8];
+        HIP_TRY(hipStreamSynchronize(s));
+        HIP_TRY(hipMemcpy(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost));
+        double sum[8] = {0};
+        for (int b = 0; b < 64; ++b) for (int k = 0; k < 8; ++k) sum[k] += static_cast<double>(h[b * 8 + k]);
+        std::fprintf(stderr, "norm phases, us per workgroup (mean of 64): load %.1f  mean %.1f  var %.1f  var-sum %.1f  store %.1f\n",
+                     sum[1] / 64 / 100, sum[2] / 64 / 100, sum[3] / 64 / 100, sum[4] / 64 / 100, sum[5] / 64 / 100);
+    }
+#endif
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+// ... over a ragged batch whose longest clip has `longest` valid frames; ctr: the group counter, zero at launch
+int launch_blm_norm_ragged(melspec_blm *b, const BlmNormRows &r, uint64_t longest, unsigned *ctr, hipStream_t s) {
+    const int nm = b->cfg.n_mels;
+    const uint64_t rows = static_cast<uint64_t>(r.n_clips) * nm;
+    const bool split = r.out_dtype != MELSPEC_OUT_F32;
+    size_t stride, per;
+    int per_cu;
+    blm_norm_shape_ragged(longest, stride, per, per_cu);      // (the split pass's rows carry two more words each: <= 512 bytes)
+    if (per < 1 || longest >= (1ull << 31)) {
+        launch_blm_norm_slow(b, r, 0, 0, s);
+        if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, split ? "blm_normalize_io_kernel launch failed" : "blm_normalize_kernel launch failed");
+        return MELSPEC_OK;
+    }
+    static std::atomic<uint64_t> attr_done[2];
+    if (int rc = split ? allow_big_lds_once(attr_done[1], "hipFuncSetAttribute(blm_normalize_ragged_io_kernel)", &blm_normalize_ragged_io_kernel<io_f16>,
+                                            &blm_normalize_ragged_io_kernel<io_bf16>)
+                       : allow_big_lds_once(attr_done[0], "hipFuncSetAttribute(blm_normalize_ragged_kernel)", &blm_normalize_ragged_kernel))
+        return rc;
+    const size_t lds = (per * stride + 2 * per + kBlmNormThreads + (split ? kBlmNormIoInfo : kBlmNormInfo) * per + 4) * sizeof(float);
+    const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
+    if (split) {
+        BlmNormRaggedIoParams rp{};
+        rp.src = r.src; rp.dst = r.dst; rp.d_src_off = r.d_src_off; rp.d_dst_off = r.d_dst_off; rp.d_cols = r.d_cols; rp.d_valid = r.d_valid;
+        rp.n_clips = r.n_clips; rp.n_mels = nm; rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
+        rp.ctr = ctr;
+        hipLaunchKernelGGL(r.out_dtype == MELSPEC_OUT_F16 ? blm_normalize_ragged_io_kernel<io_f16> : blm_normalize_ragged_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, rp);
+    } else {
+        BlmNormRaggedParams rp{};
+        rp.out = static_cast<float *>(r.dst); rp.d_out_off = r.d_dst_off; rp.d_cols = r.d_cols; rp.d_valid = r.d_valid;
+        rp.n_clips = r.n_clips; rp.n_mels = nm; rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
+        rp.longest = static_cast<uint32_t>(longest);
+        rp.ctr = ctr;
+        hipLaunchKernelGGL(blm_normalize_ragged_kernel, dim3(g2), dim3(kBlmNormThreads), lds, s, rp);
+    }
+    if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, split ? "blm_normalize_ragged_io_kernel launch failed" : "blm_normalize_ragged_kernel launch failed");
+    return MELSPEC_OK;
 }
 }  // namespace
 
@@ -811,8 +980,7 @@ static int blm_uniform(melspec_blm *b, const void *vd_pcm, uint64_t clip_stride,
     const uint64_t valid = blm_valid_frames(b, clip_len), cols = blm_padded(b, valid);
     if (cols == 0) return MELSPEC_OK;
     if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if (io && ((reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1))))
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     HIP_TRY(hipSetDevice(b->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
     const int nm = b->cfg.n_mels;
@@ -832,100 +1000,15 @@ static int blm_uniform(melspec_blm *b, const void *vd_pcm, uint64_t clip_stride,
                             b->dev.cus, s, static_cast<long long>(clip_len), b->cfg.center ? b->cfg.n_fft / 2 : 0);
         if (rc) return rc;
     } else {
-    const BatchPlan pl = plan_uniform(d_pcm, d_out, clip_stride, valid, n_clips, nm, kFbFPW, cols, true);
-    FbankFastParams fp{};
-    fp.b = pl.desc;
-    // feature-major store: waves holding adjacent units are kept in step (RoundSync); measured best for this kernel, see DESIGN 4.2b
-    if (fp.b.sync_rounds < 0) fp.b.sync_rounds = kNemoSync;
-    fp.d_blob = static_cast<const uint32_t *>(b->d_blob.p);
-    fp.blob_words = static_cast<int>(b->ft.blob.size());
-    fp.mel_off_words = b->ft.mel_off_words;
-    fp.shift = b->cfg.hop_length;
-    fp.n_mels = nm;
-    fp.preemph = b->cfg.preemphasis;
-    fp.floor_v = b->cfg.log_zero_guard;
-    fp.use_log = 1; fp.use_power = 1;
-    fp.clip_len = static_cast<long long>(clip_len);
-    fp.org0 = b->cfg.center ? -200 : 56;      // tap 0 of the window sits at position (512-400)/2 of the frame
-    fp.slots = b->ft.slots;
-    if (io) rc = launch_nemo_io(b, fp, io, s);
-    else if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
-    else if (fb_lens_match<LensSlaney128>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-    else if (fb_lens_match<LensSlaney80>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-    else rc = b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
-                                              : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-    if (rc) return rc;
+        const BatchPlan pl = plan_uniform(d_pcm, d_out, clip_stride, valid, n_clips, nm, kFbFPW, cols, true);
+        FbankFastParams fp = blm_fast_params(b, pl.desc);
+        // feature-major store: waves holding adjacent units are kept in step (RoundSync); measured best for this kernel, see DESIGN 4.2b
+        if (fp.b.sync_rounds < 0) fp.b.sync_rounds = kNemoSync;
+        fp.clip_len = static_cast<long long>(clip_len);
+        if ((rc = launch_nemo_mel(b, fp, io, s))) return rc;
     }
-    if (split) {
-        // blm_normalize_kernel's shape (rows per workgroup, workgroups per CU) on rows read from the scratch and written to the caller's
-        BlmNormIoParams np{};
-        np.src = d_out; np.dst = vd_out; np.row_w = cols; np.valid = valid; np.n_clips = n_clips; np.n_mels = nm;
-        const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-        size_t stride, per;
-        int per_cu;
-        blm_norm_shape_uniform(valid, stride, per, per_cu);
-        np.rows_per_group = static_cast<int>(per);
-        np.lds_stride = static_cast<int>(stride);
-        static std::atomic<uint64_t> attr_done{0};
-        if ((rc = allow_norm_io(&blm_normalize_io_kernel<io_f16>, &blm_normalize_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(blm_normalize_io_kernel)"))) return rc;
-        const bool f16 = out_dtype == MELSPEC_OUT_F16;
-        const size_t lds = per == 0 ? 0 : (per * stride + 2 * per + kBlmNormThreads) * sizeof(float);
-        const unsigned g2 = per == 0 ? grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4) : grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
-        hipLaunchKernelGGL(f16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, np);
-        HIP_TRY(hipGetLastError());
-        return MELSPEC_OK;
-    }
-    if (b->cfg.normalize_per_feature && valid > 0) {
-        BlmNormParams np{};
-        np.out = d_out; np.clip_stride = cols * static_cast<uint64_t>(nm); np.row_w = cols; np.valid = valid;
-        np.n_clips = n_clips; np.n_mels = nm;
-        static const int fold_sel = lab_int("MELSPEC_NORM_FOLD", -1, -1, 12);
-        np.fold_sel = fold_sel;
-        static const int norm_skip = lab_int("MELSPEC_NORM_SKIP", 0, 0, 7);
-        np.lab_skip = norm_skip;
-        const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-        size_t stride, per;
-        int per_cu;
-        blm_norm_shape_uniform(valid, stride, per, per_cu);
-        np.rows_per_group = static_cast<int>(per);
-        np.lds_stride = static_cast<int>(stride);
-        static std::atomic<uint64_t> attr_done{0};
-        if (!device_done(attr_done)) {
-            int rc2 = allow_big_lds(&blm_normalize_kernel, "hipFuncSetAttribute(blm_normalize_kernel)");
-            if (rc2) return rc2;
-            mark_device_done(attr_done);
-        }
-        if (per == 0) {
-            const unsigned g2 = grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4);
-            hipLaunchKernelGGL(blm_normalize_kernel, dim3(g2), dim3(kBlmNormThreads), 0, s, np);
-        } else {
-            const size_t lds = (per * stride + 2 * per + kBlmNormThreads) * sizeof(float);
-            const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
-#ifdef MELSPEC_LAB
-            static const int norm_dbg = lab_int("MELSPEC_NORM_DBG", 0, 0, 1);
-            static uint64_t *d_dbg = nullptr;
-            static int dbg_calls = 0;
-            if (norm_dbg) {
-                if (!d_dbg) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&d_dbg), 64 * 8 * 8));
-                HIP_TRY(hipMemsetAsync(d_dbg, 0, 64 * 8 * 8, s));
-                np.dbg = d_dbg;
-            }
-#endif
-            hipLaunchKernelGGL(blm_normalize_kernel, dim3(g2), dim3(kBlmNormThreads), lds, s, np);
-#ifdef MELSPEC_LAB
-            if (norm_dbg && ++dbg_calls == 20) {
-                uint64_t h[64 * 8];
-                HIP_TRY(hipStreamSynchronize(s));
-                HIP_TRY(hipMemcpy(h, d_dbg, sizeof(h), hipMemcpyDeviceToHost));
-                double sum[8] = {0};
-                for (int b = 0; b < 64; ++b) for (int k = 0; k < 8; ++k) sum[k] += static_cast<double>(h[b * 8 + k]);
-                std::fprintf(stderr, "norm phases, us per workgroup (mean of 64): load %.1f  mean %.1f  var %.1f  var-sum %.1f  store %.1f\n",
-                             sum[1] / 64 / 100, sum[2] / 64 / 100, sum[3] / 64 / 100, sum[4] / 64 / 100, sum[5] / 64 / 100);
-            }
-#endif
-        }
-        HIP_TRY(hipGetLastError());
-    }
+    if (b->cfg.normalize_per_feature && valid > 0)      // split: from the scratch to the caller's rows; otherwise in place
+        return launch_blm_norm(b, BlmNormRows{d_out, split ? vd_out : d_out, split ? out_dtype : MELSPEC_OUT_F32, n_clips, nullptr, nullptr, nullptr, nullptr}, cols, valid, s);
     return MELSPEC_OK;
 }
 
@@ -964,109 +1047,35 @@ static int blm_ragged(melspec_blm *b, const void *vd_pcm, const uint64_t *h_offs
     }
     if (total == 0) return MELSPEC_OK;
     if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if (io && ((reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(out_dtype) - 1))))
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     HIP_TRY(hipSetDevice(b->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
     const int nm = b->cfg.n_mels;
-    if (b->aux_used && b->aux_stream != s) HIP_TRY(hipStreamSynchronize(b->aux_stream));
-    b->aux_used = true; b->aux_stream = s;
-    int rc = b->aux.ensure(aux.size() * sizeof(uint64_t));
+    int rc = b->aux.ensure(aux.size() * sizeof(uint64_t), s);
     if (rc) return rc;
+    const uint64_t *d_aux = static_cast<const uint64_t *>(b->aux.p());
     if (split) {
         if ((rc = blm_rows32(b, total * static_cast<uint64_t>(nm), s, d_out))) return rc;
         if (own_offsets) std::copy(h_out_offsets, h_out_offsets + n_clips, aux.begin() + 2 * static_cast<size_t>(n_clips) + 1);
         h_out_offsets = nullptr;
         io &= 15;
     }
-    HIP_TRY(hipMemcpyAsync(b->aux.p, aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
+    HIP_TRY(hipMemcpyAsync(b->aux.p(), aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
     BatchPlan pl;
     RaggedSlot *slot = nullptr;
     rc = plan_ragged(b->ragged, s, d_pcm, d_out, h_offsets, cols, h_out_offsets, n_clips, nm, kFbFPW, pl, slot);
     if (!rc) {
-        FbankFastParams fp{};
-        fp.b = pl.desc;
+        FbankFastParams fp = blm_fast_params(b, pl.desc);
         fp.b.mel_major = 1;
         fp.b.sync_rounds = kNemoSync;
-        fp.d_blob = static_cast<const uint32_t *>(b->d_blob.p);
-        fp.blob_words = static_cast<int>(b->ft.blob.size());
-        fp.mel_off_words = b->ft.mel_off_words;
-        fp.shift = b->cfg.hop_length;
-        fp.n_mels = nm;
-        fp.preemph = b->cfg.preemphasis;
-        fp.floor_v = b->cfg.log_zero_guard;
-        fp.use_log = 1; fp.use_power = 1;
-        fp.org0 = b->cfg.center ? -200 : 56;
-        fp.d_len = static_cast<const uint64_t *>(b->aux.p);
-        fp.d_valid = fp.d_len + n_clips;
-        fp.slots = b->ft.slots;
-        if (io) rc = launch_nemo_io(b, fp, io, s);
-        else if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) rc = launch_nemo_f32(b->f32, fp, b->dev.cus, s);
-        else if (fb_lens_match<LensSlaney128>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-        else if (fb_lens_match<LensSlaney80>(b->ft.slots)) rc = launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-        else rc = b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
-                                                  : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-        if (!rc && split && longest > 0) {
-            // blm_normalize_ragged_kernel's shape; source rows at the plan's packed offsets, destination rows at the caller's
-            const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-            const uint64_t *d_dst_off = own_offsets ? static_cast<const uint64_t *>(b->aux.p) + 2 * static_cast<size_t>(n_clips) + 1 : pl.desc.d_out_off;
-            size_t stride, per;
-            int per_cu;
-            blm_norm_shape_ragged(longest, stride, per, per_cu);      // (its rows carry two more words each: <= 512 bytes)
-            const bool f16 = out_dtype == MELSPEC_OUT_F16;
-            if (per >= 1 && longest < (1ull << 31)) {
-                static std::atomic<uint64_t> attr_done{0};
-                rc = allow_norm_io(&blm_normalize_ragged_io_kernel<io_f16>, &blm_normalize_ragged_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(blm_normalize_ragged_io_kernel)");
-                if (!rc) {
-                    BlmNormRaggedIoParams rp{};
-                    rp.src = d_out; rp.dst = vd_out; rp.d_src_off = pl.desc.d_out_off; rp.d_dst_off = d_dst_off; rp.d_cols = pl.desc.d_frames; rp.d_valid = fp.d_valid;
-                    rp.n_clips = n_clips; rp.n_mels = nm; rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
-                    rp.ctr = reinterpret_cast<unsigned *>(static_cast<uint64_t *>(b->aux.p) + 2 * static_cast<size_t>(n_clips));
-                    const size_t lds = (per * stride + 2 * per + kBlmNormThreads + kBlmNormIoInfo * per + 4) * sizeof(float);
-                    const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
-                    hipLaunchKernelGGL(f16 ? blm_normalize_ragged_io_kernel<io_f16> : blm_normalize_ragged_io_kernel<io_bf16>, dim3(g2), dim3(kBlmNormThreads), lds, s, rp);
-                    if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_ragged_io_kernel launch failed");
-                }
-            } else {
-                // rows too long for LDS: one thread per row from HBM
-                BlmNormIoParams np{};
-                np.src = d_out; np.dst = vd_out; np.n_clips = n_clips; np.n_mels = nm; np.rows_per_group = 0;
-                np.d_src_off = pl.desc.d_out_off; np.d_dst_off = d_dst_off; np.d_cols = pl.desc.d_frames; np.d_valid = fp.d_valid;
-                hipLaunchKernelGGL(f16 ? blm_normalize_io_kernel<io_f16> : blm_normalize_io_kernel<io_bf16>,
-                                   dim3(grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4)), dim3(kBlmNormThreads), 0, s, np);
-                if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_io_kernel launch failed");
-            }
-        } else if (!rc && b->cfg.normalize_per_feature && longest > 0) {
-            const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
-            size_t stride, per;
-            int per_cu;
-            blm_norm_shape_ragged(longest, stride, per, per_cu);
-            if (per >= 1 && longest < (1ull << 31)) {
-                static std::atomic<uint64_t> attr_done{0};
-                if (!device_done(attr_done)) {
-                    rc = allow_big_lds(&blm_normalize_ragged_kernel, "hipFuncSetAttribute(blm_normalize_ragged_kernel)");
-                    if (!rc) mark_device_done(attr_done);
-                }
-                if (!rc) {
-                    BlmNormRaggedParams rp{};
-                    rp.out = d_out; rp.d_out_off = pl.desc.d_out_off; rp.d_cols = pl.desc.d_frames; rp.d_valid = fp.d_valid;
-                    rp.n_clips = n_clips; rp.n_mels = nm; rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
-                    rp.longest = static_cast<uint32_t>(longest);
-                    rp.ctr = reinterpret_cast<unsigned *>(static_cast<uint64_t *>(b->aux.p) + 2 * static_cast<size_t>(n_clips));
-                    const size_t lds = (per * stride + 2 * per + kBlmNormThreads + 4 * per + 4) * sizeof(float);
-                    const unsigned g2 = grid_for((rows + per - 1) / per, b->dev.cus, per_cu);
-                    hipLaunchKernelGGL(blm_normalize_ragged_kernel, dim3(g2), dim3(kBlmNormThreads), lds, s, rp);
-                    if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_ragged_kernel launch failed");
-                }
-            } else {
-                // rows too long for LDS: one thread per row from HBM
-                BlmNormParams np{};
-                np.fold_sel = -1;
-                np.out = d_out; np.n_clips = n_clips; np.n_mels = nm; np.rows_per_group = 0;
-                np.d_out_off = pl.desc.d_out_off; np.d_cols = pl.desc.d_frames; np.d_valid = fp.d_valid;
-                hipLaunchKernelGGL(blm_normalize_kernel, dim3(grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4)), dim3(kBlmNormThreads), 0, s, np);
-                if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_normalize_kernel launch failed");
-            }
+        fp.d_len = d_aux;
+        fp.d_valid = d_aux + n_clips;
+        rc = launch_nemo_mel(b, fp, io, s);
+        if (!rc && b->cfg.normalize_per_feature && longest > 0) {
+            // split: source rows at the plan's packed offsets in the scratch, destination rows at the caller's; otherwise in place
+            const uint64_t *d_dst_off = own_offsets ? d_aux + 2 * static_cast<size_t>(n_clips) + 1 : pl.desc.d_out_off;
+            const BlmNormRows rows{d_out, split ? vd_out : d_out, split ? out_dtype : MELSPEC_OUT_F32, n_clips, pl.desc.d_out_off, d_dst_off, pl.desc.d_frames, fp.d_valid};
+            rc = launch_blm_norm_ragged(b, rows, longest, reinterpret_cast<unsigned *>(static_cast<uint64_t *>(b->aux.p()) + 2 * static_cast<size_t>(n_clips)), s);
         }
     }
     plan_ragged_done(slot, s);
@@ -1080,8 +1089,7 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
 
 // ---- int16 PCM in / f16, bf16 rows out: see include/melspec_hip.h ----
 int melspec_blm_supports_io(const melspec_blm *b, int pcm_dtype, int out_dtype) {
-    if (!b || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    if (!b || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
     return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || blm_io_ok(b) ? 1 : 0;
 }
 
@@ -1100,12 +1108,9 @@ int melspec_blm_compute_ragged_device_io(melspec_blm *b, const void *d_pcm, int 
     return blm_ragged(b, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, io);
 }
 
-// One clip from host memory: the 16-bit bytes cross the bus, the kernels convert.
-int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
-                                size_t out_capacity_elems, size_t *rows, size_t *cols) {
-    int io, rc = blm_io_args(b, pcm_dtype, out_dtype, io);
-    if (rc) return rc;
-    if (!io) return melspec_blm_compute_host(b, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, rows, cols);
+// One clip from host memory (io = 0: the f32 call): the bytes of the caller's types cross the bus, the kernels convert.
+static int blm_host(melspec_blm *b, const void *samples, size_t n_samples, void *out, size_t out_capacity_elems, size_t *rows, size_t *cols, int io) {
+    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     if (rows) *rows = static_cast<size_t>(b->cfg.n_mels);
     if (cols) *cols = 0;
     const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
@@ -1114,7 +1119,8 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
     const uint64_t need = c * static_cast<uint64_t>(b->cfg.n_mels);
     if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
     HIP_TRY(hipSetDevice(b->dev.device));
-    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
+    const size_t ib = io_pcm_bytes(io & 15), ob = io_out_bytes(io >> 4);
+    int rc;
     if ((rc = b->h2d.ensure(n_samples * ib))) return rc;
     if ((rc = b->d2h.ensure(need * ob))) return rc;
     HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, b->stream));
@@ -1126,14 +1132,20 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
     return MELSPEC_OK;
 }
 
+int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
+                                size_t out_capacity_elems, size_t *rows, size_t *cols) {
+    int io, rc = blm_io_args(b, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return blm_host(b, samples, n_samples, out, out_capacity_elems, rows, cols, io);
+}
+
 int melspec_blm_release_scratch(melspec_blm *b) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     HIP_TRY(hipSetDevice(b->dev.device));
     HIP_TRY(hipStreamSynchronize(b->stream));
-    if (b->aux_used && b->aux_stream != b->stream) HIP_TRY(hipStreamSynchronize(b->aux_stream));
-    if (b->rows32_used && b->rows32_stream != b->stream) HIP_TRY(hipStreamSynchronize(b->rows32_stream));
-    b->pipe.release(); b->ragged.release(); b->aux.release(); b->h2d.release(); b->d2h.release(); b->rows32.release();
-    b->aux_used = false; b->rows32_used = false;
+    if (int rc = b->aux.release_after(b->stream)) return rc;
+    if (int rc = b->rows32.release_after(b->stream)) return rc;
+    b->pipe.release(); b->ragged.release(); b->h2d.release(); b->d2h.release();
     return MELSPEC_OK;
 }
 
@@ -1146,26 +1158,7 @@ int melspec_blm_synchronize(melspec_blm *b, void *stream) {
 
 int melspec_blm_compute_host(melspec_blm *b, const float *samples, size_t n_samples, float *out, size_t out_capacity_floats,
                              size_t *rows, size_t *cols) {
-    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
-    if (rows) *rows = static_cast<size_t>(b->cfg.n_mels);
-    if (cols) *cols = 0;
-    const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
-    if (c == 0) return MELSPEC_OK;
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    const uint64_t need = c * static_cast<uint64_t>(b->cfg.n_mels);
-    if (out_capacity_floats < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(b->dev.device));
-    int rc;
-    if ((rc = b->h2d.ensure(n_samples * sizeof(float)))) return rc;
-    if ((rc = b->d2h.ensure(need * sizeof(float)))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * sizeof(float), hipMemcpyHostToDevice, b->stream));
-    rc = melspec_blm_compute_uniform_device(b, static_cast<const float *>(b->h2d.p), n_samples, n_samples, 1,
-                                            static_cast<float *>(b->d2h.p), b->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, b->d2h.p, need * sizeof(float), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (cols) *cols = static_cast<size_t>(c);
-    return MELSPEC_OK;
+    return blm_host(b, samples, n_samples, out, out_capacity_floats, rows, cols, 0);
 }
 
 // BatchLogMelSpectrogram::compute on many host clips in one call: clip i -> [n_mels][cols_i] floats at out + out_offsets[i] (NULL:
@@ -1223,10 +1216,7 @@ bool fbank_io_ok(const melspec_fbank *fb) { return fb->fast && !fb->use_generic 
 // 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
 int fbank_io_args(const melspec_fbank *fb, int pcm_dtype, int out_dtype, int &io) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
-        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
-    io = pcm_dtype | out_dtype << 4;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     if (io && !fbank_io_ok(fb)) {
         char geo[256];
         std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d, low_freq = %g, high_freq = %g",
@@ -1262,12 +1252,10 @@ int launch_kaldi_io(melspec_fbank *fb, const FbankFastParams &fp, int pcm, int o
 
 // the scratch of a CMN call with 16-bit rows out on stream s: `floats` f32 rows and, behind them, `tail` 64-bit words
 int fbank_rows32(melspec_fbank *fb, uint64_t floats, size_t tail, hipStream_t s, float *&rows, uint64_t *&words) {
-    if (fb->rows32_used && fb->rows32_stream != s) HIP_TRY(hipStreamSynchronize(fb->rows32_stream));
-    fb->rows32_used = true; fb->rows32_stream = s;
     const size_t row_bytes = (static_cast<size_t>(floats) * sizeof(float) + 15) & ~static_cast<size_t>(15);
-    const int rc = fb->rows32.ensure(row_bytes + tail * sizeof(uint64_t) + 16);     // (growing frees the old buffer: hipFree waits for the device)
-    rows = static_cast<float *>(fb->rows32.p);
-    words = reinterpret_cast<uint64_t *>(static_cast<char *>(fb->rows32.p) + row_bytes);
+    const int rc = fb->rows32.ensure(row_bytes + tail * sizeof(uint64_t) + 16, s);
+    rows = static_cast<float *>(fb->rows32.p());
+    words = reinterpret_cast<uint64_t *>(static_cast<char *>(fb->rows32.p()) + row_bytes);
     return rc;
 }
 
@@ -1282,24 +1270,8 @@ int fbank_launch_io(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, ui
     int rc = (pcm | kout) == 0 ? launch_fused512<double, kFlavorKaldi, kFbSlots, LensKaldi80>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s)
                                : launch_kaldi_io(fb, fp, pcm, kout, s);
     if (rc || !fb->cfg.apply_cmn) return rc;
-    if (!split) return fbank_cmn(fb, pl.desc, n_clips, fpc, s, nullptr);        // (S16, F32): the f32 rows are the caller's, in place
-    CmnIoParams cp{};
-    cp.b = pl.desc;
-    cp.dst = vd_out;
-    cp.d_dst_off = d_dst_off;
-    cp.n_mels = fb->cfg.num_mel_bins;
-    size_t lds;
-    cmn_shape(cp.n_mels, fpc, cp.rows_per_chunk, lds);
-    static std::atomic<uint64_t> attr_done{0};
-    if ((rc = allow_norm_io(&cmn_io_kernel<io_f16>, &cmn_io_kernel<io_bf16>, attr_done, "hipFuncSetAttribute(cmn_io_kernel)"))) return rc;
-    const unsigned grid = grid_for(n_clips, fb->dev.cus, 8);
-    hipLaunchKernelGGL(out_dtype == MELSPEC_OUT_F16 ? cmn_io_kernel<io_f16> : cmn_io_kernel<io_bf16>, dim3(grid), dim3(kCmnThreads), lds, s, cp);
-    HIP_TRY(hipGetLastError());
-    return MELSPEC_OK;
-}
-
-bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
-    return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
+    if (!split) return launch_cmn(fb, pl.desc, n_clips, fpc, s, nullptr);        // (S16, F32): the f32 rows are the caller's, in place
+    return launch_cmn(fb, pl.desc, n_clips, fpc, s, nullptr, vd_out, out_dtype, d_dst_off);
 }
 
 // melspec_fbank_compute_uniform_device with io = pcm_dtype | out_dtype << 4 != 0 (fbank_io_args): int16 samples and / or f16, bf16 rows
@@ -1327,8 +1299,7 @@ int fbank_uniform_io(melspec_fbank *fb, const void *vd_pcm, uint64_t clip_stride
 extern "C" {
 
 int melspec_fbank_supports_io(const melspec_fbank *fb, int pcm_dtype, int out_dtype) {
-    if (!fb || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    if (!fb || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
     return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || fbank_io_ok(fb) ? 1 : 0;
 }
 
@@ -1347,16 +1318,13 @@ int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm,
     int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
     if (rc) return rc;
     if (!io) return melspec_fbank_compute_ragged_device(fb, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_out), h_out_offsets, stream);
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    std::vector<uint64_t> frames(n_clips);
-    uint64_t total = 0, longest = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) { frames[i] = fbank_frames(fb, h_lengths[i]); total += frames[i]; longest = std::max(longest, frames[i]); }
-    if (total == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if (io_misaligned(d_pcm, d_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    FbankRagged r;
+    bool go;
+    rc = fbank_ragged_begin(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, stream, io, r, go);
+    if (!go) return rc;
+    const std::vector<uint64_t> &frames = r.frames;
+    const uint64_t total = r.total, longest = r.longest;
+    hipStream_t s = r.s;
     const int nm = fb->cfg.num_mel_bins;
     float *d_rows = static_cast<float *>(d_out);
     // CMN with 16-bit rows: the wave kernel writes f32 rows, packed in clip order, into the scratch (fbank_uniform_io); the caller's own
@@ -1379,12 +1347,9 @@ int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm,
     return rc;
 }
 
-// One clip from host memory: the 16-bit bytes cross the bus, the kernels convert.
-int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples,
-                                  void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames) {
-    int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
-    if (rc) return rc;
-    if (!io) return melspec_fbank_compute_host(fb, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, n_frames);
+// One clip from host memory (io = 0: the f32 call): the bytes of the caller's types cross the bus, the kernels convert.
+static int fbank_host(melspec_fbank *fb, const void *samples, size_t n_samples, void *out, size_t out_capacity_elems, size_t *n_frames, int io) {
+    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     if (n_frames) *n_frames = 0;
     const uint64_t frames = fbank_frames(fb, n_samples);
     if (frames == 0) return MELSPEC_OK;
@@ -1392,16 +1357,30 @@ int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pc
     const uint64_t need = frames * static_cast<uint64_t>(fb->cfg.num_mel_bins);
     if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
     HIP_TRY(hipSetDevice(fb->dev.device));
-    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
+    const size_t ib = io_pcm_bytes(io & 15), ob = io_out_bytes(io >> 4);
+    int rc;
     if ((rc = fb->h2d.ensure(n_samples * ib))) return rc;
     if ((rc = fb->d2h.ensure(need * ob))) return rc;
     HIP_TRY(hipMemcpyAsync(fb->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, fb->stream));
-    rc = fbank_uniform_io(fb, fb->h2d.p, n_samples, n_samples, 1, fb->d2h.p, fb->stream, io);
+    rc = io ? fbank_uniform_io(fb, fb->h2d.p, n_samples, n_samples, 1, fb->d2h.p, fb->stream, io)
+            : melspec_fbank_compute_uniform_device(fb, static_cast<const float *>(fb->h2d.p), n_samples, n_samples, 1, static_cast<float *>(fb->d2h.p), fb->stream);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(out, fb->d2h.p, need * ob, hipMemcpyDeviceToHost, fb->stream));
     HIP_TRY(hipStreamSynchronize(fb->stream));
     if (n_frames) *n_frames = static_cast<size_t>(frames);
     return MELSPEC_OK;
+}
+
+int melspec_fbank_compute_host(melspec_fbank *fb, const float *samples, size_t n_samples, float *out,
+                               size_t out_capacity_floats, size_t *n_frames) {
+    return fbank_host(fb, samples, n_samples, out, out_capacity_floats, n_frames, 0);
+}
+
+int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples,
+                                  void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames) {
+    int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return fbank_host(fb, samples, n_samples, out, out_capacity_elems, n_frames, io);
 }
 
 }  // extern "C"

@@ -575,7 +575,7 @@ constexpr int kBlmNormThreads = 256;
 
 // lab builds: thread 0 of the first 64 workgroups adds up the time (100 MHz ticks) between the barriers of a round (MELSPEC_NORM_DBG)
 #if defined(MELSPEC_LAB) && !defined(MELSPEC_NORM_NO_STAMPS)
-#define MS_NORM_STAMP(k) do { if (p.dbg && tid == 0 && blockIdx.x < 64) { const uint64_t now = wall_clock64(); if ((k) > 0) p.dbg[blockIdx.x * 8 + (k)] += now - stamp; stamp = now; } } while (0)
+#define MS_NORM_STAMP(k) do { if (dbg && tid == 0 && blockIdx.x < 64) { const uint64_t now = wall_clock64(); if ((k) > 0) dbg[blockIdx.x * 8 + (k)] += now - stamp; stamp = now; } } while (0)
 #else
 #define MS_NORM_STAMP(k) do { } while (0)
 #endif
@@ -653,178 +653,38 @@ __device__ __forceinline__ void blm_row_stats_slow(const float *r, uint64_t vali
     sd = __builtin_sqrtf(f32_div_rn(q, denom)) + 1e-5f;
 }
 
-// (the two kernels that are not templates are defined once: fbank512_io.hip, which includes this header for everything around them, leaves them out)
-// KEEP IN STEP with blm_normalize_io_kernel (fbank512_io_kernels.hpp), the copy that reads the rows from a scratch and writes 16-bit rows: its
-// staging, mean fold and sum-of-squares tree must stay the ones below, operation for operation -- a 16-bit call gives the rounding of
-// this kernel's bits (tests/test_blm_io_dtypes.py).  It is a copy because this kernel's instructions were not to change.
-#ifndef MS_FBANK512_NO_PLAIN_KERNELS
-__global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_kernel(const BlmNormParams p) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];
-    const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
-    const int tid = threadIdx.x;
-    if (p.rows_per_group == 0) {
-        for (uint64_t row = (uint64_t)blockIdx.x * kBlmNormThreads + tid; row < rows; row += (uint64_t)gridDim.x * kBlmNormThreads) {
-            float *r;
-            uint64_t valid = p.valid;
-            if (p.d_out_off) {
-                const uint64_t clip = row / p.n_mels, m = row - clip * p.n_mels;
-                r = p.out + p.d_out_off[clip] + m * p.d_cols[clip];
-                valid = p.d_valid[clip];
-                if (valid == 0) continue;
-            } else {
-                r = blm_row(p, row);
-            }
-            float mean, sd;
-            blm_row_stats_slow(r, valid, mean, sd);
-            for (uint64_t k = 0; k < valid; ++k) r[k] = f32_div_rn(r[k] - mean, sd);
-        }
+// four columns of a row to 16-bit values at dst[0 .. 4) where they lie inside the row (columns [c0, c0 + 4) of row_w): one 8-byte store at
+// 2-byte alignment (rows start at odd elements whenever row_w is odd) or element by element at the row's ends
+template <class Out>
+__device__ __forceinline__ void blm_store4(Out *g, int c0, uint32_t row_w, const float (&o)[4]) {
+    typedef uint32_t w2u __attribute__((ext_vector_type(2), aligned(2)));
+    if (c0 >= 0 && static_cast<uint32_t>(c0 + 3) < row_w) {
+        const Out h0 = row_value<Out>(o[0]), h1 = row_value<Out>(o[1]), h2 = row_value<Out>(o[2]), h3 = row_value<Out>(o[3]);
+        const uint32_t lo = __builtin_bit_cast(uint16_t, h0) | static_cast<uint32_t>(__builtin_bit_cast(uint16_t, h1)) << 16;
+        const uint32_t hi = __builtin_bit_cast(uint16_t, h2) | static_cast<uint32_t>(__builtin_bit_cast(uint16_t, h3)) << 16;
+        *reinterpret_cast<w2u *>(g) = w2u{lo, hi};
         return;
     }
-    const int R = p.rows_per_group, S = p.lds_stride;
-    float *stat = tile + (size_t)R * S;      // [R][2]
-    const int fold_wave = p.fold_sel < 0 ? 0 : static_cast<int>((blockIdx.x >> p.fold_sel) & 3u);
-    // Rows of one clip are contiguous and so are the clips (clip_stride == n_mels * row_w): row r starts at out + r * row_w, at
-    // any 4-byte alignment (1001 columns for a 10 s clip without pad_to).  Global memory is accessed in whole 16-byte granules
-    // all the same: a row whose first float sits `a` floats into its granule is staged from the granule's start, at the same
-    // offset `a` in its 16-byte aligned LDS row; the granules a row shares with its neighbours are loaded by both and stored
-    // float by float.  kRowsAtOnce rows in flight per thread (a load inside a per-row `if` would be one memory round trip per
-    // row; rows past the group re-read its last row, granules past the row its last granule).
-    constexpr int kRowsAtOnce = 9;
-    const uint32_t valid = static_cast<uint32_t>(p.valid);
-    const uint32_t out_f = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p.out) >> 2) & 3u;
-    const uint32_t nq_max = (valid + 6) / 4;            // granules of a row at the worst alignment
-    // A workgroup owns a contiguous range of rows and walks it in rounds of R.  (Starting the workgroups out of step -- a short
-    // first round, a sleep per workgroup -- was measured: no effect; once its phases are cheap the pass is bandwidth-bound.)
-    const uint64_t per_wg = (rows + gridDim.x - 1) / gridDim.x;
-    const uint64_t row_begin = (uint64_t)blockIdx.x * per_wg;
-    const uint64_t row_end = row_begin + per_wg < rows ? row_begin + per_wg : rows;
-    float *part = stat + 2 * R;              // [R][PP] partial sums of squares
-    uint64_t stamp = 0;
-    (void)stamp;
-    const int PP = kBlmNormThreads / R;      // threads per row in the variance pass
-    for (uint64_t row0 = row_begin; row0 < row_end;) {
-        MS_NORM_STAMP(0);
-        const int nr = row_end - row0 < (uint64_t)R ? (int)(row_end - row0) : R;
-        const uint64_t e00 = row0 * p.row_w;
-        for (int rr0 = 0; rr0 < ((p.lab_skip & 4) ? 0 : nr); rr0 += kRowsAtOnce) {
-            for (uint32_t q = tid; q < nq_max; q += kBlmNormThreads) {
-                f4 v[kRowsAtOnce];
-                uint32_t to[kRowsAtOnce];
-                uint64_t e0 = e00 + (uint64_t)rr0 * p.row_w;
-                uint32_t t = static_cast<uint32_t>(rr0) * S;
 #pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) {
-                    const uint32_t a = (out_f + static_cast<uint32_t>(e0)) & 3u;
-                    const uint32_t nq = (a + valid + 3) >> 2;
-                    const uint32_t qq = q < nq ? q : nq - 1;
-                    v[i] = *reinterpret_cast<const f4 *>(p.out + e0 - a + 4 * qq);
-                    to[i] = t + 4 * qq;
-                    if (rr0 + i + 1 < nr) { e0 += p.row_w; t += S; }
-                }
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) *reinterpret_cast<f4 *>(tile + to[i]) = v[i];
-            }
-        }
-        __syncthreads();
-        MS_NORM_STAMP(1);
-        // the means: a few lanes of ONE wave (fold_sel: which one; measured without effect)
-        const int ft = tid - 64 * fold_wave;
-        if (ft >= 0 && ft < nr) {
-            const uint32_t a = (out_f + static_cast<uint32_t>(e00 + (uint64_t)ft * p.row_w)) & 3u;
-            MS_PRIO(3);                          // a chain of dependent adds: every issue slot it is ready for
-            stat[2 * ft] = (p.lab_skip & 1) ? 0.0f : blm_row_mean_lds(tile + (size_t)ft * S, a, valid);
-            MS_PRIO(0);
-        }
-        __syncthreads();
-        MS_NORM_STAMP(2);
-        // the unbiased variance: sum of (v - mean)^2 as a fixed tree over all threads, PP strided partial sums per row added in
-        // order.  The reference folds this sum left to right as well; unlike the mean, the order is immaterial here -- either
-        // sum is within ~1e-6 (relative) of the exact one, 5e-7 of the standard deviation, and the output moves by |out| * 5e-7.
-        {
-            const int r = tid / PP, pt = tid - r * PP;
-            if (r < nr) {
-                const uint32_t a = (out_f + static_cast<uint32_t>(e00 + (uint64_t)r * p.row_w)) & 3u;
-                const float *row = tile + (size_t)r * S + a;
-                const float mean = stat[2 * r];
-                // four sums in turn: the strided loop has a run-time step, and with one accumulator every LDS read waited for
-                // the add before it (2.1 us per round, measured with MS_NORM_STAMP; 36 values per thread at 1001 frames)
-                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-                uint32_t k = pt;
-                for (; k + 3 * PP < valid; k += 4 * PP) {
-                    const float c0 = row[k] - mean, c1 = row[k + PP] - mean, c2 = row[k + 2 * PP] - mean, c3 = row[k + 3 * PP] - mean;
-                    a0 += c0 * c0; a1 += c1 * c1; a2 += c2 * c2; a3 += c3 * c3;
-                }
-                for (; k < valid; k += PP) {
-                    const float c = row[k] - mean;
-                    a0 += c * c;
-                }
-                part[r * PP + pt] = (a0 + a1) + (a2 + a3);
-            }
-        }
-        __syncthreads();
-        MS_NORM_STAMP(3);
-        if (tid < nr) {
-            const float *pp = part + tid * PP;
-            float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
-            int i = 0;
-            for (; i + 3 < PP; i += 4) { q0 += pp[i]; q1 += pp[i + 1]; q2 += pp[i + 2]; q3 += pp[i + 3]; }
-            for (; i < PP; ++i) q0 += pp[i];
-            const float q = (q0 + q1) + (q2 + q3);
-            float denom = static_cast<float>(valid) - 1.0f;
-            denom = denom < 1.0f ? 1.0f : denom;
-            // the row's values are multiplied by 1 / (std + 1e-5) below: within one ulp of the reference's division, 9 divisions
-            // per round instead of 36 per thread (the divisions were 4.7 us of a 16 us round)
-            const float sd = __builtin_sqrtf(f32_div_rn(q, denom)) + 1e-5f;
-            stat[2 * tid + 1] = (p.lab_skip & 1) ? 1.0f : f32_div_rn(1.0f, sd);
-        }
-        __syncthreads();
-        MS_NORM_STAMP(4);
-        const uint32_t row_w = static_cast<uint32_t>(p.row_w);
-        for (int rr0 = 0; rr0 < ((p.lab_skip & 2) ? 0 : nr); rr0 += kRowsAtOnce) {
-            for (uint32_t q = tid; q < nq_max; q += kBlmNormThreads) {
-                f4 v[kRowsAtOnce];
-                float mean[kRowsAtOnce], rsd[kRowsAtOnce];
-                uint32_t t = static_cast<uint32_t>(rr0) * S + 4 * q;
-                const float *st = stat + 2 * rr0;
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) {           // every LDS read first (rows past the group: its last row again)
-                    v[i] = *reinterpret_cast<const f4 *>(tile + t);
-                    mean[i] = st[0]; rsd[i] = st[1];
-                    if (rr0 + i + 1 < nr) { t += S; st += 2; }
-                }
-                uint64_t e0 = e00 + (uint64_t)rr0 * p.row_w;
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) {
-                    const uint32_t a = (out_f + static_cast<uint32_t>(e0)) & 3u;
-                    const int c0 = static_cast<int>(4 * q) - static_cast<int>(a);       // column of the granule's first float
-                    float o[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {                 // columns past the valid frames keep their zeros
-                        const float nv = (o[e] - mean[i]) * rsd[i];
-                        o[e] = (c0 + e >= 0 && static_cast<uint32_t>(c0 + e) < valid) ? nv : 0.0f;
-                    }
-                    float *g = p.out + e0 + c0;
-                    const bool mine = rr0 + i < nr && 4 * q < a + valid;                 // granules that hold valid frames of a row of the group
-                    if (mine) {
-                        if (c0 >= 0 && static_cast<uint32_t>(c0 + 3) < row_w) {
-                            f4 w = {o[0], o[1], o[2], o[3]};
-                            *reinterpret_cast<f4 *>(g) = w;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (c0 + e >= 0 && static_cast<uint32_t>(c0 + e) < row_w) g[e] = o[e];
-                        }
-                    }
-                    if (rr0 + i + 1 < nr) e0 += p.row_w;
-                }
-            }
-        }
-        __syncthreads();
-        MS_NORM_STAMP(5);
-        row0 += nr;
-    }
+    for (int e = 0; e < 4; ++e)
+        if (c0 + e >= 0 && static_cast<uint32_t>(c0 + e) < row_w) g[e] = row_value<Out>(o[e]);
 }
 
+// The pass in place on f32 rows.  Its body is fbank512_norm_body.inc, which blm_normalize_io_kernel (fbank512_io_kernels.hpp: f32 rows of a
+// scratch -> 16-bit rows) includes too: what is set here is all that the two differ in.
+// (the two kernels that are not templates are defined once: fbank512_io.hip, which includes this header for everything around them, leaves them out)
+#ifndef MS_FBANK512_NO_PLAIN_KERNELS
+__global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_kernel(const BlmNormParams p) {
+    using Out = float;
+    constexpr bool kSplit = false;
+    const float *const src = p.out;
+    Out *const dst = p.out;
+    const uint64_t *const d_src_off = p.d_out_off, *const d_dst_off = p.d_out_off;
+    const uint64_t clip_stride = p.clip_stride;
+    const int fold_sel = p.fold_sel, lab_skip = p.lab_skip;
+    uint64_t *const dbg = p.dbg;
+#include "fbank512_norm_body.inc"
+}
 #endif
 
 // The same pass for ragged batches (clips of different lengths in one launch): rows are described per clip (first output float, row
@@ -841,141 +701,17 @@ struct BlmNormRaggedParams {
     unsigned *ctr;          // zero at launch
 };
 
-// KEEP IN STEP with blm_normalize_ragged_io_kernel (fbank512_io_kernels.hpp): see blm_normalize_kernel
+constexpr int kBlmNormInfo = 4, kBlmNormIoInfo = 6;     // words per staged row in LDS: in place, split (fbank512_norm_ragged_body.inc)
+// in place on f32 rows; blm_normalize_ragged_io_kernel (fbank512_io_kernels.hpp) includes the same body
 #ifndef MS_FBANK512_NO_PLAIN_KERNELS
 __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_ragged_kernel(const BlmNormRaggedParams p) {
-    extern __shared__ __attribute__((aligned(16))) float tile[];
-    const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
-    const int tid = threadIdx.x;
-    const int R = p.rows_per_group, S = p.lds_stride;
-    float *stat = tile + (size_t)R * S;      // [R][2]
-    float *part = stat + 2 * R;              // [R][PP]
-    uint32_t *info = reinterpret_cast<uint32_t *>(part + kBlmNormThreads);     // [R][4]: first float (lo, hi), valid frames, row width
-    uint32_t *next = info + 4 * R;
-    const int PP = kBlmNormThreads / R;
-    constexpr int kRowsAtOnce = 9;
-    const uint32_t out_f = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(p.out) >> 2) & 3u;
-    const f4 *out_base = reinterpret_cast<const f4 *>(p.out - out_f);        // the 16-byte granule `out` starts in
-    for (;;) {
-        if (tid == 0) next[0] = atomicAdd(p.ctr, 1u);
-        __syncthreads();
-        const uint64_t row0 = (uint64_t)next[0] * R;
-        if (row0 >= rows) break;
-        const int nr = rows - row0 < (uint64_t)R ? (int)(rows - row0) : R;
-        if (tid < nr) {
-            const uint64_t row = row0 + tid, clip = row / p.n_mels, m = row - clip * p.n_mels;
-            const uint64_t cols = p.d_cols[clip], e0 = p.d_out_off[clip] + m * cols;
-            info[4 * tid] = static_cast<uint32_t>(e0);
-            info[4 * tid + 1] = static_cast<uint32_t>(e0 >> 32);
-            info[4 * tid + 2] = static_cast<uint32_t>(p.d_valid[clip]);
-            info[4 * tid + 3] = static_cast<uint32_t>(cols);
-        }
-        __syncthreads();
-        // granules of the longest row OF THIS GROUP (round 5: both copy loops ran to the longest row of the batch -- clips of 5..15 s
-        // made a third of their iterations re-read and re-write a short row's last granule)
-        uint32_t gmax = 0;
-        for (int rr = 0; rr < nr; ++rr) gmax = info[4 * rr + 2] > gmax ? info[4 * rr + 2] : gmax;
-        const uint32_t nq_grp = gmax ? (gmax + 6) / 4 : 0;
-        for (int rr0 = 0; rr0 < nr; rr0 += kRowsAtOnce) {
-            for (uint32_t q = tid; q < nq_grp; q += kBlmNormThreads) {
-                f4 v[kRowsAtOnce];
-                uint32_t to[kRowsAtOnce];
-                uint64_t from[kRowsAtOnce];          // float index of the granule (from the 16-byte aligned base of `out`)
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) {
-                    const int rr = rr0 + i < nr ? rr0 + i : nr - 1;
-                    const uint64_t e0 = ((uint64_t)info[4 * rr + 1] << 32) | info[4 * rr];
-                    const uint32_t valid = info[4 * rr + 2];
-                    const uint32_t a = (out_f + static_cast<uint32_t>(e0)) & 3u;
-                    const uint32_t nq = (a + valid + 3) >> 2;
-                    const uint32_t qq = q < nq ? q : (nq ? nq - 1 : 0);
-                    from[i] = valid ? out_f + e0 - a + 4 * qq : 0;       // a row without frames may own no memory at all: the first granule instead
-                    to[i] = static_cast<uint32_t>(rr) * S + 4 * qq;
-                }
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) v[i] = out_base[from[i] >> 2];
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) *reinterpret_cast<f4 *>(tile + to[i]) = v[i];
-            }
-        }
-        __syncthreads();
-        if (tid < nr) {
-            const uint32_t valid = info[4 * tid + 2];
-            const uint32_t a = (out_f + info[4 * tid]) & 3u;
-            MS_PRIO(3);
-            stat[2 * tid] = valid ? blm_row_mean_lds(tile + (size_t)tid * S, a, valid) : 0.0f;
-            MS_PRIO(0);
-        }
-        __syncthreads();
-        {
-            const int r = tid / PP, pt = tid - r * PP;
-            if (r < nr) {
-                const uint32_t valid = info[4 * r + 2];
-                const uint32_t a = (out_f + info[4 * r]) & 3u;
-                const float *row = tile + (size_t)r * S + a;
-                const float mean = stat[2 * r];
-                float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
-                uint32_t k = pt;
-                for (; k + 3 * PP < valid; k += 4 * PP) {
-                    const float c0 = row[k] - mean, c1 = row[k + PP] - mean, c2 = row[k + 2 * PP] - mean, c3 = row[k + 3 * PP] - mean;
-                    a0 += c0 * c0; a1 += c1 * c1; a2 += c2 * c2; a3 += c3 * c3;
-                }
-                for (; k < valid; k += PP) {
-                    const float c = row[k] - mean;
-                    a0 += c * c;
-                }
-                part[r * PP + pt] = (a0 + a1) + (a2 + a3);
-            }
-        }
-        __syncthreads();
-        if (tid < nr) {
-            const float *pp = part + tid * PP;
-            float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
-            int i = 0;
-            for (; i + 3 < PP; i += 4) { q0 += pp[i]; q1 += pp[i + 1]; q2 += pp[i + 2]; q3 += pp[i + 3]; }
-            for (; i < PP; ++i) q0 += pp[i];
-            float denom = static_cast<float>(info[4 * tid + 2]) - 1.0f;
-            denom = denom < 1.0f ? 1.0f : denom;
-            const float sd = __builtin_sqrtf(f32_div_rn((q0 + q1) + (q2 + q3), denom)) + 1e-5f;
-            stat[2 * tid + 1] = f32_div_rn(1.0f, sd);
-        }
-        __syncthreads();
-        for (int rr0 = 0; rr0 < nr; rr0 += kRowsAtOnce) {
-            for (uint32_t q = tid; q < nq_grp; q += kBlmNormThreads) {
-#pragma unroll
-                for (int i = 0; i < kRowsAtOnce; ++i) {
-                    const int rr = rr0 + i < nr ? rr0 + i : nr - 1;
-                    const uint64_t e0 = ((uint64_t)info[4 * rr + 1] << 32) | info[4 * rr];
-                    const uint32_t valid = info[4 * rr + 2], row_w = info[4 * rr + 3];
-                    const uint32_t a = (out_f + static_cast<uint32_t>(e0)) & 3u;
-                    const bool mine = rr0 + i < nr && valid != 0 && 4 * q < a + valid;
-                    const f4 v = *reinterpret_cast<const f4 *>(tile + static_cast<uint32_t>(rr) * S + 4 * q);
-                    const float mean = stat[2 * rr], rsd = stat[2 * rr + 1];
-                    const int c0 = static_cast<int>(4 * q) - static_cast<int>(a);
-                    float o[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const float nv = (o[e] - mean) * rsd;
-                        o[e] = (c0 + e >= 0 && static_cast<uint32_t>(c0 + e) < valid) ? nv : 0.0f;
-                    }
-                    float *g = p.out + e0 + c0;
-                    if (mine) {
-                        if (c0 >= 0 && static_cast<uint32_t>(c0 + 3) < row_w) {
-                            f4 w = {o[0], o[1], o[2], o[3]};
-                            *reinterpret_cast<f4 *>(g) = w;
-                        } else {
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                if (c0 + e >= 0 && static_cast<uint32_t>(c0 + e) < row_w) g[e] = o[e];
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-    }
+    using Out = float;
+    constexpr bool kSplit = false;
+    const float *const src = p.out;
+    Out *const dst = p.out;
+    const uint64_t *const d_src_off = p.d_out_off, *const d_dst_off = p.d_out_off;
+#include "fbank512_norm_ragged_body.inc"
 }
-
 #endif
 
 // CMN (src/fbank.rs:224-233): per clip and mel column subtract the f32 mean over the clip's frames.  The reference's
@@ -1025,135 +761,15 @@ struct CmnParams {
     float *d_means; // not nullptr: write the clip's column means there ([clip][n_mels]) and leave the rows as they are (the split output)
 };
 
-// KEEP IN STEP with cmn_io_kernel (fbank512_kaldi_io_kernels.hpp), the copy that reads the rows from a scratch and writes 16-bit rows: its
-// staging, its fold of the chunks and its tree (CmnTree, above) are this kernel's operation for operation, and the host sizes both with
-// cmn_shape (fbank512.hip).  melspec_fbank_compute_*_io promises that the means of a 16-bit call are those of the f32 rows: a change to
-// the staging, the chunk fold, CmnTree or cmn_shape here is a change there too.
+// in place on f32 rows (or the means alone); cmn_io_kernel (fbank512_kaldi_io_kernels.hpp) includes the same body
 template <int NT>
 __global__ __launch_bounds__(NT) void cmn_kernel(const CmnParams p) {
-    extern __shared__ __attribute__((aligned(16))) float cmn_lds[];
-    const int nm = p.n_mels;
-    const int tid = threadIdx.x;
-    const int R = p.rows_per_chunk;
-    const int nmp = (nm + 3) & ~3;
-    float *mean_s = cmn_lds;                 // [nmp]
-    float *part_s = cmn_lds + nmp;           // the eight run sums of every column: [8][nmp] (staged form) / [8][NT]
-    float *rows = part_s + 8 * (R > 0 ? nmp : NT);
-    for (uint32_t clip = blockIdx.x; clip < p.b.n_clips; clip += gridDim.x) {
-        float *o;
-        uint64_t frames;
-        if (p.b.d_unit_prefix == nullptr) {
-            o = p.b.out + (uint64_t)clip * p.b.out_stride;
-            frames = p.b.frames_per_clip;
-        } else {
-            o = p.b.out + p.b.d_out_off[clip];
-            frames = p.b.d_frames[clip];
-        }
-        if (frames == 0) continue;
-        if (R > 0) {
-            CmnTree tree(frames, part_s + tid, nmp);
-            uint64_t f0 = 0;
-            const bool vec = ((reinterpret_cast<uintptr_t>(o) & 15) == 0) && (nm % 4 == 0);
-            for (;; f0 += R) {
-                const int nr = frames - f0 < (uint64_t)R ? (int)(frames - f0) : R;
-                const float *src = o + f0 * nm;
-                const int total = nr * nm;
-                __syncthreads();                                   // the previous chunk has been folded
-                if (vec) {
-                    // eight 16-byte loads per thread in flight (a plain copy loop leaves one: ~40 memory round trips per chunk)
-                    constexpr int kU = 8;
-                    const int nq = total / 4;
-                    for (int q0 = tid; q0 < nq; q0 += NT * kU) {
-                        f4 v[kU];
-#pragma unroll
-                        for (int k = 0; k < kU; ++k) {
-                            const int q = q0 + k * NT;
-                            v[k] = *reinterpret_cast<const f4 *>(src + 4 * (q < nq ? q : q0));
-                        }
-#pragma unroll
-                        for (int k = 0; k < kU; ++k) {
-                            const int q = q0 + k * NT;
-                            if (q < nq) *reinterpret_cast<f4 *>(rows + 4 * q) = v[k];
-                        }
-                    }
-                } else {
-                    for (int i = tid; i < total; i += NT) rows[i] = src[i];
-                }
-                __syncthreads();
-                if (tid < nm) {
-                    // chunks start at multiples of 4 frames (rows_per_chunk is one): whole units, then the clip's last, partial unit
-                    const float *col = rows + tid;
-                    const uint64_t ub = f0 / 4;
-                    int r = 0;
-                    for (; r + 16 <= nr; r += 16) {
-                        float v[16];
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) v[i] = col[(r + i) * nm];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) tree.unit(ub + (r >> 2) + i, v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-                    }
-                    for (; r + 4 <= nr; r += 4) tree.unit(ub + (r >> 2), col[r * nm], col[(r + 1) * nm], col[(r + 2) * nm], col[(r + 3) * nm]);
-                    if (r < nr)
-                        tree.unit(ub + (r >> 2), col[r * nm], r + 1 < nr ? col[(r + 1) * nm] : 0.0f, r + 2 < nr ? col[(r + 2) * nm] : 0.0f, 0.0f);
-                }
-                if (f0 + nr >= frames) break;
-            }
-            if (tid < nm) mean_s[tid] = f32_div_rn(tree.finish(), (float)frames);
-            __syncthreads();
-            // the last chunk from LDS, the earlier ones from memory
-            const int nr = (int)(frames - f0);
-            const int G = NT / nm;
-            const int g = tid / nm, m = tid - g * nm;
-            if (p.d_means) {
-                if (tid < nm) p.d_means[(uint64_t)clip * nm + tid] = mean_s[tid];
-            } else if (g < G) {
-                const float mean = mean_s[m];
-                for (int r = g; r < nr; r += G) o[(f0 + r) * nm + m] = rows[r * nm + m] - mean;
-                // earlier chunks: 8 rows per thread in flight
-                uint64_t f = g;
-                for (; f + 7 * (uint64_t)G < f0; f += 8 * (uint64_t)G) {
-                    float v[8];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) v[k] = o[(f + k * (uint64_t)G) * nm + m];
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) o[(f + k * (uint64_t)G) * nm + m] = v[k] - mean;
-                }
-                for (; f < f0; f += G) o[f * nm + m] -= mean;
-            }
-            __syncthreads();                                       // mean_s / rows are reused by the next clip
-            continue;
-        }
-        for (int m0 = 0; m0 < nm; m0 += NT) {                 // column chunks when n_mels > NT
-            const int cols = nm - m0 < NT ? nm - m0 : NT;
-            const int G = NT / cols;                           // frame groups per column
-            const int g = tid / cols, m = m0 + tid - g * cols;
-            if (tid < cols) {
-                constexpr int kB = 16;
-                const float *col = o + m0 + tid;
-                CmnTree tree(frames, part_s + tid, NT);
-                uint64_t f = 0;
-                for (; f + kB <= frames; f += kB) {
-                    float v[kB];
-#pragma unroll
-                    for (int i = 0; i < kB; ++i) v[i] = col[(f + i) * nm];
-#pragma unroll
-                    for (int i = 0; i < kB / 4; ++i) tree.unit(f / 4 + i, v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]);
-                }
-                for (; f + 4 <= frames; f += 4) tree.unit(f / 4, col[f * nm], col[(f + 1) * nm], col[(f + 2) * nm], col[(f + 3) * nm]);
-                if (f < frames)
-                    tree.unit(f / 4, col[f * nm], f + 1 < frames ? col[(f + 1) * nm] : 0.0f, f + 2 < frames ? col[(f + 2) * nm] : 0.0f, 0.0f);
-                rows[tid] = f32_div_rn(tree.finish(), (float)frames);
-            }
-            __syncthreads();
-            if (p.d_means) {
-                if (tid < cols) p.d_means[(uint64_t)clip * nm + m0 + tid] = rows[tid];
-            } else if (g < G) {
-                const float mean = rows[tid - g * cols];
-                for (uint64_t f = g; f < frames; f += G) o[f * nm + m] -= mean;
-            }
-            __syncthreads();
-        }
-    }
+    using Out = float;
+    constexpr bool kSplit = false;
+    Out *const dst = p.b.out;
+    const uint64_t *const d_dst_off = p.b.d_out_off;
+    float *const d_means = p.d_means;
+#include "fbank512_cmn_body.inc"
 }
 
 

@@ -119,6 +119,27 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// A grow-only device buffer of an object that its calls use in stream order: a call on another stream first waits for the stream that used
+// the buffer last (growing frees the old buffer: hipFree waits for the device).
+struct StreamBuf {
+    DevBuf buf;
+    hipStream_t last = nullptr;
+    bool used = false;
+    void *p() const { return buf.p; }
+    int ensure(size_t bytes, hipStream_t s) {
+        if (used && last != s) HIP_TRY(hipStreamSynchronize(last));
+        used = true; last = s;
+        return buf.ensure(bytes);
+    }
+    // release with the same wait; `synced`: a stream the caller has just synchronised
+    int release_after(hipStream_t synced) {
+        if (used && last != synced) HIP_TRY(hipStreamSynchronize(last));
+        release();
+        return MELSPEC_OK;
+    }
+    void release() { buf.release(); used = false; last = nullptr; }
+};
+
 template <typename T>
 inline int upload(DevBuf &buf, const std::vector<T> &v) {
     const size_t bytes = v.size() * sizeof(T);
