@@ -33,18 +33,14 @@ template <class T, int FLAVOR, int NSLOTS, class Lens = LensRuntime>
 int launch_fused512(int waves, const FbankFastParams &fp, size_t lds, int cus, hipStream_t s) {
     // frame-major plain output (Kaldi always, Whisper-512 without a layout): a contiguous run of units per wave, 8-wave shape only
     constexpr bool kCanRun = FLAVOR != kFlavorNemo;
-    const bool plain = !fp.b.mel_major && (fp.b.d_unit_prefix != nullptr || fp.b.out_width == fp.b.frames_per_clip);
+    const bool plain = !is_layout(fp.b);
     if constexpr (sizeof(T) == 4) {
         // MELSPEC_PRECISION_F32: the f32 instantiation, twelve waves = three per SIMD (158-168 VGPRs without spills; at sixteen waves the
         // 128-VGPR budget spills 24-38 registers inside the unit loop and the kernel is slower than the f64 one, profiles/r05_fb512_twelve_waves.txt)
         static_assert(Lens::kStatic, "the f32 instantiation exists for the compile-time banks");
-        static std::atomic<uint64_t> attr12{0};
-        if (!device_done(attr12)) {
-            int rc = allow_big_lds(&fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens>, "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)");
-            if (!rc && kCanRun) rc = allow_big_lds(&fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens, kCanRun>, "hipFuncSetAttribute(fbank512_wave_kernel<float>, runs)");
-            if (rc) return rc;
-            mark_device_done(attr12);
-        }
+        static std::atomic<uint64_t> attr12{0};          // (without kCanRun the second kernel is the first again)
+        if (int rc = allow_big_lds_once(attr12, "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)", &fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens>,
+                                        &fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens, kCanRun>)) return rc;
         const unsigned grid12 = grid_for_xcd((fp.b.n_units + 11) / 12, cus, 1);
         if (kCanRun && plain) hipLaunchKernelGGL((fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens, kCanRun>), dim3(grid12), dim3(768), lds, s, fp);
         else hipLaunchKernelGGL((fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens>), dim3(grid12), dim3(768), lds, s, fp);
@@ -53,13 +49,8 @@ int launch_fused512(int waves, const FbankFastParams &fp, size_t lds, int cus, h
     } else {                  // (an else: the f32 instantiation must not instantiate the eight- and four-wave kernels it never launches)
         const bool runs = kCanRun && plain && waves == 8;
         static std::atomic<uint64_t> attr_done{0};          // one bit per device: function attributes are per device
-        if (!device_done(attr_done)) {
-            int rc = allow_big_lds(&fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens>, "hipFuncSetAttribute(fbank512_wave_kernel, 8 waves)");
-            if (!rc) rc = allow_big_lds(&fbank512_wave_kernel<T, 4, 1, FLAVOR, NSLOTS, LensRuntime>, "hipFuncSetAttribute(fbank512_wave_kernel, 4 waves)");
-            if (!rc && kCanRun) rc = allow_big_lds(&fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens, kCanRun>, "hipFuncSetAttribute(fbank512_wave_kernel, runs)");
-            if (rc) return rc;
-            mark_device_done(attr_done);
-        }
+        if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)", &fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens>,
+                                        &fbank512_wave_kernel<T, 4, 1, FLAVOR, NSLOTS, LensRuntime>, &fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens, kCanRun>)) return rc;
         const uint64_t blocks = (fp.b.n_units + waves - 1) / waves;
         static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);   // one workgroup is resident per CU; measured best
         const unsigned grid = grid_for_xcd(blocks, cus, per_cu);
@@ -98,12 +89,7 @@ namespace {
 template <int NSLOTS, class Lens>
 int launch_w512_auto_t(melspec_ctx *c, const FbankFastParams &fp64, const BatchDesc &desc, hipStream_t stream) {
     static std::atomic<uint64_t> attr_done{0};
-    if (!device_done(attr_done)) {
-        int rc = allow_big_lds(&w512_auto_kernel<float, kFused512F32Waves, NSLOTS, Lens>, "hipFuncSetAttribute(w512_auto_kernel<float>)");
-        if (!rc) rc = allow_big_lds(&w512_auto_kernel<double, 8, NSLOTS, Lens>, "hipFuncSetAttribute(w512_auto_kernel<double>)");
-        if (rc) return rc;
-        mark_device_done(attr_done);
-    }
+    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(w512_auto_kernel)", &w512_auto_kernel<float, kFused512F32Waves, NSLOTS, Lens>, &w512_auto_kernel<double, 8, NSLOTS, Lens>)) return rc;
     FixSink sink{};
     int rc = auto_sink(c, desc, stream, true, sink);
     if (rc) return rc;
@@ -140,6 +126,21 @@ bool w512_auto_ok(const melspec_ctx *c) {
            (fb_lens_match<LensSlaney80W>(c->ft512.slots) || fb_lens_match<LensSlaney128>(c->ft512.slots));
 }
 
+// the precision a plain batch of an n_fft = 512 context computes in: F32 where asked for and built, AUTO's voting pair where the bank
+// allows it, else f64
+static int w512_precision(const melspec_ctx *c) {
+    if (c->precision == MELSPEC_PRECISION_F32 && c->f512.ok) return MELSPEC_PRECISION_F32;
+    if (c->precision == MELSPEC_PRECISION_AUTO && c->fix.adaptive && w512_auto_ok(c)) return MELSPEC_PRECISION_AUTO;
+    return MELSPEC_PRECISION_F64;
+}
+const char *whisper512_kernel_name(const melspec_ctx *c) {
+    switch (w512_precision(c)) {
+        case MELSPEC_PRECISION_F32: return "melspec::fbank512_wave_kernel<float, 12, 1, kFlavorWhisper, RUNS> (n_fft = 512, f32, three waves per SIMD)";
+        case MELSPEC_PRECISION_AUTO: return "melspec::w512_auto_kernel<float, 12> (n_fft = 512, f32, precision guard + vote) + the gated melspec::w512_auto_kernel<double, 8>";
+        default: return "melspec::fbank512_wave_kernel<double, 8, 1, kFlavorWhisper, RUNS> (n_fft = 512, f64)";
+    }
+}
+
 // the Whisper flavour of the 512-point kernel: launch_ctx's branch for the n_fft = 512 contexts
 int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream) {
         FbankFastParams fp{};
@@ -151,14 +152,15 @@ int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream)
         fp.n_mels = c->n_mels;
         fp.use_log = 1; fp.use_power = 1;
         fp.slots = c->ft512.slots;
-        if (c->precision == MELSPEC_PRECISION_F32 && c->f512.ok) return launch_w512_f32(c->f512, fp, c->dev.cus, stream);
+        const int mode = w512_precision(c);
+        if (mode == MELSPEC_PRECISION_F32) return launch_w512_f32(c->f512, fp, c->dev.cus, stream);
         // AUTO (round 6): plain batches -- uniform and ragged -- vote like the n_fft = 400 contexts do; the layouts stay on the f64 kernel
-        const bool plain = !desc.mel_major && (desc.d_unit_prefix != nullptr || desc.out_width == desc.frames_per_clip);
+        const bool plain = !is_layout(desc);
         // ... when there is a batch to speak of: below two units per f32 wave of the grid (6144 units = 24 576 frames on an MI355X) a call is
         // launch-bound, the pair of launches is slower than the f64 kernel alone, and the f64 kernel it is (also what keeps the streaming
         // bank's hop-sized pushes on the reference's golden within 1e-6; a rule on the batch's size: still a function of the batch alone)
         const bool sizeable = desc.n_units >= 2ull * kFused512F32Waves * static_cast<unsigned>(c->dev.cus);
-        if (c->precision == MELSPEC_PRECISION_AUTO && c->fix.adaptive && plain && sizeable && w512_auto_ok(c))
+        if (mode == MELSPEC_PRECISION_AUTO && plain && sizeable)
             return fb_lens_match<LensSlaney80W>(c->ft512.slots) ? launch_w512_auto_t<kFbSlots, LensSlaney80W>(c, fp, desc, stream)
                                                                 : launch_w512_auto_t<kBlmSlots, LensSlaney128>(c, fp, desc, stream);
         if (fb_lens_match<LensSlaney80W>(c->ft512.slots)) return launch_fused512<double, kFlavorWhisper, kFbSlots, LensSlaney80W>(c->waves512, fp, c->lds512, c->dev.cus, stream);
@@ -184,15 +186,6 @@ int io_dtypes(int pcm_dtype, int out_dtype, int &io) {
 }
 bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
     return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
-}
-// the LDS attribute of the kernels of a pass, once per device
-template <class... K>
-int allow_big_lds_once(std::atomic<uint64_t> &done, const char *name, K... kernels) {
-    if (device_done(done)) return MELSPEC_OK;
-    int rc = MELSPEC_OK;
-    ((rc = rc ? rc : allow_big_lds(kernels, name)), ...);
-    if (!rc) mark_device_done(done);
-    return rc;
 }
 }  // namespace
 
@@ -415,16 +408,9 @@ static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips
              (reinterpret_cast<uintptr_t>(pl.desc.out) & 15) == 0 && pl.desc.out_stride % 4 == 0 &&
              n_clips >= cus && static_cast<uint64_t>(n_clips) * 100 >= static_cast<uint64_t>(passes) * cus * 85))) {
             static std::atomic<uint64_t> attr_done{0};
-            if (!device_done(attr_done)) {
-                rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensKaldi80>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (!rc) rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensRuntime>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (!rc) rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensKaldi80, true>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (!rc) rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensRuntime, true>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (!rc) rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensKaldi40>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (!rc) rc = allow_big_lds(&fbank512_clip_kernel<kFbSlots, LensKaldi40, true>, "hipFuncSetAttribute(fbank512_clip_kernel)");
-                if (rc) return rc;
-                mark_device_done(attr_done);
-            }
+            if ((rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_clip_kernel)", &fbank512_clip_kernel<kFbSlots, LensKaldi80>, &fbank512_clip_kernel<kFbSlots, LensRuntime>,
+                                         &fbank512_clip_kernel<kFbSlots, LensKaldi80, true>, &fbank512_clip_kernel<kFbSlots, LensRuntime, true>,
+                                         &fbank512_clip_kernel<kFbSlots, LensKaldi40>, &fbank512_clip_kernel<kFbSlots, LensKaldi40, true>))) return rc;
             FbankClipParams q{};
             q.f = fp;
             q.frames = fpc;
@@ -652,14 +638,7 @@ int launch_nemo_io(melspec_blm *b, FbankFastParams fp, int io, hipStream_t s) {
     const int pcm = io & 15, out = io >> 4;
     if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || io == 0 || !blm_io_ok(b)) return fail(MELSPEC_ERR_INTERNAL, "launch_nemo_io: no such combination");
     const NemoIoKernels &k = table[pcm][out];
-    if (!device_done(attr_done[pcm][out])) {
-        int rc = allow_big_lds(k.f64_128, "hipFuncSetAttribute(fbank512_nemo_io_kernel<double, 128 mels>)");
-        if (!rc) rc = allow_big_lds(k.f64_80, "hipFuncSetAttribute(fbank512_nemo_io_kernel<double, 80 mels>)");
-        if (!rc) rc = allow_big_lds(k.f32_128, "hipFuncSetAttribute(fbank512_nemo_io_kernel<float, 128 mels>)");
-        if (!rc) rc = allow_big_lds(k.f32_80, "hipFuncSetAttribute(fbank512_nemo_io_kernel<float, 80 mels>)");
-        if (rc) return rc;
-        mark_device_done(attr_done[pcm][out]);
-    }
+    if (int rc = allow_big_lds_once(attr_done[pcm][out], "hipFuncSetAttribute(fbank512_nemo_io_kernel)", k.f64_128, k.f64_80, k.f32_128, k.f32_80)) return rc;
     const bool wide = fb_lens_match<LensSlaney128>(b->ft.slots);
     if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) {
         f32_params(b->f32, fp);
@@ -1239,10 +1218,7 @@ int launch_kaldi_io(melspec_fbank *fb, const FbankFastParams &fp, int pcm, int o
     static std::atomic<uint64_t> attr_done[2][3];
     if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || (pcm | out) == 0 || !fbank_io_ok(fb)) return fail(MELSPEC_ERR_INTERNAL, "launch_kaldi_io: no such combination");
     const Kernel k = table[pcm][out];
-    if (!device_done(attr_done[pcm][out])) {
-        if (int rc = allow_big_lds(k, "hipFuncSetAttribute(fbank512_kaldi_io_kernel)")) return rc;
-        mark_device_done(attr_done[pcm][out]);
-    }
+    if (int rc = allow_big_lds_once(attr_done[pcm][out], "hipFuncSetAttribute(fbank512_kaldi_io_kernel)", k)) return rc;
     static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);
     const unsigned grid = grid_for_xcd((fp.b.n_units + 7) / 8, fb->dev.cus, per_cu);
     hipLaunchKernelGGL(k, dim3(grid), dim3(512), fb->fast_lds, s, fp);

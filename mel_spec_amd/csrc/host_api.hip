@@ -258,39 +258,9 @@ int melspec_set_precise(melspec_ctx *c, int on) { return melspec_set_precision(c
 int melspec_is_precise(const melspec_ctx *c) { return c && melspec_precision(c) == MELSPEC_PRECISION_F64 ? 1 : 0; }   // the generic kernels are f64 whatever the mode
 
 const char *melspec_plain_kernel_name(const melspec_ctx *c) {
-    // the same decisions launch_ctx takes for a plain (uniform or ragged, [frame][mel]) batch
     if (!c) return "";
-    if (!c->fast) {
-        if (c->fast512 && c->precision == MELSPEC_PRECISION_F32 && c->f512.ok) return "melspec::fbank512_wave_kernel<float, 12, 1, kFlavorWhisper, RUNS> (n_fft = 512, f32, three waves per SIMD)";
-        if (c->precision == MELSPEC_PRECISION_AUTO && c->fix.adaptive && w512_auto_ok(c))
-            return "melspec::w512_auto_kernel<float, 12> (n_fft = 512, f32, precision guard + vote) + the gated melspec::w512_auto_kernel<double, 8>";
-        if (c->fast512) return "melspec::fbank512_wave_kernel<double, 8, 1, kFlavorWhisper, RUNS> (n_fft = 512, f64)";
-        switch (pow2_logm(c->gt)) {
-            case 6: return "melspec::pow2_frame_kernel<6, kFlavorWhisper> (n_fft = 128, f64, frames owned by lane groups of a wave)";
-            case 7: return "melspec::pow2_frame_kernel<7, kFlavorWhisper> (n_fft = 256, f64, frames owned by lane groups of a wave)";
-            case 8: return "melspec::pow2_frame_kernel<8, kFlavorWhisper> (n_fft = 512, f64, frames owned by lane groups of a wave)";
-            case 9: return "melspec::pow2_frame_kernel<9, kFlavorWhisper> (n_fft = 1024, f64, frames owned by lane groups of a wave)";
-            case 10: return "melspec::pow2_frame_kernel<10, kFlavorWhisper> (n_fft = 2048 as two 512-point halves, f64, frames owned by lane groups of a wave)";
-            default: break;
-        }
-        return "melspec::generic_frame_kernel<256> (f64, one frame per workgroup)";
-    }
-    if (c->precision == MELSPEC_PRECISION_F64 && c->six64_wide)
-        return "melspec::whisper400_six64_kernel<15, LensSix128> (f64 FFT, six frames per wave, three waves per SIMD, fifteen mel slots)";
-    if (c->precision == MELSPEC_PRECISION_F64 && c->six64)
-        return "melspec::whisper400_six64_kernel<9, .> (f64 FFT, six frames per wave, three waves per SIMD)";
-    if (c->precision == MELSPEC_PRECISION_F64)
-        return c->ft.slots.n_slots <= 8 ? "melspec::whisper400_precise_kernel<8, ., RUNS> (f64 FFT)" : "melspec::whisper400_precise_kernel<12, ., RUNS> (f64 FFT)";
-    const bool fix = c->precision == MELSPEC_PRECISION_AUTO;
-    if (c->six)
-        return c->six_static == 1 ? (fix ? "melspec::whisper400_six_runs_kernel<9, LensSix80> (precision guard on)" : "melspec::whisper400_six_runs_kernel<9, LensSix80>")
-             : c->six_static == 2 ? (fix ? "melspec::whisper400_six_wide_runs_kernel<9, LensSix64> (twelve waves; precision guard on)" : "melspec::whisper400_six_wide_runs_kernel<9, LensSix64> (twelve waves)")
-             : c->six_static == 3 ? (fix ? "melspec::whisper400_six_wide_runs_kernel<9, LensSix40> (twelve waves; precision guard on)" : "melspec::whisper400_six_wide_runs_kernel<9, LensSix40> (twelve waves)")
-                             : (fix ? "melspec::whisper400_six_runs_kernel<9, LensRuntime> (precision guard on)" : "melspec::whisper400_six_runs_kernel<9, LensRuntime>");
-    if (c->six_wide32) return fix ? "melspec::whisper400_six_wide_runs_kernel<15, LensSix128> (six frames per wave, twelve waves; precision guard on)"
-                                  : "melspec::whisper400_six_wide_runs_kernel<15, LensSix128> (six frames per wave, twelve waves)";
-    if (c->ft.slots.n_slots <= 8) return fix ? "melspec::whisper400_wave_runs_kernel<8, .> (precision guard on)" : "melspec::whisper400_wave_runs_kernel<8, .>";
-    return fix ? "melspec::whisper400_wave_runs_kernel<12, .> (precision guard on)" : "melspec::whisper400_wave_runs_kernel<12, .>";
+    if (c->fast) return route400(ctx_shape(c), BatchKind::kUniform).name;
+    return c->fast512 ? whisper512_kernel_name(c) : generic_kernel_name(c->gt);
 }
 
 int melspec_guard_count(melspec_ctx *c, uint64_t *frames) {

@@ -3,6 +3,7 @@
 //
 //   host_api.hip    the C ABI of melspec_ctx (src/cuda.rs:27-148's CudaMelSpectrogram), the sharded object, table builders, memory helpers
 //   whisper400.hip  launch_ctx: every n_fft = 400 kernel (f32 + guard + vote, f64), the STFT export
+//   ctx_route.hpp   route400: which of them a batch runs on, its unit size and the name reported for it (no HIP: host-testable)
 //   fbank512.hip    the fused 512-point family: Kaldi fbank (melspec_fbank_*), NeMo frontend (melspec_blm_*), Whisper at n_fft = 512
 //   pow2.hip        generic_frame_kernel / pow2_frame_kernel / generic_stft_kernel: every other geometry, f64
 //   aux.hip         batch planners, streaming bank, TGA quantiser, VAD columns, stand-alone mel helpers, synthetic PCM
@@ -37,6 +38,7 @@
 #include "host_pipe.hpp"
 #include "stream_plan.hpp"
 #include "tables.hpp"
+#include "ctx_route.hpp"
 
 namespace melspec {
 namespace host {
@@ -96,6 +98,15 @@ inline uint64_t current_device_bit() {
 // the masks are shared by every context of the process (one context per thread and device is the threading model)
 inline bool device_done(const std::atomic<uint64_t> &mask) { return (mask.load(std::memory_order_acquire) & current_device_bit()) != 0; }
 inline void mark_device_done(std::atomic<uint64_t> &mask) { mask.fetch_or(current_device_bit(), std::memory_order_release); }
+// the LDS attribute of the kernels that share a flag, once per device (at their first launch there)
+template <class... K>
+int allow_big_lds_once(std::atomic<uint64_t> &done, const char *name, K... kernels) {
+    if (device_done(done)) return MELSPEC_OK;
+    int rc = MELSPEC_OK;
+    ((rc = rc ? rc : allow_big_lds(kernels, name)), ...);
+    if (!rc) mark_device_done(done);
+    return rc;
+}
 
 struct DeviceInfo {
     int device = -1;
@@ -276,6 +287,8 @@ inline BatchPlan plan_uniform(const float *d_pcm, float *d_out, uint64_t clip_st
     pl.total_frames = frames_per_clip * n_clips;
     return pl;
 }
+// a padded / mel-major batch (ragged batches: both widths zero)
+inline bool is_layout(const BatchDesc &b) { return b.mel_major || b.out_width != b.frames_per_clip; }
 // Fills the next slot and queues its upload on `stream`.  The caller launches on `stream` and then calls plan_ragged_done.  (aux.hip)
 int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *h_off,
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
@@ -310,8 +323,7 @@ inline unsigned grid_for_xcd(uint64_t units, int cus, int per_cu) {
 }
 
 // ---- pow2.hip: every geometry off the fused kernels -------------------------------------------------------------------------------
-// log2 of the complex transform pow2_frame_kernel would run this geometry with (6..10), or 0: generic_frame_kernel
-int pow2_logm(const GenericTables &gt);
+const char *generic_kernel_name(const GenericTables &gt);          // melspec_plain_kernel_name of the contexts launch_generic serves
 int launch_generic(const GenericTables &gt, const BatchDesc &desc, int hop, int flavour /* 0 Whisper, 1 Kaldi fbank, 2 NeMo */, int use_log, int use_power,
                    double preemph, double floor_v, int cus, hipStream_t stream, long long clip_len = 0, int pad = 0);
 int generic_allow_lds();          // hipFuncSetAttribute(generic_frame_kernel): once per context that runs on it
@@ -462,29 +474,21 @@ int launch_stft(melspec_ctx *c, const BatchDesc &desc, int bins, int dtype, hipS
 int launch_generic_stft(melspec_ctx *c, const BatchDesc &desc, int bins, int dtype, hipStream_t s);
 int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream);
 bool w512_auto_ok(const melspec_ctx *c);
-bool twelve_waves_for(const melspec_ctx *c, bool layout);      // whisper400.hip: the six-frame family's batches that run on twelve waves per CU
+const char *whisper512_kernel_name(const melspec_ctx *c);          // melspec_plain_kernel_name of the n_fft = 512 contexts
 
-// frames per work unit of the kernel a batch is planned for (called once per batch, before it is planned).  AUTO plans for the f32
-// kernel: when the batch's vote says "heavy", the f64 kernel walks the same plan (whisper400_precise_kernel, MODE 2).
-// layout: a padded / mel-major batch (the f64 kernel of the layouts is the five-frame one)
-// The six-frame f64 kernel serves a padded / mel-major batch only with one of the compile-time banks: its run-time-lens layout instantiation
-// keeps 141 SGPRs' worth of slot tables and reloads 13 spilled registers inside the unit loop (tools/hotloop_spills.py); those banks stay
-// on whisper400_precise_kernel's layout form.
-inline bool six64_layout_ok(const melspec_ctx *c) { return c->six64 && !c->six64_wide && c->six_static != 0; }
-
-// int16 PCM in / f16, bf16 rows out: the contexts whose plain batches run the six-frame kernels with one of the compile-time Whisper banks
-// in every precision mode -- 80 mels (whisper400_six_runs_kernel + whisper400_six64_kernel<9, .>) and 128 mels (whisper400_six_wide_runs_kernel
-// + whisper400_six64_kernel<15, .>)
-inline bool ctx_supports_io(const melspec_ctx *c) {
-    return c->fast && c->six64 && ((c->six && c->six_static == 1 && !c->six64_wide) || (!c->six && c->six_wide32 && c->six64_wide));
+// ---- ctx_route.hpp: the n_fft = 400 contexts ---------------------------------------------------------------------------------------
+inline CtxShape ctx_shape(const melspec_ctx *c) {
+    return CtxShape{c->fast, c->six, c->six_static, c->six64, c->six64_wide, c->six_wide32, c->six_wide32_layouts, c->lens_kind, c->ft.slots.n_slots, c->precision, c->fix.adaptive};
 }
+static_assert(kSixFrames == 6 && kFPW == 5, "ctx_route.hpp spells the two unit sizes out");
 
+// int16 PCM in / f16, bf16 rows out (melspec_supports_io): see io_shape_ok
+inline bool ctx_supports_io(const melspec_ctx *c) { return io_shape_ok(ctx_shape(c)); }
+
+// frames per work unit of the kernel a batch is planned for (called once per batch, before it is planned).
+// layout: a padded / mel-major batch
 inline int ctx_frames_per_unit(melspec_ctx *c, bool layout = false) {
-    if (c->fast) {
-        if (c->precision == MELSPEC_PRECISION_F64) return (layout ? six64_layout_ok(c) : c->six64) ? kSixFrames : kFPW;
-        if (c->six_wide32 && (!layout || c->six_wide32_layouts)) return kSixFrames;          // the 128-mel bank: six frames per wave on twelve waves
-        return c->six ? kSixFrames : kFPW;
-    }
+    if (c->fast) return route400(ctx_shape(c), layout ? BatchKind::kLayout : BatchKind::kUniform).frames_per_unit;
     return c->fast512 ? kFbFPW : 1;
 }
 

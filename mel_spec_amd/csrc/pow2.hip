@@ -23,14 +23,10 @@ template <int LOGM, int FLAVOR>
 int launch_pow2(const GenericParams &gp, int cus, hipStream_t stream) {
     using S = Pow2Shape<LOGM>;
     const int waves = pow2_waves<LOGM>(gp.n_jobs, gp.n_mels, gp.n_bins);
-    if (waves == 0) return -1;
+    if (waves == 0) return fail(MELSPEC_ERR_INTERNAL, "launch_pow2: the bank is past the kernel");          // pow2_logm asked
     const size_t lds = sizeof(double) * static_cast<size_t>(pow2_lds<LOGM>(gp.n_jobs, gp.n_mels, waves).total);
     static std::atomic<uint64_t> attr_done{0};
-    if (!device_done(attr_done)) {
-        int rc = allow_big_lds(&pow2_frame_kernel<LOGM, FLAVOR>, "hipFuncSetAttribute(pow2_frame_kernel)");
-        if (rc) return rc;
-        mark_device_done(attr_done);
-    }
+    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(pow2_frame_kernel)", &pow2_frame_kernel<LOGM, FLAVOR>)) return rc;
     const uint64_t groups = (gp.b.n_units + static_cast<uint64_t>(waves) * S::FW - 1) / (static_cast<uint64_t>(waves) * S::FW);
     const unsigned grid = grid_for(groups, cus, 1);
     hipLaunchKernelGGL((pow2_frame_kernel<LOGM, FLAVOR>), dim3(grid), dim3(waves * 64), lds, stream, gp);
@@ -38,8 +34,10 @@ int launch_pow2(const GenericParams &gp, int cus, hipStream_t stream) {
     return MELSPEC_OK;
 }
 
-// log2 of the complex transform pow2_frame_kernel would run this geometry with (6..10), or 0: generic_frame_kernel
-int pow2_logm(const GenericTables &gt) {
+// log2 of the complex transform pow2_frame_kernel runs this geometry with (6..10), or 0: generic_frame_kernel.  Power-of-two frame sizes
+// 128 .. 2048: frames owned by lane groups of a wave; lab builds: MELSPEC_POW2=0 keeps the workgroup-per-frame kernel, which is also the
+// on-device cross-check of the tests (melspec_*_use_generic)
+static int pow2_logm(const GenericTables &gt) {
     static const bool pow2_on = lab_int("MELSPEC_POW2", 1, 0, 1) != 0;
     if (!pow2_on || gt.force_generic) return 0;
     int waves = 0;
@@ -52,6 +50,18 @@ int pow2_logm(const GenericTables &gt) {
         default: break;
     }
     return waves ? gt.fft_log2 - 1 : 0;
+}
+
+// what launch_generic runs a Whisper-flavoured batch of these tables on (melspec_plain_kernel_name)
+const char *generic_kernel_name(const GenericTables &gt) {
+    switch (pow2_logm(gt)) {
+        case 6: return "melspec::pow2_frame_kernel<6, kFlavorWhisper> (n_fft = 128, f64, frames owned by lane groups of a wave)";
+        case 7: return "melspec::pow2_frame_kernel<7, kFlavorWhisper> (n_fft = 256, f64, frames owned by lane groups of a wave)";
+        case 8: return "melspec::pow2_frame_kernel<8, kFlavorWhisper> (n_fft = 512, f64, frames owned by lane groups of a wave)";
+        case 9: return "melspec::pow2_frame_kernel<9, kFlavorWhisper> (n_fft = 1024, f64, frames owned by lane groups of a wave)";
+        case 10: return "melspec::pow2_frame_kernel<10, kFlavorWhisper> (n_fft = 2048 as two 512-point halves, f64, frames owned by lane groups of a wave)";
+        default: return "melspec::generic_frame_kernel<256> (f64, one frame per workgroup)";
+    }
 }
 
 int launch_generic(const GenericTables &gt, const BatchDesc &desc, int hop, int flavour /* 0 Whisper, 1 Kaldi fbank, 2 NeMo */, int use_log, int use_power,
@@ -75,20 +85,15 @@ int launch_generic(const GenericTables &gt, const BatchDesc &desc, int hop, int 
     gp.d_jw = static_cast<const double *>(gt.jw.p);
     gp.d_job = static_cast<const int *>(gt.job.p);
     gp.n_jobs = gt.n_jobs;
-    // power-of-two frame sizes 128 .. 2048: frames owned by lane groups of a wave (pow2_frame_kernel); lab builds: MELSPEC_POW2=0 keeps
-    // the workgroup-per-frame kernel, which is also the on-device cross-check of the tests (melspec_*_use_generic)
-    static const bool pow2_on = lab_int("MELSPEC_POW2", 1, 0, 1) != 0;
-    if (pow2_on && !gt.force_generic && gt.fft_log2 >= 7 && gt.fft_log2 <= 11) {
-        int rc = -1;
+    if (pow2_logm(gt)) {
         switch (gt.fft_log2 * 4 + flavour) {
 #define MS_POW2_CASE(LOG2, LOGM) \
-            case LOG2 * 4 + 0: rc = launch_pow2<LOGM, 0>(gp, cus, stream); break; \
-            case LOG2 * 4 + 1: rc = launch_pow2<LOGM, 1>(gp, cus, stream); break; \
-            case LOG2 * 4 + 2: rc = launch_pow2<LOGM, 2>(gp, cus, stream); break;
+            case LOG2 * 4 + 0: return launch_pow2<LOGM, 0>(gp, cus, stream); \
+            case LOG2 * 4 + 1: return launch_pow2<LOGM, 1>(gp, cus, stream); \
+            case LOG2 * 4 + 2: return launch_pow2<LOGM, 2>(gp, cus, stream);
             MS_POW2_CASE(7, 6) MS_POW2_CASE(8, 7) MS_POW2_CASE(9, 8) MS_POW2_CASE(10, 9) MS_POW2_CASE(11, 10)
 #undef MS_POW2_CASE
         }
-        if (rc >= 0) return rc;          // -1: the bank is wider than the kernel's lanes cover
     }
     const unsigned grid = grid_for(desc.n_units, cus, 8);
     hipLaunchKernelGGL(generic_frame_kernel<kGenericNT>, dim3(grid), dim3(kGenericNT), gt.lds_bytes, stream, gp);
@@ -110,11 +115,7 @@ int launch_generic_stft(melspec_ctx *c, const BatchDesc &desc, int bins, int dty
     const size_t lds = sizeof(double) * (c->gt.plan.n_rad ? 6 : 3) * static_cast<size_t>(c->fft_size);
     if (lds > kLdsLimit) return fail(MELSPEC_ERR_UNSUPPORTED, "geometry needs more LDS than one workgroup has");
     static std::atomic<uint64_t> attr_done{0};
-    if (!device_done(attr_done)) {
-        int rc = allow_big_lds(&generic_stft_kernel<kGenericNT>, "hipFuncSetAttribute(generic_stft_kernel)");
-        if (rc) return rc;
-        mark_device_done(attr_done);
-    }
+    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(generic_stft_kernel)", &generic_stft_kernel<kGenericNT>)) return rc;
     hipLaunchKernelGGL(generic_stft_kernel<kGenericNT>, dim3(grid_for(desc.n_units, c->dev.cus, 8)), dim3(kGenericNT), lds, s, g);
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;

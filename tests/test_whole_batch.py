@@ -8,7 +8,7 @@ padding is exactly 0.0, the gaps between ragged outputs still hold the sentinel 
 Batch sizes are chosen at the edges of the run-per-wave partition of the plain kernels (ClipRun::init, kernels_common.hpp: each of
 grid x waves waves takes a contiguous run of ceil(units / (grid x waves)) units; grid_for_xcd, host_common.hpp): fewer units than
 waves, exactly grid x waves units, k x grid x waves + 1 units, and runs whose boundaries fall inside clips.  The CPU test at the end
-keeps the matrix in step with melspec_plain_kernel_name (host_api.hip): every name it can return has a row here."""
+keeps the matrix in step with melspec_plain_kernel_name (ctx_route.hpp, fbank512.hip, pow2.hip): every name it can return has a row here."""
 import os
 import re
 from concurrent.futures import ThreadPoolExecutor
@@ -669,10 +669,18 @@ def test_auto_state_does_not_leak_into_the_next_batch(gpu, oracle):
 # ---- the matrix against the source (CPU) ------------------------------------------------------------------------------------------
 
 def plain_kernel_name_literals():
-    src = open(os.path.join(ROOT, "mel_spec_amd", "csrc", "host_api.hip")).read()
-    start = src.index("const char *melspec_plain_kernel_name(")
-    body = src[start:src.index("\n}\n", start)]
-    return {s for s in re.findall(r'"((?:[^"\\]|\\.)*)"', body) if s}
+    """the strings melspec_plain_kernel_name hands out: the names of the n_fft = 400 routes (ctx_route.hpp) and of the two families off them"""
+    csrc = os.path.join(ROOT, "mel_spec_amd", "csrc")
+    found = set()
+    for file, heads in (("ctx_route.hpp", ("inline const char *route_name(F32Kernel k, bool guarded) {", "inline const char *route_name(F64Kernel k) {")),
+                        ("fbank512.hip", ("const char *whisper512_kernel_name(const melspec_ctx *c) {",)),
+                        ("pow2.hip", ("const char *generic_kernel_name(const GenericTables &gt) {",))):
+        src = open(os.path.join(csrc, file)).read()
+        for head in heads:
+            start = src.index(head)
+            body = src[start:src.index("\n}\n", start)]
+            found |= {s for s in re.findall(r'"((?:[^"\\]|\\.)*)"', body) if s}
+    return found
 
 
 def test_whole_batch_matrix_names_every_plain_kernel():
