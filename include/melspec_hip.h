@@ -502,6 +502,36 @@ int melspec_blm_compute_ragged_device_io(melspec_blm *b, const void *d_pcm, int 
 /* melspec_blm_compute_host with 16-bit ends: the int16 bytes are what crosses the bus, and so are the 16-bit features. */
 int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
                                 size_t out_capacity_elems, size_t *rows, size_t *cols);
+
+/* ---- split output for this frontend: un-normalised rows + per-feature mean and 1 / std ----------------------------------------------
+ * normalize_per_feature (src/mel.rs:721-749) needs a row's mean and standard deviation, which are known only when the whole clip is
+ * done: the normalised call therefore reads and rewrites every row a second time.  The split call returns what that pass would need
+ * instead -- as melspec_fbank_compute_uniform_device_split does for the CMN -- and leaves (x - mean) * inv_std on the valid columns to a
+ * consumer that can fold it into its own first read.
+ *   d_rows    [clip][n_mels][cols] f32, cols = melspec_blm_padded_frames(clip_len): the un-normalised log-mel rows, zero past the valid
+ *             frames -- the bits melspec_blm_compute_uniform_device writes from a context with the same config, normalize_per_feature
+ *             = 0 and the same precision mode.  The context's own normalize_per_feature does not matter to this call.
+ *   d_mean    [clip][n_mels] f32: the row's mean over its valid frames.
+ *   d_inv_std [clip][n_mels] f32: 1 / (sqrt(var) + 1e-5), var the unbiased variance with the denominator max(valid - 1, 1); one valid
+ *             frame gives var = 0 and inv_std = 1e5, as in the reference.
+ * The statistics are accumulated next to the rows by the mel kernel (per block of 32 or 48 frames counted from the clip's first frame, in
+ * f32 around the block's own mean) and merged per row in f64, rounded once: they are closer to the exact statistics of the returned rows
+ * than the reference's f32 left folds (which the normalised call reproduces), and a function of the clip's samples, its length and the
+ * precision mode only -- not of the clip's place in the batch, the batch's size or what the context ran before.  The partial sums live in
+ * a scratch of the context (grow-only, n_clips * ceil(cols / 32) * n_mels * 8 bytes; melspec_blm_release_scratch gives it back).
+ * What it costs today (1024 x 10 s, profiles/blm_split.txt): in MELSPEC_PRECISION_F32 the call takes 0.79-0.87 x the time of the
+ * normalised call; in the default (f64) mode it is SLOWER than the normalised call (1.15-1.39 x) -- there the call saves the consumer's
+ * own pass over the rows, not time inside this library.  Set the F32 mode where the call is used for speed.
+ * A clip_len without a valid frame returns MELSPEC_OK and writes nothing.  Supported: the fused geometry (n_fft 512 / win_length 400)
+ * with the 80- or 128-mel Slaney bank, both precision modes (melspec_blm_supports_split == 1; the condition of the 16-bit ends); every
+ * other context returns MELSPEC_ERR_UNSUPPORTED, names its geometry in melspec_last_error and touches no buffer.  Uniform batches and
+ * the single host clip only: no ragged form, no 16-bit ends. */
+int melspec_blm_supports_split(const melspec_blm *b);
+int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
+                                             uint32_t n_clips, float *d_rows, float *d_mean, float *d_inv_std, void *stream);
+/* One clip from host memory: rows = [n_mels][cols] (capacity in floats), mean / inv_std = [n_mels]; *n_rows = n_mels, *n_cols = cols. */
+int melspec_blm_compute_host_split(melspec_blm *b, const float *samples, size_t n_samples, float *rows, size_t rows_capacity_floats,
+                                   float *mean, float *inv_std, size_t *n_rows, size_t *n_cols);
 /* Arithmetic of the fused kernel (n_fft 512 / win_length 400, 80 or 128 mels).  MELSPEC_PRECISION_F32: f32 window, FFT, power and
  * projection -- the reference's own arithmetic type for this frontend (src/mel.rs:251-252,356-357), as far from the f64 evaluation of
  * its definition as upstream's f32 code is (2.4e-4 on jfk_f32le.wav) at ~0.8 x the time.  AUTO (default) / F64: f64 up to |X|^2, within 1e-4

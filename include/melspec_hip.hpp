@@ -260,6 +260,30 @@ public:
         return a;
     }
 
+    // additive: the split output (melspec_hip.h) -- un-normalised rows + per-feature mean and 1 / (std + 1e-5); the consumer applies
+    // (x - mean) * inv_std on the valid columns
+    bool supports_split() const { return melspec_blm_supports_split(b_) != 0; }
+    void compute_uniform_device_split(const float *d_pcm, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, float *d_rows,
+                                      float *d_mean, float *d_inv_std, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_uniform_device_split(b_, d_pcm, clip_stride, clip_len, n_clips, d_rows, d_mean, d_inv_std, stream), false);
+    }
+    struct Split {
+        Array2f rows;                      // (n_mels, cols), un-normalised
+        std::vector<float> mean, inv_std;  // (n_mels)
+    };
+    Split compute_split(const std::vector<float> &samples) {
+        Split s;
+        s.rows.rows = n_mels_;
+        s.rows.cols = melspec_blm_padded_frames(b_, samples.size());
+        s.rows.data.assign(s.rows.rows * s.rows.cols, 0.0f);
+        s.mean.assign(n_mels_, 0.0f);
+        s.inv_std.assign(n_mels_, 0.0f);
+        std::size_t rows = 0, cols = 0;
+        detail::check(melspec_blm_compute_host_split(b_, samples.data(), samples.size(), s.rows.data.data(), s.rows.data.size(), s.mean.data(), s.inv_std.data(),
+                                                     &rows, &cols), false);
+        return s;
+    }
+
     // additive: 16-bit ends (MELSPEC_PCM_*, MELSPEC_OUT_* of melspec_hip.h); strides, offsets and lengths count elements
     bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_blm_supports_io(b_, pcm_dtype, out_dtype) != 0; }
     void compute_uniform_device_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_out,

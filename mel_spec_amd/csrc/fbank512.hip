@@ -4,6 +4,8 @@
 #include "host_common.hpp"
 #include "fbank512_io_kernels.hpp"
 #include "fbank512_kaldi_io_kernels.hpp"
+#include "fbank512_stats_kernels.hpp"
+#include "blm_stats_plan.hpp"
 
 namespace melspec {
 // emitted by fbank512_io.hip: the NeMo frontend with int16 PCM in and / or f16, bf16 rows out
@@ -24,6 +26,11 @@ MS_IO_COMBOS(MS_IO_EXTERN)
 #undef MS_IO_EXTERN
 extern template __global__ void cmn_io_kernel<io_f16>(const CmnIoParams);
 extern template __global__ void cmn_io_kernel<io_bf16>(const CmnIoParams);
+// emitted by fbank512_stats.hip: the NeMo frontend's split output (rows + the partials of the row statistics)
+extern template __global__ void fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>(const FbankStatsParams);
+extern template __global__ void fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>(const FbankStatsParams);
+extern template __global__ void fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>(const FbankStatsParams);
+extern template __global__ void fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>(const FbankStatsParams);
 }  // namespace melspec
 
 namespace {
@@ -589,6 +596,8 @@ struct melspec_blm {
     HostPipe pipe;              // melspec_blm_compute_batch_host
     StreamBuf rows32;           // normalize_per_feature with f16 / bf16 rows out: the f32 rows between the mel kernel and the normaliser
                                 //   (n_clips * n_mels * cols * 4 bytes)
+    StreamBuf stats;            // the split output: the per-block partials between the mel kernel and blm_stats_finish_kernel
+                                //   (n_clips * ceil(cols / 32 or 48) * n_mels * 8 bytes)
 };
 
 namespace {
@@ -930,6 +939,7 @@ void melspec_blm_destroy(melspec_blm *b) {
     if (b->dev.device >= 0) (void)hipSetDevice(b->dev.device);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
     b->d_blob.release(); b->f32.d_blob.release(); b->h2d.release(); b->d2h.release(); b->gt.release(); b->ragged.release(); b->aux.release(); b->pipe.release(); b->rows32.release();
+    b->stats.release();
     delete b;
 }
 
@@ -1118,12 +1128,109 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
     return blm_host(b, samples, n_samples, out, out_capacity_elems, rows, cols, io);
 }
 
+// ---- the split output: un-normalised rows + per-feature mean and 1 / (std + 1e-5), see include/melspec_hip.h ----
+// LDS of a stats launch: the mel kernel's, plus the f64 kernel's unit partials
+static bool blm_stats_f32(const melspec_blm *b) { return b->precision == MELSPEC_PRECISION_F32 && b->f32.ok; }
+static size_t blm_stats_lds(const melspec_blm *b) {
+    return blm_stats_f32(b) ? b->f32.lds : b->fast_lds + RoundStats<8>::bytes(b->cfg.n_mels);
+}
+// the contexts whose kernels have the instantiations (blm_io_ok's condition), in the precision mode the context is in
+static bool blm_stats_ok(const melspec_blm *b) { return blm_io_ok(b) && blm_stats_lds(b) <= kLdsLimit; }
+
+int melspec_blm_supports_split(const melspec_blm *b) { return b && blm_stats_ok(b) ? 1 : 0; }
+
+int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
+                                             uint32_t n_clips, float *d_rows, float *d_mean, float *d_inv_std, void *stream) {
+    const uint64_t valid = b ? blm_valid_frames(b, clip_len) : 0, cols = b ? blm_padded(b, valid) : 0;
+    const BlmStatsArgs a = blm_stats_args(b != nullptr, b && blm_stats_ok(b), n_clips, cols, d_pcm, d_rows, d_mean, d_inv_std);
+    if (a.verdict == kBlmStatsDone) return MELSPEC_OK;
+    if (a.verdict == kBlmStatsFail) {
+        if (a.msg) return fail(a.status, a.msg);
+        g_last_error = "the split output (rows + per-feature mean and 1 / std) is computed by the n_fft = 512 / win_length = 400 frontend with the 80- or 128-mel Slaney bank only; "
+                       "this context is n_fft = " + std::to_string(b->cfg.n_fft) + ", win_length = " + std::to_string(b->cfg.win_length) + ", n_mels = " +
+                       std::to_string(b->cfg.n_mels) + (b->fast ? " (another filterbank)" : "");
+        return a.status;
+    }
+    const int nm = b->cfg.n_mels;
+    const bool f32 = blm_stats_f32(b);
+    BlmStatsPlan sp;
+    if (!blm_stats_plan(cols, n_clips, nm, f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
+    int rc;
+    if ((rc = b->stats.ensure(static_cast<size_t>(sp.part_bytes) + 16, s))) return rc;
+    // the raw call's batch (blm_uniform with normalize_per_feature off), every clip's units rounded up to whole rounds of the workgroup
+    BatchPlan pl = plan_uniform(d_pcm, d_rows, clip_stride, valid, n_clips, nm, kFbFPW, cols, true);
+    pl.desc.units_per_clip = sp.units_per_clip;
+    pl.desc.n_units = sp.n_units;
+    FbankStatsParams q{};
+    q.f = blm_fast_params(b, pl.desc);
+    q.f.b.sync_rounds = f32 ? 0 : kNemoSync;          // as the raw call: StagedRows instead of RoundSync (f32), the f64 kernel's measured best, which is none
+    q.f.clip_len = static_cast<long long>(clip_len);
+    q.d_part = static_cast<float2 *>(b->stats.p());
+    q.blocks_per_clip = sp.blocks_per_clip;
+    const bool wide = fb_lens_match<LensSlaney128>(b->ft.slots);
+    static std::atomic<uint64_t> attr_done{0};
+    if ((rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_nemo_stats_kernel)", &fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>,
+                                 &fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>, &fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>,
+                                 &fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>))) return rc;
+    const unsigned grid = grid_for_xcd(sp.n_units / sp.waves, b->dev.cus, 1);
+    const size_t lds = blm_stats_lds(b);
+    if (f32) {
+        f32_params(b->f32, q.f);
+        if (wide) hipLaunchKernelGGL((fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>), dim3(grid), dim3(kFused512F32Waves * 64), lds, s, q);
+        else hipLaunchKernelGGL((fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>), dim3(grid), dim3(kFused512F32Waves * 64), lds, s, q);
+    } else {
+        if (wide) hipLaunchKernelGGL((fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>), dim3(grid), dim3(512), lds, s, q);
+        else hipLaunchKernelGGL((fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>), dim3(grid), dim3(512), lds, s, q);
+    }
+    HIP_TRY(hipGetLastError());
+    BlmStatsFinishParams fq{};
+    fq.part = q.d_part; fq.mean = d_mean; fq.inv_std = d_inv_std; fq.valid = valid;
+    fq.n_clips = n_clips; fq.blocks_per_clip = sp.blocks_per_clip; fq.block_frames = sp.block_frames; fq.n_mels = nm;
+    const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+    hipLaunchKernelGGL(blm_stats_finish_kernel, dim3(grid_for((rows + kBlmStatsFinishThreads - 1) / kBlmStatsFinishThreads, b->dev.cus, 8)), dim3(kBlmStatsFinishThreads), 0, s, fq);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+// One clip from host memory; the rows and the two statistics share the context's device-to-host buffer.
+int melspec_blm_compute_host_split(melspec_blm *b, const float *samples, size_t n_samples, float *rows, size_t rows_capacity_floats,
+                                   float *mean, float *inv_std, size_t *n_rows, size_t *n_cols) {
+    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
+    if (n_rows) *n_rows = static_cast<size_t>(b->cfg.n_mels);
+    if (n_cols) *n_cols = 0;
+    const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
+    const uint64_t nm = static_cast<uint64_t>(b->cfg.n_mels), need = c * nm;
+    if (blm_stats_ok(b) && c != 0) {        // (an unsupported context: the device call words the error)
+        if (!samples || !rows) return fail(MELSPEC_ERR_INVALID_ARG, "samples/rows is NULL");
+        if (!mean || !inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "mean / inv_std is NULL");
+        if (rows_capacity_floats < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+        HIP_TRY(hipSetDevice(b->dev.device));
+        int rc;
+        if ((rc = b->h2d.ensure(n_samples * sizeof(float)))) return rc;
+        if ((rc = b->d2h.ensure((need + 2 * nm) * sizeof(float)))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    }
+    float *d_rows = static_cast<float *>(b->d2h.p);
+    const int rc = melspec_blm_compute_uniform_device_split(b, static_cast<const float *>(b->h2d.p), n_samples, n_samples, 1, d_rows, d_rows ? d_rows + need : nullptr,
+                                                            d_rows ? d_rows + need + nm : nullptr, b->stream);
+    if (rc || c == 0) return rc;
+    HIP_TRY(hipMemcpyAsync(rows, d_rows, need * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(mean, d_rows + need, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(inv_std, d_rows + need + nm, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (n_cols) *n_cols = static_cast<size_t>(c);
+    return MELSPEC_OK;
+}
+
 int melspec_blm_release_scratch(melspec_blm *b) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     HIP_TRY(hipSetDevice(b->dev.device));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (int rc = b->aux.release_after(b->stream)) return rc;
     if (int rc = b->rows32.release_after(b->stream)) return rc;
+    if (int rc = b->stats.release_after(b->stream)) return rc;
     b->pipe.release(); b->ragged.release(); b->h2d.release(); b->d2h.release();
     return MELSPEC_OK;
 }

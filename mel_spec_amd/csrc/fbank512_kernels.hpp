@@ -107,6 +107,12 @@ struct StagedRows {
     // a wave's unit of this round (every lane calls; vals: this lane's mel j + 15 i of frame fl, zero for a column past the valid frames)
     template <int NSLOTS>
     __device__ __forceinline__ void put(int wave, int lane, const float (&vals)[NSLOTS], Out *col, long long row_w, int ns) {
+        stage<NSLOTS>(wave, lane, vals, col, row_w, ns);
+        publish(lane);
+    }
+    // put's two halves (fbank512_nemo_stats_kernel drains the previous round between them): the wave's unit into the image ...
+    template <int NSLOTS>
+    __device__ __forceinline__ void stage(int wave, int lane, const float (&vals)[NSLOTS], Out *col, long long row_w, int ns) const {
         const int l = fresh_lane_value(lane), fl = l / kFbLanes, j = l - fl * kFbLanes;      // derived here, not held across the unit loop
         float *mine = image + (round & 1u) * image_floats(n_mels) + j * kPitch + (wave << 2) + fl;
         if (j < kFbOwn) {
@@ -115,6 +121,9 @@ struct StagedRows {
                 if (j + kFbOwn * i < n_mels) mine[i * kFbOwn * kPitch] = vals[i];
         }
         if (lane == 0) info[(round & 1u) * WAVES + wave] = UnitInfo{col, row_w, ns, 0};
+    }
+    // ... and the count that tells the other waves so
+    __device__ __forceinline__ void publish(int lane) {
         __builtin_amdgcn_wave_barrier();
         if (lane == 0) __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         ++round;

@@ -1,6 +1,8 @@
 // fbank512_wave_body.inc -- the body of fbank512_wave_kernel (fbank512_kernels.hpp), included once per kernel that has it: the kernel itself
 // (MS_FB512_IN = MS_FB512_OUT = float), fbank512_nemo_io_kernel (fbank512_io_kernels.hpp: int16 samples in, f16 / bf16 rows out, NeMo
 // flavour) and fbank512_kaldi_io_kernel (fbank512_kaldi_io_kernels.hpp: the same ends, Kaldi flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
+// MS_FB512_STATS (fbank512_nemo_stats_kernel, fbank512_stats_kernels.hpp: NeMo flavour, parameter q around p): the per-block partials of the
+// split output next to the rows; without the macro the text below is what it always was.
     using L = FbankLayout<T>;
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
     const int tid = threadIdx.x;
@@ -39,6 +41,22 @@
     if (RUNS && !cr.init(p.b, (uint64_t)xcd_logical_block() * WAVES + wave, (uint64_t)gridDim.x * WAVES)) return;
     RoundSync<WAVES> rs((ROUNDS && !STAGE) ? p.b.sync_rounds : 0, wave, arrive);
     StagedRows<STAGE ? WAVES : 4, MS_FB512_OUT> staged(arrive + 16, arrive + 15, p.n_mels);
+#ifdef MS_FB512_STATS
+    static_assert(FLAVOR == kFlavorNemo && !RUNS, "the partials are the NeMo flavour's");
+    // f32: the block of the round that is drained next (this wave's previous round); f64: the waves' unit partials where the f32 kernel has
+    // its images, counters arrive[8], [9]
+    using SStats = StagedStats<STAGE ? WAVES : 4>;
+    // the round's block of the batch, clip * blocks_per_clip + block = first / WAVES (the plan keeps it in 32 bits): counted, not divided
+    uint32_t sblock = xcd_logical_block();
+    // the partials of the round before this one (its image has just been drained)
+    auto sreduce = [&](unsigned r, int t) __attribute__((always_inline)) {
+        const uint32_t sprev = sblock - gridDim.x, blk = sprev % q.blocks_per_clip;
+        const uint64_t bf0 = (uint64_t)blk * (WAVES * kFbFPW), vf = p.b.frames_per_clip;
+        const int n = vf > bf0 ? (vf - bf0 < (uint64_t)(WAVES * kFbFPW) ? (int)(vf - bf0) : WAVES * kFbFPW) : 0;
+        SStats::reduce(staged, r, t, q.d_part + (uint64_t)sprev * (uint64_t)p.n_mels, n);
+    };
+    RoundStats<WAVES> rstats(arrive + 16, arrive + 8, p.n_mels);
+#endif
     // batches planned on the device (plan_ragged_device_kernel) keep the real unit count in d_n_units; n_units is the host's bound
     const uint64_t n_units = RUNS ? 0 : scalar64(batch_n_units(p.b));
     // (STAGE with a contiguous range of units per workgroup instead of rounds dealt over the grid -- consecutive rounds extending the same
@@ -119,12 +137,36 @@
                 w512_phase4<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, slice_f, vals, loc.out + f0 * (uint64_t)p.n_mels, 0);
         } else {
             const uint64_t row_w = p.b.d_unit_prefix == nullptr ? p.b.out_width : loc.frames;
+#ifdef MS_FB512_STATS
+            const uint64_t wleft = (have && f0 < row_w) ? row_w - f0 : 0;      // the clip's units are rounded up to whole rounds: some lie past the row
+            // the round's block (computed where it is used, by the one wave that uses it): WAVES units from unit blk * WAVES of the clip on,
+            // nb valid frames, its partials at pdst
+#define MS_FB512_STATS_BLOCK                                                                                                             \
+            const uint64_t blk = loc.unit / WAVES, bf0 = blk * (WAVES * kFbFPW);                                                         \
+            const int nb = vframes > bf0 ? (vframes - bf0 < (uint64_t)(WAVES * kFbFPW) ? (int)(vframes - bf0) : WAVES * kFbFPW) : 0;     \
+            float2 *const pdst = q.d_part + ((uint64_t)loc.clip * q.blocks_per_clip + blk) * (uint64_t)p.n_mels;
+#else
             const uint64_t wleft = have ? row_w - f0 : 0;
+#endif
             const int ns = wleft < (uint64_t)kFbFPW ? (int)wleft : kFbFPW;
             if (STAGE) {
                 float vals[NSLOTS];
 #pragma unroll
-                for (int i = 0; i < NSLOTS; ++i) vals[i] = act ? fast_ln((rise[i] + fnext[i]) + p.floor_v) : 0.0f;     // nemo_phase3_store's value
+                for (int i = 0; i < NSLOTS; ++i) vals[i] = act ? fast_ln((rise[i] + fnext[i]) + p.floor_v) : 0.0f;
+#ifdef MS_FB512_STATS
+                // the unit goes into its image first and the previous round is drained behind it, when the unit's values are out of the
+                // registers (the reduction of the drained block needs them); the count is raised last: a wave that sees every wave's count for
+                // round r knows that each has drained round r - 1, as it does without the partials
+                if (staged.round > 0) staged.wait_staged(staged.round, lane);
+                staged.template stage<NSLOTS>(wave, lane, vals, loc.out + f0, (long long)row_w, ns);
+                if (staged.round > 0) {
+                    int dtid = tid;
+                    asm volatile("" : "+v"(dtid));          // see StagedRows::drain
+                    staged.drain(staged.round - 1, dtid);
+                    sreduce(staged.round - 1, dtid);
+                }
+                staged.publish(lane);
+#else
                 if (staged.round > 0) {
                     int dtid = tid;
                     asm volatile("" : "+v"(dtid));          // see StagedRows::drain
@@ -132,16 +174,55 @@
                     staged.drain(staged.round - 1, dtid);
                 }
                 staged.template put<NSLOTS>(wave, lane, vals, loc.out + f0, (long long)row_w, ns);
+#endif
             } else {
                 rs.template before_stores<2>(lane);
+#ifndef MS_FB512_STATS
                 nemo_phase3_store<NSLOTS>(fl, j, in && fl < ns, act, p.n_mels, p.floor_v, rise, fnext, loc.out + f0, (long long)row_w);
+#else
+                {
+                    // nemo_phase3_store's values, computed ONCE for the rows and the partials: a second use of rise[i] keeps the compiler from
+                    // contracting a one-bin interval's product into this sum the way the raw kernel's only use lets it, and the rows of the
+                    // 128-mel bank (three such slots) then differ from the raw call's in the last place
+                    float vals[NSLOTS];
+#pragma unroll
+                    for (int i = 0; i < NSLOTS; ++i) vals[i] = act ? fast_ln((rise[i] + fnext[i]) + p.floor_v) : 0.0f;
+                    nemo_store_vals<NSLOTS>(fl, j, in && fl < ns, p.n_mels, vals, loc.out + f0, (long long)row_w);
+                    // the unit's partial per mel row {c, squares around c} of its valid frames' values; c = the first frame's value + the mean
+                    // distance from it (fbank512_stats_kernels.hpp says why)
+                    rstats.wait_free(lane);
+                    const float inv_nv = nv == 4 ? 0.25f : nv == 3 ? 0.333333343f : nv == 2 ? 0.5f : 1.0f;
+                    float2 *mine = rstats.part + wave * p.n_mels + j;
+#pragma unroll
+                    for (int i = 0; i < NSLOTS; ++i) {
+                        const float v = vals[i];
+                        const float first = stats_sum_frames(lane < kFbLanes ? v : 0.0f);
+                        const float d = act ? v - first : 0.0f;
+                        const float shift = f32_mul_rn(stats_sum_frames(d), inv_nv);
+                        const float e = act ? d - shift : 0.0f;
+                        const float sq = stats_sum_frames(f32_mul_rn(e, e));
+                        if (lane < kFbOwn && j + kFbOwn * i < p.n_mels) mine[kFbOwn * i] = make_float2(first + shift, sq);
+                    }
+                    MS_FB512_STATS_BLOCK
+                    rstats.arrive(lane, pdst, nb);
+                }
+#endif
             }
         }
+#ifdef MS_FB512_STATS
+#undef MS_FB512_STATS_BLOCK
+#endif
         __builtin_amdgcn_wave_barrier();
         if (ROUNDS) rs.after_round();
         if (RUNS) ++cr.unit;
+#ifdef MS_FB512_STATS
+        sblock += gridDim.x;
+#endif
     }
     if (STAGE && staged.round > 0) {
         staged.wait_staged(staged.round, lane);
         staged.drain(staged.round - 1, tid);
+#ifdef MS_FB512_STATS
+        sreduce(staged.round - 1, tid);
+#endif
     }

@@ -751,6 +751,28 @@ class BatchLogMelSpectrogram:
         _check(lib().melspec_blm_compute_uniform_device(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
                                                         C.c_void_p(d_out), C.c_void_p(stream)))
 
+    # -- split output: un-normalised rows + per-feature mean and 1 / (std + 1e-5) (melspec_hip.h) ---------------------------------------
+    def supports_split(self) -> bool:
+        return bool(lib().melspec_blm_supports_split(self._h))
+
+    def compute_uniform_device_split(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int, d_mean: int, d_inv_std: int,
+                                     stream: int = 0) -> None:
+        """compute_uniform_device without the normaliser's second pass: d_rows = [clip][n_mels][cols] un-normalised rows, d_mean /
+        d_inv_std = [clip][n_mels]; the consumer applies (x - mean) * inv_std on the valid columns."""
+        _check(lib().melspec_blm_compute_uniform_device_split(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips, C.c_void_p(d_rows),
+                                                              C.c_void_p(d_mean), C.c_void_p(d_inv_std), C.c_void_p(stream)))
+
+    def compute_split(self, samples):
+        """One host clip -> (rows (n_mels, cols), mean (n_mels,), inv_std (n_mels,)): melspec_blm_compute_host_split."""
+        x = _f32(samples).reshape(-1)
+        cols = self.padded_frames(x.shape[0])
+        nm = self.config.n_mels
+        rows, mean, inv_std = np.zeros((nm, cols), np.float32), np.zeros(nm, np.float32), np.zeros(nm, np.float32)
+        r, c = C.c_size_t(0), C.c_size_t(0)
+        _check(lib().melspec_blm_compute_host_split(self._h, _fp(x), x.shape[0], _fp(rows), rows.size, _fp(mean), _fp(inv_std), C.byref(r), C.byref(c)))
+        assert r.value == nm and c.value == cols
+        return rows, mean, inv_std
+
     # -- 16-bit ends: int16 PCM in, f16 / bf16 features out (melspec_hip.h; codes PCM_* / OUT_* of this module) ------------------------
     def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
         return bool(lib().melspec_blm_supports_io(self._h, int(pcm_dtype), int(out_dtype)))

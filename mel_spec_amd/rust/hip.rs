@@ -86,6 +86,11 @@ unsafe extern "C" {
     fn melspec_blm_padded_frames(b: *const BlmHandle, n: usize) -> usize;
     fn melspec_blm_num_frames(b: *const BlmHandle, n: usize) -> usize;
     fn melspec_blm_compute_host(b: *mut BlmHandle, samples: *const f32, n: usize, out: *mut f32, cap: usize, rows: *mut usize, cols: *mut usize) -> c_int;
+    fn melspec_blm_supports_split(b: *const BlmHandle) -> c_int;
+    fn melspec_blm_compute_uniform_device_split(b: *mut BlmHandle, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, d_rows: *mut f32,
+                                                d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_host_split(b: *mut BlmHandle, samples: *const f32, n_samples: usize, rows: *mut f32, rows_capacity_floats: usize,
+                                      mean: *mut f32, inv_std: *mut f32, n_rows: *mut usize, n_cols: *mut usize) -> c_int;
     fn melspec_blm_supports_io(b: *const BlmHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
     fn melspec_blm_compute_uniform_device_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
                                              d_out: *mut c_void, out_dtype: c_int, stream: *mut c_void) -> c_int;
@@ -743,6 +748,32 @@ impl HipBatchLogMel {
             return Err(HipError::Runtime(last_error()));
         }
         Ok((ndarray::Array2::from_shape_vec((self.n_mels, got_cols), flat).expect("shape"), valid))
+    }
+    /// Additive: does this frontend compute the split output (un-normalised rows + per-feature mean and `1 / (std + 1e-5)`)?
+    pub fn supports_split(&self) -> bool {
+        unsafe { melspec_blm_supports_split(self.b) != 0 }
+    }
+    /// Additive: equal-length clips resident in device memory -> un-normalised rows `[clip][n_mels][cols]` plus `[clip][n_mels]` means and
+    /// inverse standard deviations of `normalize_per_feature` (src/mel.rs:721-749); the consumer applies `(x - mean) * inv_std`.
+    ///
+    /// # Safety
+    /// `d_pcm` must be a device pointer valid for `n_clips * clip_stride` samples, `d_rows` for `n_clips * n_mels * cols` floats, `d_mean`
+    /// and `d_inv_std` for `n_clips * n_mels` floats each.
+    pub unsafe fn compute_uniform_device_split(&mut self, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, d_rows: *mut f32,
+                                               d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_blm_compute_uniform_device_split(self.b, d_pcm, clip_stride, clip_len, n_clips, d_rows, d_mean, d_inv_std, stream))
+    }
+    /// Additive: `compute` without the normaliser's pass: `(rows (n_mels, cols), mean, inv_std)` of one host clip.
+    pub fn compute_split(&mut self, samples: &[f32]) -> Result<(ndarray::Array2<f32>, Vec<f32>, Vec<f32>), HipError> {
+        let cols = unsafe { melspec_blm_padded_frames(self.b, samples.len()) };
+        let mut flat = vec![0.0f32; self.n_mels * cols];
+        let (mut mean, mut inv_std) = (vec![0.0f32; self.n_mels], vec![0.0f32; self.n_mels]);
+        let (mut rows, mut got_cols) = (0usize, 0usize);
+        check(unsafe {
+            melspec_blm_compute_host_split(self.b, samples.as_ptr(), samples.len(), flat.as_mut_ptr(), flat.len(), mean.as_mut_ptr(), inv_std.as_mut_ptr(),
+                                           &mut rows, &mut got_cols)
+        })?;
+        Ok((ndarray::Array2::from_shape_vec((self.n_mels, got_cols), flat).expect("shape"), mean, inv_std))
     }
     /// Additive: does this frontend take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` features (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?
     pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
