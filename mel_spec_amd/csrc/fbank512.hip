@@ -8,172 +8,165 @@
 #include "blm_stats_plan.hpp"
 
 namespace melspec {
-// emitted by fbank512_io.hip: the NeMo frontend with int16 PCM in and / or f16, bf16 rows out
-#define MS_IO_EXTERN(In, Out)                                                                                                       \
-    extern template __global__ void fbank512_nemo_io_kernel<double, 8, kBlmSlots, LensSlaney128, In, Out>(const FbankFastParams);  \
-    extern template __global__ void fbank512_nemo_io_kernel<double, 8, kFbSlots, LensSlaney80, In, Out>(const FbankFastParams);    \
-    extern template __global__ void fbank512_nemo_io_kernel<float, 12, kBlmSlots, LensSlaney128, In, Out>(const FbankFastParams);  \
-    extern template __global__ void fbank512_nemo_io_kernel<float, 12, kFbSlots, LensSlaney80, In, Out>(const FbankFastParams);
-MS_IO_COMBOS(MS_IO_EXTERN)
+// emitted by fbank512_io.hip / fbank512_kaldi_io.hip: the NeMo frontend and the Kaldi fbank with int16 PCM in and / or f16, bf16 rows out
+#define MS_IO_EXTERN(name, In, Out, fam, T, W, N, L) extern template __global__ void fbank512_##fam##_io_kernel<T, W, N, L, In, Out>(const FbankFastParams);
+MS_K512_IO(MS_IO_EXTERN)
 #undef MS_IO_EXTERN
 extern template __global__ void blm_normalize_io_kernel<io_f16>(const BlmNormIoParams);
 extern template __global__ void blm_normalize_io_kernel<io_bf16>(const BlmNormIoParams);
 extern template __global__ void blm_normalize_ragged_io_kernel<io_f16>(const BlmNormRaggedIoParams);
 extern template __global__ void blm_normalize_ragged_io_kernel<io_bf16>(const BlmNormRaggedIoParams);
-// emitted by fbank512_kaldi_io.hip: the Kaldi fbank with the same 16-bit ends
-#define MS_IO_EXTERN(In, Out) extern template __global__ void fbank512_kaldi_io_kernel<double, 8, kFbSlots, LensKaldi80, In, Out>(const FbankFastParams);
-MS_IO_COMBOS(MS_IO_EXTERN)
-#undef MS_IO_EXTERN
 extern template __global__ void cmn_io_kernel<io_f16>(const CmnIoParams);
 extern template __global__ void cmn_io_kernel<io_bf16>(const CmnIoParams);
 // emitted by fbank512_stats.hip: the NeMo frontend's split output (rows + the partials of the row statistics)
-extern template __global__ void fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>(const FbankStatsParams);
-extern template __global__ void fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>(const FbankStatsParams);
-extern template __global__ void fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>(const FbankStatsParams);
-extern template __global__ void fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>(const FbankStatsParams);
+#define MS_STATS_EXTERN(name, T, W, N, L) extern template __global__ void fbank512_nemo_stats_kernel<T, W, N, L>(const FbankStatsParams);
+MS_K512_STATS(MS_STATS_EXTERN)
+#undef MS_STATS_EXTERN
 }  // namespace melspec
 
 namespace {
-// Lens: compile-time slot lengths when the context's filterbank is one of the default banks (8-wave shape only; the
-// 4-wave fallback for oversized tables keeps the run-time loop)
-template <class T, int FLAVOR, int NSLOTS, class Lens = LensRuntime>
-int launch_fused512(int waves, const FbankFastParams &fp, size_t lds, int cus, hipStream_t s) {
-    // frame-major plain output (Kaldi always, Whisper-512 without a layout): a contiguous run of units per wave, 8-wave shape only
-    constexpr bool kCanRun = FLAVOR != kFlavorNemo;
-    const bool plain = !is_layout(fp.b);
-    if constexpr (sizeof(T) == 4) {
-        // MELSPEC_PRECISION_F32: the f32 instantiation, twelve waves = three per SIMD (158-168 VGPRs without spills; at sixteen waves the
-        // 128-VGPR budget spills 24-38 registers inside the unit loop and the kernel is slower than the f64 one, profiles/r05_fb512_twelve_waves.txt)
-        static_assert(Lens::kStatic, "the f32 instantiation exists for the compile-time banks");
-        static std::atomic<uint64_t> attr12{0};          // (without kCanRun the second kernel is the first again)
-        if (int rc = allow_big_lds_once(attr12, "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)", &fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens>,
-                                        &fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens, kCanRun>)) return rc;
-        const unsigned grid12 = grid_for_xcd((fp.b.n_units + 11) / 12, cus, 1);
-        if (kCanRun && plain) hipLaunchKernelGGL((fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens, kCanRun>), dim3(grid12), dim3(768), lds, s, fp);
-        else hipLaunchKernelGGL((fbank512_wave_kernel<T, 12, 1, FLAVOR, NSLOTS, Lens>), dim3(grid12), dim3(768), lds, s, fp);
-        HIP_TRY(hipGetLastError());
-        return MELSPEC_OK;
-    } else {                  // (an else: the f32 instantiation must not instantiate the eight- and four-wave kernels it never launches)
-        const bool runs = kCanRun && plain && waves == 8;
-        static std::atomic<uint64_t> attr_done{0};          // one bit per device: function attributes are per device
-        if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)", &fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens>,
-                                        &fbank512_wave_kernel<T, 4, 1, FLAVOR, NSLOTS, LensRuntime>, &fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens, kCanRun>)) return rc;
-        const uint64_t blocks = (fp.b.n_units + waves - 1) / waves;
-        static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);   // one workgroup is resident per CU; measured best
-        const unsigned grid = grid_for_xcd(blocks, cus, per_cu);
-        if (runs)
-            hipLaunchKernelGGL((fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens, kCanRun>), dim3(grid), dim3(512), lds, s, fp);
-        else if (waves == 8)
-            hipLaunchKernelGGL((fbank512_wave_kernel<T, 8, 1, FLAVOR, NSLOTS, Lens>), dim3(grid), dim3(512), lds, s, fp);
-        else
-            hipLaunchKernelGGL((fbank512_wave_kernel<T, 4, 1, FLAVOR, NSLOTS, LensRuntime>), dim3(grid), dim3(256), lds, s, fp);
-        HIP_TRY(hipGetLastError());
-        return MELSPEC_OK;
+// ---- the kernel behind every K512 (the lists of fused512_route.hpp), by parameter struct; one launcher for them all ----------------------
+// MELSPEC_PRECISION_F32: twelve waves = three per SIMD (158-168 VGPRs without spills; at sixteen waves the 128-VGPR budget spills 24-38
+// registers inside the unit loop and the kernel is slower than the f64 one, profiles/r05_fb512_twelve_waves.txt)
+#define MS_WAVE(name, T, W, F, N, L, R)                                                                                     \
+    static_assert(sizeof(T) == 8 ? (W == 8 || (W == 4 && !L::kStatic)) : (W == kFused512F32Waves && L::kStatic),            \
+                  "the f32 instantiation exists for the compile-time banks, the four-wave one for run-time slot lengths");
+MS_K512_WAVE(MS_WAVE)
+#undef MS_WAVE
+#define MS_WAVE(name, T, W, F, N, L, R) &fbank512_wave_kernel<T, W, 1, kFlavor##F, N, L, R>,
+#define MS_IO(name, In, Out, fam, T, W, N, L) &fbank512_##fam##_io_kernel<T, W, N, L, In, Out>,
+#define MS_CLIP(name, N, L, R) &fbank512_clip_kernel<N, L, R>,
+#define MS_STATS(name, T, W, N, L) &fbank512_nemo_stats_kernel<T, W, N, L>,
+#define MS_AUTO(name, T, W, N, L) &w512_auto_kernel<T, W, N, L>,
+void (*const kFastKernels[])(const FbankFastParams) = {MS_K512_WAVE(MS_WAVE) MS_K512_IO(MS_IO)};
+void (*const kClipKernels[])(const FbankClipParams) = {MS_K512_CLIP(MS_CLIP)};
+void (*const kStatsKernels[])(const FbankStatsParams) = {MS_K512_STATS(MS_STATS)};
+void (*const kAutoKernels[])(const W512AutoParams) = {MS_K512_AUTO(MS_AUTO)};
+#undef MS_WAVE
+#undef MS_IO
+#undef MS_CLIP
+#undef MS_STATS
+#undef MS_AUTO
+constexpr int idx(K512 k) { return static_cast<int>(k); }
+static_assert(sizeof(kFastKernels) / sizeof(kFastKernels[0]) == idx(K512::kClip80) && sizeof(kClipKernels) / sizeof(kClipKernels[0]) == idx(K512::kStats128) - idx(K512::kClip80) &&
+              sizeof(kStatsKernels) / sizeof(kStatsKernels[0]) == idx(K512::kAuto80Vote) - idx(K512::kStats128) &&
+              sizeof(kAutoKernels) / sizeof(kAutoKernels[0]) == idx(K512::kCount) - idx(K512::kAuto80Vote), "one kernel per K512, in the order of the lists");
+static_assert(kFused512F32Waves == 12, "fused512_route.hpp spells the f32 kernels' waves out");
+
+inline auto kernel512(K512 k, const FbankFastParams &) { return is_fast(k) ? kFastKernels[idx(k)] : nullptr; }
+inline auto kernel512(K512 k, const FbankClipParams &) { return is_clip(k) ? kClipKernels[idx(k) - idx(K512::kClip80)] : nullptr; }
+inline auto kernel512(K512 k, const FbankStatsParams &) { return is_stats(k) ? kStatsKernels[idx(k) - idx(K512::kStats128)] : nullptr; }
+inline auto kernel512(K512 k, const W512AutoParams &) { return is_auto(k) ? kAutoKernels[idx(k) - idx(K512::kAuto80Vote)] : nullptr; }
+inline const BatchDesc &batch_of(const FbankFastParams &p) { return p.b; }
+template <class P> const BatchDesc &batch_of(const P &q) { return q.f.b; }
+
+// an object's dynamic LDS: of its f64 kernels, of its f32 kernels (0: none), and the bin count RoundStats is sized by
+struct Lds512Sizes {
+    size_t f64, f32;
+    int n_mels;
+};
+size_t lds512(Lds512 which, const Lds512Sizes &z) {
+    switch (which) {
+        case Lds512::kF32: return z.f32;
+        case Lds512::kF64PlusClipCmn: return z.f64 + sizeof(ClipCmnShared<8>);
+        case Lds512::kF64PlusRoundStats: return z.f64 + RoundStats<8>::bytes(z.n_mels);
+        default: return z.f64;
     }
 }
+unsigned grid512(const Launch512 &l, uint64_t n_units, int cus) {
+    static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);   // one workgroup is resident per CU; measured best
+    if (l.units_per_group == 0) return static_cast<unsigned>(cus);
+    return grid_for_xcd((n_units + l.units_per_group - 1) / l.units_per_group, cus, l.lab_per_cu ? per_cu : 1);
+}
+const char *attr_name(K512 k) {
+    return is_clip(k) ? "hipFuncSetAttribute(fbank512_clip_kernel)" : is_stats(k) ? "hipFuncSetAttribute(fbank512_nemo_stats_kernel)"
+         : is_auto(k) ? "hipFuncSetAttribute(w512_auto_kernel)" : k >= K512::kKaldiIo80 ? "hipFuncSetAttribute(fbank512_kaldi_io_kernel)"
+         : is_io(k) ? "hipFuncSetAttribute(fbank512_nemo_io_kernel)" : info_of(k).f32 ? "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)"
+                    : "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)";
+}
+// one launch of a route with the parameters of its kernel's group; z: the object's LDS sizes
+template <class P>
+int launch512(const Launch512 &l, const P &p, const Lds512Sizes &z, int cus, hipStream_t s) {
+    static std::atomic<uint64_t> attr_done[idx(K512::kCount)];          // one bit per device: function attributes are per device
+    const auto kernel = kernel512(l.kernel, p);
+    if (!kernel) return fail(MELSPEC_ERR_INTERNAL, "launch512: the object has no kernel for this batch");
+    if (int rc = allow_big_lds_once(attr_done[idx(l.kernel)], attr_name(l.kernel), kernel)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid512(l, batch_of(p).n_units, cus)), dim3(l.waves * 64), lds512(l.lds, z), s, p);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
 
-void f32_params(const Fused512F32 &f, FbankFastParams &fp) {
-    fp.d_blob = static_cast<const uint32_t *>(f.d_blob.p);
-    fp.blob_words = static_cast<int>(f.ft.blob.size());
-    fp.mel_off_words = f.ft.mel_off_words;
-    fp.slots = f.ft.slots;
+// the tables' part of the fused kernels' parameters ...
+void set_tables(FbankFastParams &fp, const FbankFastTables &ft, const DevBuf &blob) {
+    fp.d_blob = static_cast<const uint32_t *>(blob.p);
+    fp.blob_words = static_cast<int>(ft.blob.size());
+    fp.mel_off_words = ft.mel_off_words;
+    fp.slots = ft.slots;
 }
-int launch_w512_f32(const Fused512F32 &f, FbankFastParams fp, int cus, hipStream_t s) {
-    f32_params(f, fp);
-    if (fb_lens_match<LensSlaney80W>(f.ft.slots)) return launch_fused512<float, kFlavorWhisper, kFbSlots, LensSlaney80W>(kFused512F32Waves, fp, f.lds, cus, s);
-    return launch_fused512<float, kFlavorWhisper, kBlmSlots, LensSlaney128>(kFused512F32Waves, fp, f.lds, cus, s);
+// ... and what every object fills alike; the caller adds its own fields
+FbankFastParams fast_params(const FbankFastTables &ft, const DevBuf &blob, const BatchDesc &desc, int shift, int n_mels) {
+    FbankFastParams fp{};
+    fp.b = desc;
+    set_tables(fp, ft, blob);
+    fp.shift = shift;
+    fp.n_mels = n_mels;
+    return fp;
 }
-int launch_nemo_f32(const Fused512F32 &f, FbankFastParams fp, int cus, hipStream_t s) {
-    f32_params(f, fp);
-    fp.b.sync_rounds = 0;        // StagedRows instead of RoundSync
-    if (fb_lens_match<LensSlaney128>(f.ft.slots)) return launch_fused512<float, kFlavorNemo, kBlmSlots, LensSlaney128>(kFused512F32Waves, fp, f.lds, cus, s);
-    return launch_fused512<float, kFlavorNemo, kFbSlots, LensSlaney80>(kFused512F32Waves, fp, f.lds, cus, s);
+// what a route asks of its kernel's parameters: an f32 kernel reads the f32 tables; RoundSync as the route has it
+void apply_route(const Route512 &r, FbankFastParams &fp, const Fused512F32 &f32) {
+    if (info_of(r.run.kernel).f32) set_tables(fp, f32.ft, f32.d_blob);
+    if (r.sync_rounds != kSyncKeep) fp.b.sync_rounds = r.sync_rounds;
 }
-}  // namespace
+// the compile-time bank an object's tables have, of the two its flavour has kernels for
+template <class A, class B>
+Bank512 bank512(const MelSlots &ms, Bank512 a, Bank512 b) { return fb_lens_match<A>(ms) ? a : fb_lens_match<B>(ms) ? b : Bank512::kRuntime; }
 
-namespace {
+Fused512Shape w512_shape(const melspec_ctx *c) {
+    return Fused512Shape{Flavor512::kWhisper, c->fast512, bank512<LensSlaney80W, LensSlaney128>(c->ft512.slots, Bank512::kSlaney80W, Bank512::kSlaney128),
+                         c->ft512.slots.n_slots <= kFbSlots, c->waves512, c->f512.ok, c->precision, c->fix.adaptive, c->fix.count.p != nullptr, false};
+}
+
 // MELSPEC_PRECISION_AUTO at n_fft = 512: the voting f32 launch and, gated on its verdict, the f64 launch (w512_auto_kernel)
-template <int NSLOTS, class Lens>
-int launch_w512_auto_t(melspec_ctx *c, const FbankFastParams &fp64, const BatchDesc &desc, hipStream_t stream) {
-    static std::atomic<uint64_t> attr_done{0};
-    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(w512_auto_kernel)", &w512_auto_kernel<float, kFused512F32Waves, NSLOTS, Lens>, &w512_auto_kernel<double, 8, NSLOTS, Lens>)) return rc;
+int launch_w512_auto(melspec_ctx *c, const Route512 &r, const FbankFastParams &fp64, const Lds512Sizes &z, hipStream_t stream) {
+    const BatchDesc &desc = fp64.b;
     FixSink sink{};
     int rc = auto_sink(c, desc, stream, true, sink);
     if (rc) return rc;
     sink.tab = nullptr;
-    const unsigned grid32 = grid_for_xcd((desc.n_units + kFused512F32Waves - 1) / kFused512F32Waves, c->dev.cus, 1);
+    const unsigned grid32 = grid512(r.vote, desc.n_units, c->dev.cus);
     W512AutoParams q{};
     q.f = fp64;
-    f32_params(c->f512, q.f);
+    set_tables(q.f, c->f512.ft, c->f512.d_blob);
     q.fix = sink_armed(c, sink, desc, grid32);
     q.fix.vote_groups = std::min<unsigned>(grid32, static_cast<unsigned>(c->dev.cus));
-    hipLaunchKernelGGL((w512_auto_kernel<float, kFused512F32Waves, NSLOTS, Lens>), dim3(grid32), dim3(kFused512F32Waves * 64), c->f512.lds, stream, q);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch512(r.vote, q, z, c->dev.cus, stream))) return rc;
     // the gated launch: this batch's verdict (its number is c->fix.seq) decides between every unit, the noted units and nothing
-    const unsigned grid64 = grid_for_xcd((desc.n_units + 7) / 8, c->dev.cus, 1);
     W512AutoParams g{};
     g.f = fp64;
     FixSink stat{};
     stat.count = sink.count; stat.acc = sink.acc; stat.host = sink.host; stat.list = sink.list;
-    g.fix = sink_armed(c, stat, desc, grid64);          // (a launch number of its own: the host tells the two reports apart by kStatFromGated)
+    g.fix = sink_armed(c, stat, desc, grid512(r.gated, desc.n_units, c->dev.cus));          // (a launch number of its own: the host tells the two reports apart by kStatFromGated)
     g.fix.frames |= kStatFromGated;
     g.gate = sink.decision;
     g.gate_seq = q.fix.seq;
-    hipLaunchKernelGGL((w512_auto_kernel<double, 8, NSLOTS, Lens>), dim3(grid64), dim3(512), c->lds512, stream, g);
-    HIP_TRY(hipGetLastError());
-    return MELSPEC_OK;
+    return launch512(r.gated, g, z, c->dev.cus, stream);
 }
 }  // namespace
 
 namespace melspec {
 namespace host {
-// can a plain batch of this n_fft = 512 context run in MELSPEC_PRECISION_AUTO's f32 / f64 pair?  (the compile-time banks, eight f64 waves)
-bool w512_auto_ok(const melspec_ctx *c) {
-    return c->fast512 && c->f512.ok && c->waves512 == 8 && c->fix.count.p != nullptr &&
-           (fb_lens_match<LensSlaney80W>(c->ft512.slots) || fb_lens_match<LensSlaney128>(c->ft512.slots));
-}
-
-// the precision a plain batch of an n_fft = 512 context computes in: F32 where asked for and built, AUTO's voting pair where the bank
-// allows it, else f64
-static int w512_precision(const melspec_ctx *c) {
-    if (c->precision == MELSPEC_PRECISION_F32 && c->f512.ok) return MELSPEC_PRECISION_F32;
-    if (c->precision == MELSPEC_PRECISION_AUTO && c->fix.adaptive && w512_auto_ok(c)) return MELSPEC_PRECISION_AUTO;
-    return MELSPEC_PRECISION_F64;
-}
-const char *whisper512_kernel_name(const melspec_ctx *c) {
-    switch (w512_precision(c)) {
-        case MELSPEC_PRECISION_F32: return "melspec::fbank512_wave_kernel<float, 12, 1, kFlavorWhisper, RUNS> (n_fft = 512, f32, three waves per SIMD)";
-        case MELSPEC_PRECISION_AUTO: return "melspec::w512_auto_kernel<float, 12> (n_fft = 512, f32, precision guard + vote) + the gated melspec::w512_auto_kernel<double, 8>";
-        default: return "melspec::fbank512_wave_kernel<double, 8, 1, kFlavorWhisper, RUNS> (n_fft = 512, f64)";
-    }
-}
+bool w512_auto_ok(const melspec_ctx *c) { return w512_auto_ok(w512_shape(c)); }
+const char *whisper512_kernel_name(const melspec_ctx *c) { return whisper512_kernel_name(w512_shape(c)); }
 
 // the Whisper flavour of the 512-point kernel: launch_ctx's branch for the n_fft = 512 contexts
 int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream) {
-        FbankFastParams fp{};
-        fp.b = desc;
-        fp.d_blob = static_cast<const uint32_t *>(c->d_blob512.p);
-        fp.blob_words = static_cast<int>(c->ft512.blob.size());
-        fp.mel_off_words = c->ft512.mel_off_words;
-        fp.shift = c->hop_size;
-        fp.n_mels = c->n_mels;
-        fp.use_log = 1; fp.use_power = 1;
-        fp.slots = c->ft512.slots;
-        const int mode = w512_precision(c);
-        if (mode == MELSPEC_PRECISION_F32) return launch_w512_f32(c->f512, fp, c->dev.cus, stream);
-        // AUTO (round 6): plain batches -- uniform and ragged -- vote like the n_fft = 400 contexts do; the layouts stay on the f64 kernel
-        const bool plain = !is_layout(desc);
-        // ... when there is a batch to speak of: below two units per f32 wave of the grid (6144 units = 24 576 frames on an MI355X) a call is
-        // launch-bound, the pair of launches is slower than the f64 kernel alone, and the f64 kernel it is (also what keeps the streaming
-        // bank's hop-sized pushes on the reference's golden within 1e-6; a rule on the batch's size: still a function of the batch alone)
-        const bool sizeable = desc.n_units >= 2ull * kFused512F32Waves * static_cast<unsigned>(c->dev.cus);
-        if (mode == MELSPEC_PRECISION_AUTO && plain && sizeable)
-            return fb_lens_match<LensSlaney80W>(c->ft512.slots) ? launch_w512_auto_t<kFbSlots, LensSlaney80W>(c, fp, desc, stream)
-                                                                : launch_w512_auto_t<kBlmSlots, LensSlaney128>(c, fp, desc, stream);
-        if (fb_lens_match<LensSlaney80W>(c->ft512.slots)) return launch_fused512<double, kFlavorWhisper, kFbSlots, LensSlaney80W>(c->waves512, fp, c->lds512, c->dev.cus, stream);
-        if (fb_lens_match<LensSlaney128>(c->ft512.slots)) return launch_fused512<double, kFlavorWhisper, kBlmSlots, LensSlaney128>(c->waves512, fp, c->lds512, c->dev.cus, stream);
-        return c->ft512.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorWhisper, kFbSlots>(c->waves512, fp, c->lds512, c->dev.cus, stream)
-                                                  : launch_fused512<double, kFlavorWhisper, kBlmSlots>(c->waves512, fp, c->lds512, c->dev.cus, stream);
+    const Route512 r = route512(w512_shape(c), is_layout(desc) ? Batch512::kLayout : Batch512::kPlain);
+    FbankFastParams fp = fast_params(c->ft512, c->d_blob512, desc, c->hop_size, c->n_mels);
+    fp.use_log = 1; fp.use_power = 1;
+    const Lds512Sizes z{c->lds512, c->f512.lds, c->n_mels};
+    if (r.vote.kernel != K512::kNone && desc.n_units >= w512_auto_min_units(c->dev.cus)) return launch_w512_auto(c, r, fp, z, stream);
+    apply_route(r, fp, c->f512);
+    return launch512(r.run, fp, z, c->dev.cus, stream);
 }
 }  // namespace host
 }  // namespace melspec
@@ -299,24 +292,20 @@ int melspec_fbank_use_generic(melspec_fbank *fb, int on) {
     return MELSPEC_OK;
 }
 
-static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, float *d_means = nullptr);
-
 static double fbank_floor(const melspec_fbank *fb) { return fb->cfg.energy_floor > 0.0 ? fb->cfg.energy_floor : static_cast<double>(FLT_EPSILON); }
+
+static Fused512Shape fbank_shape(const melspec_fbank *fb) {
+    return Fused512Shape{Flavor512::kKaldi, fb->fast && !fb->use_generic, bank512<LensKaldi80, LensKaldi40>(fb->ft.slots, Bank512::kKaldi80, Bank512::kKaldi40),
+                         fb->ft.slots.n_slots <= kFbSlots, fb->waves, false, MELSPEC_PRECISION_F64, false, false, fb->cfg.apply_cmn && fb->cfg.use_power};
+}
 
 // the fused kernels' parameters of a batch of this object
 static FbankFastParams fbank_fast_params(const melspec_fbank *fb, const BatchDesc &desc) {
-    FbankFastParams fp{};
-    fp.b = desc;
-    fp.d_blob = static_cast<const uint32_t *>(fb->d_blob.p);
-    fp.blob_words = static_cast<int>(fb->ft.blob.size());
-    fp.mel_off_words = fb->ft.mel_off_words;
-    fp.shift = fb->frame_shift;
-    fp.n_mels = fb->cfg.num_mel_bins;
+    FbankFastParams fp = fast_params(fb->ft, fb->d_blob, desc, fb->frame_shift, fb->cfg.num_mel_bins);
     fp.preemph = fb->cfg.preemphasis > 0.0 ? fb->cfg.preemphasis : 0.0;   // src/fbank.rs:172
     fp.floor_v = static_cast<float>(fbank_floor(fb));
     fp.use_log = fb->cfg.use_log_fbank;
     fp.use_power = fb->cfg.use_power;
-    fp.slots = fb->ft.slots;
     return fp;
 }
 
@@ -360,19 +349,96 @@ static int launch_cmn(melspec_fbank *fb, const BatchDesc &desc, uint32_t n_clips
     return MELSPEC_OK;
 }
 
+// the scratch of a CMN call with 16-bit rows out on stream s: `floats` f32 rows and, behind them, `tail` 64-bit words
+static int fbank_rows32(melspec_fbank *fb, uint64_t floats, size_t tail, hipStream_t s, float *&rows, uint64_t *&words) {
+    const size_t row_bytes = (static_cast<size_t>(floats) * sizeof(float) + 15) & ~static_cast<size_t>(15);
+    const int rc = fb->rows32.ensure(row_bytes + tail * sizeof(uint64_t) + 16, s);
+    rows = static_cast<float *>(fb->rows32.p());
+    words = reinterpret_cast<uint64_t *>(static_cast<char *>(fb->rows32.p()) + row_bytes);
+    return rc;
+}
+
+// Kernels of one batch (uniform or ragged plan): the fused 512-point kernel or the generic one, then the CMN per clip -- or the
+// workgroup-per-clip kernel with the normalisation inside.  fpc: frames of the longest clip (LDS budget of the CMN).
+// io = 0: the f32 call; d_means not nullptr: its split output -- un-normalised rows + the clips' column means.
+// io != 0 (an object that kaldi_io_ok): the plan is the f32 call's, sample offsets and strides in elements; always the two-kernel path.
+// pl.desc.out is where the rows of the wave kernel go: the caller's buffer, or -- CMN with 16-bit rows out -- the scratch, from where
+// cmn_io_kernel writes them to vd_out (ragged: at d_dst_off).
+static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, int io = 0, float *d_means = nullptr,
+                        void *vd_out = nullptr, const uint64_t *d_dst_off = nullptr) {
+    const int nm = fb->cfg.num_mel_bins, out_dtype = io >> 4;
+    const bool split = out_dtype != MELSPEC_OUT_F32 && fb->cfg.apply_cmn;
+    int rc = MELSPEC_OK;
+    if (fb->fast && !fb->use_generic) {
+        const Fused512Shape shape = fbank_shape(fb);
+        const FbankFastParams fp = fbank_fast_params(fb, pl.desc);
+        const Lds512Sizes z{fb->fast_lds, 0, nm};
+        // many clips of one length + CMN: the workgroup-per-clip kernel with the normalisation inside (fbank512_clip_kernel) when the
+        // clips fill the CUs evenly enough (lab builds: MELSPEC_FB_CLIP=0 keeps the two kernels)
+        static const bool clip_on = lab_int("MELSPEC_FB_CLIP", 1, 0, 1) != 0;
+        const uint32_t cus = static_cast<uint32_t>(fb->dev.cus);
+        const bool ragged_by_clip = pl.desc.d_order != nullptr;       // fbank_ragged decided (and checked the alignment)
+        if (!io && clip_on && (ragged_by_clip ||
+            (clip_shape_ok(shape, nm) && pl.desc.d_unit_prefix == nullptr && (reinterpret_cast<uintptr_t>(pl.desc.out) & 15) == 0 && pl.desc.out_stride % 4 == 0 &&
+             clip_uniform_ok(n_clips, cus)))) {
+            const Route512 r = route512(shape, ragged_by_clip ? Batch512::kClipRagged : Batch512::kClipUniform);
+            if (lds512(r.run.lds, z) <= kLdsLimit) {
+                FbankClipParams q{};
+                q.f = fp;
+                q.frames = fpc;
+                static const int clip_skip = lab_int("MELSPEC_FB_CLIP_SKIP", 0, 0, 15);
+                q.lab_skip = clip_skip;
+                q.d_means = d_means;
+                return launch512(r.run, q, z, fb->dev.cus, s);
+            }
+        }
+        // (F32 samples, f32 rows into the scratch) is the f32 call's kernel
+        const int kio = split ? io & 15 : io;
+        const Route512 r = route512(shape, kio ? Batch512::kIo : is_layout(pl.desc) ? Batch512::kLayout : Batch512::kPlain, kio);
+        rc = launch512(r.run, fp, z, fb->dev.cus, s);
+        // the CMN pass below walks clips, not units
+    } else {
+        rc = launch_generic(fb->gt, pl.desc, fb->frame_shift, 1, fb->cfg.use_log_fbank, fb->cfg.use_power,
+                            fb->cfg.preemphasis, fbank_floor(fb), fb->dev.cus, s);
+    }
+    if (rc || !fb->cfg.apply_cmn) return rc;
+    if (split) return launch_cmn(fb, pl.desc, n_clips, fpc, s, nullptr, vd_out, out_dtype, d_dst_off);
+    return launch_cmn(fb, pl.desc, n_clips, fpc, s, d_means);          // in place ((S16, F32): the f32 rows are the caller's)
+}
+
+// The uniform batch of melspec_fbank_compute_uniform_device, of its split form (d_means) and of its _io form.  io = pcm_dtype |
+// out_dtype << 4 (fbank_io_args): 0 is the f32 call and launches exactly what it always did; otherwise vd_pcm / vd_out are int16 samples
+// / f16, bf16 rows and the plan counts elements.
+static int fbank_uniform(melspec_fbank *fb, const void *vd_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, void *vd_out, void *stream, int io,
+                         float *d_means = nullptr) {
+    if (n_clips == 0) return MELSPEC_OK;
+    const uint64_t fpc = fbank_frames(fb, clip_len);
+    const int nm = fb->cfg.num_mel_bins;
+    if (fpc == 0) {                     // zeros((0, num_mel_bins)), src/fbank.rs:147-149: no rows; the mean of nothing is reported as 0
+        if (!d_means) return MELSPEC_OK;
+        HIP_TRY(hipSetDevice(fb->dev.device));
+        HIP_TRY(hipMemsetAsync(d_means, 0, static_cast<size_t>(n_clips) * nm * sizeof(float), stream ? static_cast<hipStream_t>(stream) : fb->stream));
+        return MELSPEC_OK;
+    }
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    const bool fused = fb->fast && !fb->use_generic;
+    float *d_rows = static_cast<float *>(vd_out);
+    // 16-bit rows cannot have their means subtracted in place: the wave kernel then writes f32 rows into the object's scratch
+    if ((io >> 4) != MELSPEC_OUT_F32 && fb->cfg.apply_cmn) {
+        uint64_t *words;
+        if (int rc = fbank_rows32(fb, static_cast<uint64_t>(n_clips) * fpc * nm, 0, s, d_rows, words)) return rc;
+    }
+    const BatchPlan pl = plan_uniform(static_cast<const float *>(vd_pcm), d_rows, clip_stride, fpc, n_clips, nm, fused ? kFbFPW : 1);
+    return fbank_launch(fb, pl, n_clips, fpc, s, io, d_means, vd_out, nullptr);
+}
+
 int melspec_fbank_compute_uniform_device(melspec_fbank *fb, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
                                          uint32_t n_clips, float *d_out, void *stream) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    if (n_clips == 0) return MELSPEC_OK;
-    const uint64_t fpc = fbank_frames(fb, clip_len);
-    if (fpc == 0) return MELSPEC_OK;   // zeros((0, num_mel_bins)), src/fbank.rs:147-149
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
-    const int nm = fb->cfg.num_mel_bins;
-    const bool fused = fb->fast && !fb->use_generic;
-    const BatchPlan pl = plan_uniform(d_pcm, d_out, clip_stride, fpc, n_clips, nm, fused ? kFbFPW : 1);
-    return fbank_launch(fb, pl, n_clips, fpc, s);
+    return fbank_uniform(fb, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, 0);
 }
 
 int melspec_fbank_compute_uniform_device_split(melspec_fbank *fb, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
@@ -380,130 +446,59 @@ int melspec_fbank_compute_uniform_device_split(melspec_fbank *fb, const float *d
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     if (!fb->cfg.apply_cmn) return fail(MELSPEC_ERR_INVALID_ARG, "the split output is the CMN's two halves: FbankConfig::apply_cmn is off");
     if (n_clips == 0) return MELSPEC_OK;
-    const uint64_t fpc = fbank_frames(fb, clip_len);
     if (!d_means) return fail(MELSPEC_ERR_INVALID_ARG, "d_means is NULL");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
-    const int nm = fb->cfg.num_mel_bins;
-    if (fpc == 0) {                     // zeros((0, num_mel_bins)): no rows; the mean of nothing is reported as 0
-        HIP_TRY(hipMemsetAsync(d_means, 0, static_cast<size_t>(n_clips) * nm * sizeof(float), s));
-        return MELSPEC_OK;
-    }
-    if (!d_pcm || !d_rows) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    const bool fused = fb->fast && !fb->use_generic;
-    const BatchPlan pl = plan_uniform(d_pcm, d_rows, clip_stride, fpc, n_clips, nm, fused ? kFbFPW : 1);
-    return fbank_launch(fb, pl, n_clips, fpc, s, d_means);
+    return fbank_uniform(fb, d_pcm, clip_stride, clip_len, n_clips, d_rows, stream, 0, d_means);
 }
 
-// kernels of one batch (uniform or ragged plan): fused 512-point kernel or the generic one, then CMN per clip
-static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc /* frames of the longest clip (LDS budget of the CMN) */, hipStream_t s,
-                        float *d_means /* not nullptr: the split output -- un-normalised rows + the clips' column means */) {
-    const int nm = fb->cfg.num_mel_bins;
-    const bool fused = fb->fast && !fb->use_generic;
-    const double floor_v = fbank_floor(fb);
-    int rc = MELSPEC_OK;
-    if (fused) {
-        const FbankFastParams fp = fbank_fast_params(fb, pl.desc);
-        // many clips of one length + CMN: the workgroup-per-clip kernel with the normalisation inside (fbank512_clip_kernel) when the
-        // clips fill the CUs evenly enough to beat the two-kernel path's 1.29 x (lab builds: MELSPEC_FB_CLIP=0 keeps the two kernels)
-        static const bool clip_on = lab_int("MELSPEC_FB_CLIP", 1, 0, 1) != 0;
-        const uint32_t cus = static_cast<uint32_t>(fb->dev.cus);
-        const uint32_t passes = (n_clips + cus - 1) / cus;
-        const bool ragged_by_clip = pl.desc.d_order != nullptr;       // melspec_fbank_compute_ragged_device decided (and checked the alignment)
-        if (clip_on && (ragged_by_clip ||
-            (fb->cfg.apply_cmn && fb->cfg.use_power && fb->waves == 8 && pl.desc.d_unit_prefix == nullptr && nm % 4 == 0 && nm <= 89 &&
-             (reinterpret_cast<uintptr_t>(pl.desc.out) & 15) == 0 && pl.desc.out_stride % 4 == 0 &&
-             n_clips >= cus && static_cast<uint64_t>(n_clips) * 100 >= static_cast<uint64_t>(passes) * cus * 85))) {
-            static std::atomic<uint64_t> attr_done{0};
-            if ((rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_clip_kernel)", &fbank512_clip_kernel<kFbSlots, LensKaldi80>, &fbank512_clip_kernel<kFbSlots, LensRuntime>,
-                                         &fbank512_clip_kernel<kFbSlots, LensKaldi80, true>, &fbank512_clip_kernel<kFbSlots, LensRuntime, true>,
-                                         &fbank512_clip_kernel<kFbSlots, LensKaldi40>, &fbank512_clip_kernel<kFbSlots, LensKaldi40, true>))) return rc;
-            FbankClipParams q{};
-            q.f = fp;
-            q.frames = fpc;
-            static const int clip_skip = lab_int("MELSPEC_FB_CLIP_SKIP", 0, 0, 15);
-            q.lab_skip = clip_skip;
-            q.d_means = d_means;
-            const size_t lds = fb->fast_lds + sizeof(ClipCmnShared<8>);
-            if (lds <= kLdsLimit) {
-                const bool k80 = fb_lens_match<LensKaldi80>(fb->ft.slots), k40 = fb_lens_match<LensKaldi40>(fb->ft.slots);
-                if (ragged_by_clip) {
-                    if (k80) hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensKaldi80, true>), dim3(cus), dim3(512), lds, s, q);
-                    else if (k40) hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensKaldi40, true>), dim3(cus), dim3(512), lds, s, q);
-                    else hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensRuntime, true>), dim3(cus), dim3(512), lds, s, q);
-                } else if (k80) hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensKaldi80>), dim3(cus), dim3(512), lds, s, q);
-                else if (k40) hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensKaldi40>), dim3(cus), dim3(512), lds, s, q);
-                else hipLaunchKernelGGL((fbank512_clip_kernel<kFbSlots, LensRuntime>), dim3(cus), dim3(512), lds, s, q);
-                HIP_TRY(hipGetLastError());
-                return MELSPEC_OK;
-            }
-        }
-        if (fb_lens_match<LensKaldi80>(fb->ft.slots))
-            rc = launch_fused512<double, kFlavorKaldi, kFbSlots, LensKaldi80>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s);
-        else if (fb_lens_match<LensKaldi40>(fb->ft.slots))
-            rc = launch_fused512<double, kFlavorKaldi, kFbSlots, LensKaldi40>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s);
-        else
-            rc = launch_fused512<double, kFlavorKaldi, kFbSlots>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s);
-        if (rc) return rc;
-        // the CMN pass below walks clips, not units
-    } else {
-        rc = launch_generic(fb->gt, pl.desc, fb->frame_shift, 1, fb->cfg.use_log_fbank, fb->cfg.use_power,
-                            fb->cfg.preemphasis, floor_v, fb->dev.cus, s);
-    }
-    if (rc) return rc;
-    if (fb->cfg.apply_cmn) return launch_cmn(fb, pl.desc, n_clips, fpc, s, d_means);
-    return MELSPEC_OK;
-}
-
-// What a ragged call (io = 0: the f32 one) begins with: the checks of its arguments, every clip's frames, the device and the stream.
-// `go` is false when the call ends here, with the status returned (MELSPEC_OK: a batch without frames).
-struct FbankRagged {
-    std::vector<uint64_t> frames;
-    uint64_t total = 0, longest = 0;
-    hipStream_t s = nullptr;
-};
-static int fbank_ragged_begin(melspec_fbank *fb, const void *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
-                              const void *d_out, void *stream, int io, FbankRagged &r, bool &go) {
-    go = false;
+// Fbank::compute per clip of any length (src/fbank.rs:141): clip c = vd_pcm[h_offsets[c] .. + h_lengths[c]) -> its frames at
+// vd_out + h_out_offsets[c] elements (NULL: packed); CMN per clip.  io: as in fbank_uniform; an _io batch runs on the two-kernel path
+// (the wave-owned kernel, then the CMN per clip), whatever its shape.
+static int fbank_ragged(melspec_fbank *fb, const void *vd_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips, void *vd_out,
+                        const uint64_t *h_out_offsets, void *stream, int io) {
     if (n_clips == 0) return MELSPEC_OK;
     if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    r.frames.resize(n_clips);
-    for (uint32_t i = 0; i < n_clips; ++i) { r.frames[i] = fbank_frames(fb, h_lengths[i]); r.total += r.frames[i]; r.longest = std::max(r.longest, r.frames[i]); }
-    if (r.total == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if (io && io_misaligned(d_pcm, d_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    std::vector<uint64_t> frames(n_clips);
+    uint64_t total = 0, longest = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) { frames[i] = fbank_frames(fb, h_lengths[i]); total += frames[i]; longest = std::max(longest, frames[i]); }
+    if (total == 0) return MELSPEC_OK;
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     HIP_TRY(hipSetDevice(fb->dev.device));
-    r.s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
-    go = true;
-    return MELSPEC_OK;
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    const bool fused = fb->fast && !fb->use_generic;
+    const int nm = fb->cfg.num_mel_bins;
+    int rc;
+    float *d_rows = static_cast<float *>(vd_out);
+    // CMN with 16-bit rows: the wave kernel writes f32 rows, packed in clip order, into the scratch (fbank_uniform); the caller's own
+    // output offsets travel behind them
+    const bool split = (io >> 4) != MELSPEC_OUT_F32 && fb->cfg.apply_cmn;
+    const uint64_t *d_own = nullptr;
+    if (split) {
+        uint64_t *words;
+        if ((rc = fbank_rows32(fb, total * static_cast<uint64_t>(nm), h_out_offsets ? n_clips : 0, s, d_rows, words))) return rc;
+        if (h_out_offsets) {
+            HIP_TRY(hipMemcpyAsync(words, h_out_offsets, static_cast<size_t>(n_clips) * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
+            d_own = words;
+        }
+    }
+    // whole clips per workgroup (fbank512_clip_kernel) when the batch can keep every CU busy (clip_ragged_ok); outputs at 16-byte offsets
+    // (packed outputs of n_mels % 4 == 0 are)
+    bool by_clip = !io && clip_shape_ok(fbank_shape(fb), nm) && (reinterpret_cast<uintptr_t>(vd_out) & 15) == 0 &&
+                   clip_ragged_ok(n_clips, static_cast<uint32_t>(fb->dev.cus), longest, total);
+    if (by_clip && h_out_offsets)
+        for (uint32_t i = 0; i < n_clips && by_clip; ++i) by_clip = h_out_offsets[i] % 4 == 0;
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    rc = plan_ragged(fb->ragged, s, static_cast<const float *>(vd_pcm), d_rows, h_offsets, frames, split ? nullptr : h_out_offsets, n_clips, nm, fused ? kFbFPW : 1, pl, slot, by_clip);
+    if (!rc) rc = fbank_launch(fb, pl, n_clips, longest, s, io, nullptr, vd_out, d_own ? d_own : pl.desc.d_out_off);
+    plan_ragged_done(slot, s);
+    return rc;
 }
 
-// Fbank::compute per clip of any length (src/fbank.rs:141): clip c = d_pcm[h_offsets[c] .. + h_lengths[c]) -> its frames at
-// d_out + h_out_offsets[c] floats (NULL: packed); CMN per clip.
 int melspec_fbank_compute_ragged_device(melspec_fbank *fb, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                         uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    FbankRagged r;
-    bool go;
-    int rc = fbank_ragged_begin(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, stream, 0, r, go);
-    if (!go) return rc;
-    const std::vector<uint64_t> &frames = r.frames;
-    const uint64_t total = r.total, longest = r.longest;
-    hipStream_t s = r.s;
-    const bool fused = fb->fast && !fb->use_generic;
-    BatchPlan pl;
-    RaggedSlot *slot = nullptr;
-    // whole clips per workgroup (fbank512_clip_kernel) when the batch can keep every CU busy: at least two clips per CU and no clip
-    // longer than half a CU's share; outputs at 16-byte offsets (packed outputs of n_mels % 4 == 0 are)
-    const int nm = fb->cfg.num_mel_bins;
-    bool by_clip = fused && fb->cfg.apply_cmn && fb->cfg.use_power && fb->waves == 8 && nm % 4 == 0 && nm <= 89 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0 &&
-                   n_clips >= 2u * static_cast<uint32_t>(fb->dev.cus) && longest * 2 * static_cast<uint64_t>(fb->dev.cus) <= total && longest < (1ull << 31);
-    if (by_clip && h_out_offsets)
-        for (uint32_t i = 0; i < n_clips && by_clip; ++i) by_clip = h_out_offsets[i] % 4 == 0;
-    rc = plan_ragged(fb->ragged, s, d_pcm, d_out, h_offsets, frames, h_out_offsets, n_clips, nm, fused ? kFbFPW : 1, pl, slot, by_clip);
-    if (!rc) rc = fbank_launch(fb, pl, n_clips, longest, s);
-    plan_ragged_done(slot, s);
-    return rc;
+    return fbank_ragged(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, 0);
 }
 
 // The same with the clip table in device memory (see melspec_compute_ragged_device_desc).
@@ -540,37 +535,22 @@ int melspec_fbank_synchronize(melspec_fbank *fb, void *stream) {
     return MELSPEC_OK;
 }
 
-// Fbank::compute on many host clips in one call: whole clips (the CMN is per clip) in chunks of ~16 MiB of PCM through the pinned,
-// double-buffered pipeline of host_pipe.hpp, one ragged launch per chunk.
+// Fbank::compute on many host clips in one call: whole clips (the CMN is per clip) through the host pipeline, one ragged launch per chunk.
 int melspec_fbank_compute_batch_host(melspec_fbank *fb, const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips,
                                      float *out, const uint64_t *out_offsets, size_t out_capacity_floats, uint64_t *total_frames) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     if (total_frames) *total_frames = 0;
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!offsets || !lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    const uint64_t nm = static_cast<uint64_t>(fb->cfg.num_mel_bins);
     std::vector<HostSeg> segs;
-    segs.reserve(n_clips);
-    uint64_t total = 0, cursor = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) {
-        const uint64_t f = fbank_frames(fb, lengths[i]);
-        const uint64_t oo = out_offsets ? out_offsets[i] : cursor;
-        if (f && oo + f * nm > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-        if (f && (!samples || !out)) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-        if (f) segs.push_back(HostSeg{samples + offsets[i], lengths[i], out + oo, f});
-        cursor += f * nm; total += f;
-    }
+    uint64_t total;
+    if (int rc = host_segments(samples, offsets, lengths, n_clips, out, out_offsets, out_capacity_floats, static_cast<uint64_t>(fb->cfg.num_mel_bins),
+                               [fb](uint64_t n) { return fbank_frames(fb, n); }, segs, total)) return rc;
     if (total_frames) *total_frames = total;
     if (total == 0) return MELSPEC_OK;
     HIP_TRY(hipSetDevice(fb->dev.device));
-    const char *where = "";
-    const int rc = fb->pipe.run(segs, fb->cfg.num_mel_bins, kPipeChunkSamples, fb->stream,
-                                [fb](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out,
-                                     const uint64_t *ooffs, hipStream_t s) {
-                                    return melspec_fbank_compute_ragged_device(fb, d_in, offs, lens, n, d_out, ooffs, s);
-                                }, &where);
-    if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
-    return rc;
+    return host_pipe_run(fb->pipe, segs, fb->cfg.num_mel_bins, fb->stream,
+                         [fb](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out, const uint64_t *ooffs, hipStream_t s) {
+                             return melspec_fbank_compute_ragged_device(fb, d_in, offs, lens, n, d_out, ooffs, s);
+                         });
 }
 
 }  // extern "C"
@@ -612,9 +592,14 @@ uint64_t blm_padded(const melspec_blm *b, uint64_t frames) {         // pad_len,
     return p == 0 ? frames : (frames + p - 1) / p * p;
 }
 
+Fused512Shape blm_shape(const melspec_blm *b) {
+    return Fused512Shape{Flavor512::kNemo, b->fast, bank512<LensSlaney128, LensSlaney80>(b->ft.slots, Bank512::kSlaney128, Bank512::kSlaney80),
+                         b->ft.slots.n_slots <= kFbSlots, b->waves, b->f32.ok, b->precision, false, false, false};
+}
+
 // ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io) ---------------------------------------------------------------------
 // the contexts whose kernels have the instantiations: the fused geometry on eight f64 waves with one of the compile-time Slaney banks
-bool blm_io_ok(const melspec_blm *b) { return b->fast && b->waves == 8 && nemo_f32_bank(b->ft.slots); }
+bool blm_io_ok(const melspec_blm *b) { return nemo_io_ok(blm_shape(b)); }
 // 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
 int blm_io_args(const melspec_blm *b, int pcm_dtype, int out_dtype, int &io) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
@@ -625,41 +610,6 @@ int blm_io_args(const melspec_blm *b, int pcm_dtype, int out_dtype, int &io) {
                        (b->fast ? " (another filterbank)" : "");
         return MELSPEC_ERR_UNSUPPORTED;
     }
-    return MELSPEC_OK;
-}
-
-struct NemoIoKernels {
-    void (*f64_128)(const FbankFastParams);
-    void (*f64_80)(const FbankFastParams);
-    void (*f32_128)(const FbankFastParams);
-    void (*f32_80)(const FbankFastParams);
-};
-template <class In, class Out>
-NemoIoKernels nemo_io_kernels_of() {
-    return NemoIoKernels{&fbank512_nemo_io_kernel<double, 8, kBlmSlots, LensSlaney128, In, Out>, &fbank512_nemo_io_kernel<double, 8, kFbSlots, LensSlaney80, In, Out>,
-                         &fbank512_nemo_io_kernel<float, 12, kBlmSlots, LensSlaney128, In, Out>, &fbank512_nemo_io_kernel<float, 12, kFbSlots, LensSlaney80, In, Out>};
-}
-// the mel kernel of a (sample, row) combination on fp, a batch planned like the f32 call's: launch_fused512's grids and LDS sizes
-int launch_nemo_io(melspec_blm *b, FbankFastParams fp, int io, hipStream_t s) {
-    static const NemoIoKernels table[2][3] = {{NemoIoKernels{}, nemo_io_kernels_of<float, io_f16>(), nemo_io_kernels_of<float, io_bf16>()},
-                                              {nemo_io_kernels_of<io_s16, float>(), nemo_io_kernels_of<io_s16, io_f16>(), nemo_io_kernels_of<io_s16, io_bf16>()}};
-    static std::atomic<uint64_t> attr_done[2][3];
-    const int pcm = io & 15, out = io >> 4;
-    if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || io == 0 || !blm_io_ok(b)) return fail(MELSPEC_ERR_INTERNAL, "launch_nemo_io: no such combination");
-    const NemoIoKernels &k = table[pcm][out];
-    if (int rc = allow_big_lds_once(attr_done[pcm][out], "hipFuncSetAttribute(fbank512_nemo_io_kernel)", k.f64_128, k.f64_80, k.f32_128, k.f32_80)) return rc;
-    const bool wide = fb_lens_match<LensSlaney128>(b->ft.slots);
-    if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) {
-        f32_params(b->f32, fp);
-        fp.b.sync_rounds = 0;        // StagedRows instead of RoundSync
-        const unsigned grid = grid_for_xcd((fp.b.n_units + kFused512F32Waves - 1) / kFused512F32Waves, b->dev.cus, 1);
-        hipLaunchKernelGGL(wide ? k.f32_128 : k.f32_80, dim3(grid), dim3(kFused512F32Waves * 64), b->f32.lds, s, fp);
-    } else {
-        static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);
-        const unsigned grid = grid_for_xcd((fp.b.n_units + 7) / 8, b->dev.cus, per_cu);
-        hipLaunchKernelGGL(wide ? k.f64_128 : k.f64_80, dim3(grid), dim3(512), b->fast_lds, s, fp);
-    }
-    HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
 }
 
@@ -704,29 +654,20 @@ void blm_norm_shape_ragged(uint64_t longest, size_t &stride, size_t &per, int &p
 
 // the fused kernels' parameters of a batch of this context (fbank_fast_params' counterpart); the caller adds what its kind of batch has
 FbankFastParams blm_fast_params(const melspec_blm *b, const BatchDesc &desc) {
-    FbankFastParams fp{};
-    fp.b = desc;
-    fp.d_blob = static_cast<const uint32_t *>(b->d_blob.p);
-    fp.blob_words = static_cast<int>(b->ft.blob.size());
-    fp.mel_off_words = b->ft.mel_off_words;
-    fp.shift = b->cfg.hop_length;
-    fp.n_mels = b->cfg.n_mels;
+    FbankFastParams fp = fast_params(b->ft, b->d_blob, desc, b->cfg.hop_length, b->cfg.n_mels);
     fp.preemph = b->cfg.preemphasis;
     fp.floor_v = b->cfg.log_zero_guard;
     fp.use_log = 1; fp.use_power = 1;
     fp.org0 = b->cfg.center ? -200 : 56;      // tap 0 of the window sits at position (512-400)/2 of the frame
-    fp.slots = b->ft.slots;
     return fp;
 }
+Lds512Sizes blm_lds(const melspec_blm *b) { return Lds512Sizes{b->fast_lds, b->f32.lds, b->cfg.n_mels}; }
 
 // the mel kernel of a batch: the (sample, row) combination io, the f32 kernel, the f64 kernel of a compile-time bank or of any bank
-int launch_nemo_mel(melspec_blm *b, const FbankFastParams &fp, int io, hipStream_t s) {
-    if (io) return launch_nemo_io(b, fp, io, s);
-    if (b->precision == MELSPEC_PRECISION_F32 && b->f32.ok) return launch_nemo_f32(b->f32, fp, b->dev.cus, s);
-    if (fb_lens_match<LensSlaney128>(b->ft.slots)) return launch_fused512<double, kFlavorNemo, kBlmSlots, LensSlaney128>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-    if (fb_lens_match<LensSlaney80>(b->ft.slots)) return launch_fused512<double, kFlavorNemo, kFbSlots, LensSlaney80>(b->waves, fp, b->fast_lds, b->dev.cus, s);
-    return b->ft.slots.n_slots <= kFbSlots ? launch_fused512<double, kFlavorNemo, kFbSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s)
-                                           : launch_fused512<double, kFlavorNemo, kBlmSlots>(b->waves, fp, b->fast_lds, b->dev.cus, s);
+int launch_nemo_mel(melspec_blm *b, FbankFastParams fp, int io, hipStream_t s) {
+    const Route512 r = route512(blm_shape(b), io ? Batch512::kIo : Batch512::kLayout, io);
+    apply_route(r, fp, b->f32);
+    return launch512(r.run, fp, blm_lds(b), b->dev.cus, s);
 }
 
 // The rows a normaliser works on: f32 rows read at src and written at dst as out_dtype -- MELSPEC_OUT_F32: in place (dst == src), f16 / bf16:
@@ -1103,22 +1044,11 @@ static int blm_host(melspec_blm *b, const void *samples, size_t n_samples, void 
     if (rows) *rows = static_cast<size_t>(b->cfg.n_mels);
     if (cols) *cols = 0;
     const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
-    if (c == 0) return MELSPEC_OK;
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    const uint64_t need = c * static_cast<uint64_t>(b->cfg.n_mels);
-    if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(b->dev.device));
-    const size_t ib = io_pcm_bytes(io & 15), ob = io_out_bytes(io >> 4);
-    int rc;
-    if ((rc = b->h2d.ensure(n_samples * ib))) return rc;
-    if ((rc = b->d2h.ensure(need * ob))) return rc;
-    HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, b->stream));
-    rc = blm_uniform(b, b->h2d.p, n_samples, n_samples, 1, b->d2h.p, b->stream, io);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, b->d2h.p, need * ob, hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    if (cols) *cols = static_cast<size_t>(c);
-    return MELSPEC_OK;
+    const int rc = host_one_clip(b->dev.device, b->h2d, b->d2h, b->stream, samples, n_samples * io_pcm_bytes(io & 15), out, out_capacity_elems,
+                                 c * static_cast<uint64_t>(b->cfg.n_mels), io_out_bytes(io >> 4),
+                                 [&](const void *d_in, void *d_out) { return blm_uniform(b, d_in, n_samples, n_samples, 1, d_out, b->stream, io); });
+    if (!rc && cols) *cols = static_cast<size_t>(c);
+    return rc;
 }
 
 int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
@@ -1129,13 +1059,12 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
 }
 
 // ---- the split output: un-normalised rows + per-feature mean and 1 / (std + 1e-5), see include/melspec_hip.h ----
-// LDS of a stats launch: the mel kernel's, plus the f64 kernel's unit partials
-static bool blm_stats_f32(const melspec_blm *b) { return b->precision == MELSPEC_PRECISION_F32 && b->f32.ok; }
-static size_t blm_stats_lds(const melspec_blm *b) {
-    return blm_stats_f32(b) ? b->f32.lds : b->fast_lds + RoundStats<8>::bytes(b->cfg.n_mels);
+// the contexts whose kernels have the instantiations (blm_io_ok's condition), in the precision mode the context is in: the launch's LDS
+// -- the mel kernel's, plus the f64 kernel's unit partials -- has to fit
+static bool blm_stats_ok(const melspec_blm *b) {
+    const Fused512Shape shape = blm_shape(b);
+    return stats_ok(shape) && lds512(route512(shape, Batch512::kStats).run.lds, blm_lds(b)) <= kLdsLimit;
 }
-// the contexts whose kernels have the instantiations (blm_io_ok's condition), in the precision mode the context is in
-static bool blm_stats_ok(const melspec_blm *b) { return blm_io_ok(b) && blm_stats_lds(b) <= kLdsLimit; }
 
 int melspec_blm_supports_split(const melspec_blm *b) { return b && blm_stats_ok(b) ? 1 : 0; }
 
@@ -1152,9 +1081,9 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
         return a.status;
     }
     const int nm = b->cfg.n_mels;
-    const bool f32 = blm_stats_f32(b);
+    const Route512 r = route512(blm_shape(b), Batch512::kStats);
     BlmStatsPlan sp;
-    if (!blm_stats_plan(cols, n_clips, nm, f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
+    if (!blm_stats_plan(cols, n_clips, nm, info_of(r.run.kernel).f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
     HIP_TRY(hipSetDevice(b->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
     int rc;
@@ -1165,26 +1094,12 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
     pl.desc.n_units = sp.n_units;
     FbankStatsParams q{};
     q.f = blm_fast_params(b, pl.desc);
-    q.f.b.sync_rounds = f32 ? 0 : kNemoSync;          // as the raw call: StagedRows instead of RoundSync (f32), the f64 kernel's measured best, which is none
+    q.f.b.sync_rounds = kNemoSync;          // as the raw call: the f64 kernel's measured best, which is none (f32: the route's StagedRows)
+    apply_route(r, q.f, b->f32);
     q.f.clip_len = static_cast<long long>(clip_len);
     q.d_part = static_cast<float2 *>(b->stats.p());
     q.blocks_per_clip = sp.blocks_per_clip;
-    const bool wide = fb_lens_match<LensSlaney128>(b->ft.slots);
-    static std::atomic<uint64_t> attr_done{0};
-    if ((rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(fbank512_nemo_stats_kernel)", &fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>,
-                                 &fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>, &fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>,
-                                 &fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>))) return rc;
-    const unsigned grid = grid_for_xcd(sp.n_units / sp.waves, b->dev.cus, 1);
-    const size_t lds = blm_stats_lds(b);
-    if (f32) {
-        f32_params(b->f32, q.f);
-        if (wide) hipLaunchKernelGGL((fbank512_nemo_stats_kernel<float, 12, kBlmSlots, LensSlaney128>), dim3(grid), dim3(kFused512F32Waves * 64), lds, s, q);
-        else hipLaunchKernelGGL((fbank512_nemo_stats_kernel<float, 12, kFbSlots, LensSlaney80>), dim3(grid), dim3(kFused512F32Waves * 64), lds, s, q);
-    } else {
-        if (wide) hipLaunchKernelGGL((fbank512_nemo_stats_kernel<double, 8, kBlmSlots, LensSlaney128>), dim3(grid), dim3(512), lds, s, q);
-        else hipLaunchKernelGGL((fbank512_nemo_stats_kernel<double, 8, kFbSlots, LensSlaney80>), dim3(grid), dim3(512), lds, s, q);
-    }
-    HIP_TRY(hipGetLastError());
+    if ((rc = launch512(r.run, q, blm_lds(b), b->dev.cus, s))) return rc;
     BlmStatsFinishParams fq{};
     fq.part = q.d_part; fq.mean = d_mean; fq.inv_std = d_inv_std; fq.valid = valid;
     fq.n_clips = n_clips; fq.blocks_per_clip = sp.blocks_per_clip; fq.block_frames = sp.block_frames; fq.n_mels = nm;
@@ -1254,20 +1169,11 @@ int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const u
                                    float *out, const uint64_t *out_offsets, size_t out_capacity_floats, uint64_t *total_columns) {
     if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
     if (total_columns) *total_columns = 0;
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!offsets || !lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
     const uint64_t nm = static_cast<uint64_t>(b->cfg.n_mels);
     std::vector<HostSeg> segs;
-    segs.reserve(n_clips);
-    uint64_t total = 0, cursor = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) {
-        const uint64_t c = blm_padded(b, blm_valid_frames(b, lengths[i]));
-        const uint64_t oo = out_offsets ? out_offsets[i] : cursor;
-        if (c && oo + c * nm > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-        if (c && (!samples || !out)) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-        if (c) segs.push_back(HostSeg{samples + offsets[i], lengths[i], out + oo, c});
-        cursor += c * nm; total += c;
-    }
+    uint64_t total;
+    if (int rc = host_segments(samples, offsets, lengths, n_clips, out, out_offsets, out_capacity_floats, nm,
+                               [b](uint64_t n) { return blm_padded(b, blm_valid_frames(b, n)); }, segs, total)) return rc;
     if (total_columns) *total_columns = total;
     if (total == 0) return MELSPEC_OK;
     HIP_TRY(hipSetDevice(b->dev.device));
@@ -1278,16 +1184,11 @@ int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const u
         }
         return MELSPEC_OK;
     }
-    const char *where = "";
-    const int rc = b->pipe.run(segs, b->cfg.n_mels, kPipeChunkSamples, b->stream,
-                               [b](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out,
-                                   const uint64_t *ooffs, hipStream_t s) {
-                                   return melspec_blm_compute_ragged_device(b, d_in, offs, lens, n, d_out, ooffs, s);
-                               }, &where);
-    if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
-    return rc;
+    return host_pipe_run(b->pipe, segs, b->cfg.n_mels, b->stream,
+                         [b](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out, const uint64_t *ooffs, hipStream_t s) {
+                             return melspec_blm_compute_ragged_device(b, d_in, offs, lens, n, d_out, ooffs, s);
+                         });
 }
-
 
 }  // extern "C"
 
@@ -1295,9 +1196,7 @@ int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const u
 // Kaldi fbank with int16 PCM in / f16, bf16 rows out (melspec_fbank_compute_*_io): see include/melspec_hip.h
 // ------------------------------------------------------------------------------------
 namespace {
-// the objects whose kernels have the instantiations: the fused path on eight f64 waves with the compile-time 80-bin Kaldi bank.  The
-// frame shift is not part of the condition: it is a run-time value of the kernel (FbankFastParams::shift), the default 10 ms or not.
-bool fbank_io_ok(const melspec_fbank *fb) { return fb->fast && !fb->use_generic && fb->waves == 8 && fb_lens_match<LensKaldi80>(fb->ft.slots); }
+bool fbank_io_ok(const melspec_fbank *fb) { return kaldi_io_ok(fbank_shape(fb)); }
 
 // 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
 int fbank_io_args(const melspec_fbank *fb, int pcm_dtype, int out_dtype, int &io) {
@@ -1315,68 +1214,6 @@ int fbank_io_args(const melspec_fbank *fb, int pcm_dtype, int out_dtype, int &io
     return MELSPEC_OK;
 }
 
-// the wave-owned kernel of a (sample, row) combination on fp, a batch planned like the f32 call's: launch_fused512's grid and LDS size
-int launch_kaldi_io(melspec_fbank *fb, const FbankFastParams &fp, int pcm, int out, hipStream_t s) {
-    typedef void (*Kernel)(const FbankFastParams);
-#define MS_KALDI_IO(In, Out) &fbank512_kaldi_io_kernel<double, 8, kFbSlots, LensKaldi80, In, Out>
-    static const Kernel table[2][3] = {{nullptr, MS_KALDI_IO(float, io_f16), MS_KALDI_IO(float, io_bf16)},
-                                       {MS_KALDI_IO(io_s16, float), MS_KALDI_IO(io_s16, io_f16), MS_KALDI_IO(io_s16, io_bf16)}};
-#undef MS_KALDI_IO
-    static std::atomic<uint64_t> attr_done[2][3];
-    if (pcm < 0 || pcm > 1 || out < 0 || out > 2 || (pcm | out) == 0 || !fbank_io_ok(fb)) return fail(MELSPEC_ERR_INTERNAL, "launch_kaldi_io: no such combination");
-    const Kernel k = table[pcm][out];
-    if (int rc = allow_big_lds_once(attr_done[pcm][out], "hipFuncSetAttribute(fbank512_kaldi_io_kernel)", k)) return rc;
-    static const int per_cu = lab_int("MELSPEC_FB_GRID_PER_CU", 1, 1, 4096);
-    const unsigned grid = grid_for_xcd((fp.b.n_units + 7) / 8, fb->dev.cus, per_cu);
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), fb->fast_lds, s, fp);
-    HIP_TRY(hipGetLastError());
-    return MELSPEC_OK;
-}
-
-// the scratch of a CMN call with 16-bit rows out on stream s: `floats` f32 rows and, behind them, `tail` 64-bit words
-int fbank_rows32(melspec_fbank *fb, uint64_t floats, size_t tail, hipStream_t s, float *&rows, uint64_t *&words) {
-    const size_t row_bytes = (static_cast<size_t>(floats) * sizeof(float) + 15) & ~static_cast<size_t>(15);
-    const int rc = fb->rows32.ensure(row_bytes + tail * sizeof(uint64_t) + 16, s);
-    rows = static_cast<float *>(fb->rows32.p());
-    words = reinterpret_cast<uint64_t *>(static_cast<char *>(fb->rows32.p()) + row_bytes);
-    return rc;
-}
-
-// The kernels of one batch of an _io call (io != 0) on an object that fbank_io_ok.  pl: the plan of the f32 call, sample offsets and
-// strides in elements; pl.desc.out is where the f32 or 16-bit rows of the wave kernel go: the caller's buffer, or -- split: CMN with
-// 16-bit rows out -- the scratch, from where cmn_io_kernel writes them to vd_out (ragged: at d_dst_off).
-int fbank_launch_io(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, int io, bool split, void *vd_out, const uint64_t *d_dst_off) {
-    const int pcm = io & 15, out_dtype = io >> 4;
-    const int kout = split ? 0 : out_dtype;           // the row type the wave kernel writes
-    const FbankFastParams fp = fbank_fast_params(fb, pl.desc);
-    // (F32 samples, f32 rows into the scratch): the existing kernel, as the f32 call's two-kernel path launches it
-    int rc = (pcm | kout) == 0 ? launch_fused512<double, kFlavorKaldi, kFbSlots, LensKaldi80>(fb->waves, fp, fb->fast_lds, fb->dev.cus, s)
-                               : launch_kaldi_io(fb, fp, pcm, kout, s);
-    if (rc || !fb->cfg.apply_cmn) return rc;
-    if (!split) return launch_cmn(fb, pl.desc, n_clips, fpc, s, nullptr);        // (S16, F32): the f32 rows are the caller's, in place
-    return launch_cmn(fb, pl.desc, n_clips, fpc, s, nullptr, vd_out, out_dtype, d_dst_off);
-}
-
-// melspec_fbank_compute_uniform_device with io = pcm_dtype | out_dtype << 4 != 0 (fbank_io_args): int16 samples and / or f16, bf16 rows
-int fbank_uniform_io(melspec_fbank *fb, const void *vd_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, void *vd_out, void *stream, int io) {
-    if (n_clips == 0) return MELSPEC_OK;
-    const uint64_t fpc = fbank_frames(fb, clip_len);
-    if (fpc == 0) return MELSPEC_OK;   // zeros((0, num_mel_bins)), src/fbank.rs:147-149
-    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if (io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
-    const int nm = fb->cfg.num_mel_bins;
-    float *d_rows = static_cast<float *>(vd_out);
-    // 16-bit rows cannot have their means subtracted in place: the wave kernel then writes f32 rows into the object's scratch
-    const bool split = (io >> 4) != 0 && fb->cfg.apply_cmn;
-    if (split) {
-        uint64_t *words;
-        if (int rc = fbank_rows32(fb, static_cast<uint64_t>(n_clips) * fpc * nm, 0, s, d_rows, words)) return rc;
-    }
-    const BatchPlan pl = plan_uniform(static_cast<const float *>(vd_pcm), d_rows, clip_stride, fpc, n_clips, nm, kFbFPW);
-    return fbank_launch_io(fb, pl, n_clips, fpc, s, io, split, vd_out, nullptr);
-}
 }  // namespace
 
 extern "C" {
@@ -1390,44 +1227,15 @@ int melspec_fbank_compute_uniform_device_io(melspec_fbank *fb, const void *d_pcm
                                             uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
     int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
     if (rc) return rc;
-    if (!io) return melspec_fbank_compute_uniform_device(fb, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_out), stream);
-    return fbank_uniform_io(fb, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, io);
+    return fbank_uniform(fb, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, io);
 }
 
-// The ragged batch on the two-kernel path (the wave-owned kernel, then the CMN per clip), whatever the batch's shape.
 int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
                                            const uint64_t *h_lengths, uint32_t n_clips, void *d_out, int out_dtype,
                                            const uint64_t *h_out_offsets, void *stream) {
     int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
     if (rc) return rc;
-    if (!io) return melspec_fbank_compute_ragged_device(fb, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_out), h_out_offsets, stream);
-    FbankRagged r;
-    bool go;
-    rc = fbank_ragged_begin(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, stream, io, r, go);
-    if (!go) return rc;
-    const std::vector<uint64_t> &frames = r.frames;
-    const uint64_t total = r.total, longest = r.longest;
-    hipStream_t s = r.s;
-    const int nm = fb->cfg.num_mel_bins;
-    float *d_rows = static_cast<float *>(d_out);
-    // CMN with 16-bit rows: the wave kernel writes f32 rows, packed in clip order, into the scratch (fbank_uniform_io); the caller's own
-    // output offsets travel behind them
-    const bool split = out_dtype != MELSPEC_OUT_F32 && fb->cfg.apply_cmn;
-    const uint64_t *d_own = nullptr;
-    if (split) {
-        uint64_t *words;
-        if ((rc = fbank_rows32(fb, total * static_cast<uint64_t>(nm), h_out_offsets ? n_clips : 0, s, d_rows, words))) return rc;
-        if (h_out_offsets) {
-            HIP_TRY(hipMemcpyAsync(words, h_out_offsets, static_cast<size_t>(n_clips) * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
-            d_own = words;
-        }
-    }
-    BatchPlan pl;
-    RaggedSlot *slot = nullptr;
-    rc = plan_ragged(fb->ragged, s, static_cast<const float *>(d_pcm), d_rows, h_offsets, frames, split ? nullptr : h_out_offsets, n_clips, nm, kFbFPW, pl, slot);
-    if (!rc) rc = fbank_launch_io(fb, pl, n_clips, longest, s, io, split, d_out, d_own ? d_own : pl.desc.d_out_off);
-    plan_ragged_done(slot, s);
-    return rc;
+    return fbank_ragged(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, io);
 }
 
 // One clip from host memory (io = 0: the f32 call): the bytes of the caller's types cross the bus, the kernels convert.
@@ -1435,23 +1243,11 @@ static int fbank_host(melspec_fbank *fb, const void *samples, size_t n_samples, 
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     if (n_frames) *n_frames = 0;
     const uint64_t frames = fbank_frames(fb, n_samples);
-    if (frames == 0) return MELSPEC_OK;
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    const uint64_t need = frames * static_cast<uint64_t>(fb->cfg.num_mel_bins);
-    if (out_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    const size_t ib = io_pcm_bytes(io & 15), ob = io_out_bytes(io >> 4);
-    int rc;
-    if ((rc = fb->h2d.ensure(n_samples * ib))) return rc;
-    if ((rc = fb->d2h.ensure(need * ob))) return rc;
-    HIP_TRY(hipMemcpyAsync(fb->h2d.p, samples, n_samples * ib, hipMemcpyHostToDevice, fb->stream));
-    rc = io ? fbank_uniform_io(fb, fb->h2d.p, n_samples, n_samples, 1, fb->d2h.p, fb->stream, io)
-            : melspec_fbank_compute_uniform_device(fb, static_cast<const float *>(fb->h2d.p), n_samples, n_samples, 1, static_cast<float *>(fb->d2h.p), fb->stream);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(out, fb->d2h.p, need * ob, hipMemcpyDeviceToHost, fb->stream));
-    HIP_TRY(hipStreamSynchronize(fb->stream));
-    if (n_frames) *n_frames = static_cast<size_t>(frames);
-    return MELSPEC_OK;
+    const int rc = host_one_clip(fb->dev.device, fb->h2d, fb->d2h, fb->stream, samples, n_samples * io_pcm_bytes(io & 15), out, out_capacity_elems,
+                                 frames * static_cast<uint64_t>(fb->cfg.num_mel_bins), io_out_bytes(io >> 4),
+                                 [&](const void *d_in, void *d_out) { return fbank_uniform(fb, d_in, n_samples, n_samples, 1, d_out, fb->stream, io); });
+    if (!rc && n_frames) *n_frames = static_cast<size_t>(frames);
+    return rc;
 }
 
 int melspec_fbank_compute_host(melspec_fbank *fb, const float *samples, size_t n_samples, float *out,

@@ -5,6 +5,7 @@
 //   whisper400.hip  launch_ctx: every n_fft = 400 kernel (f32 + guard + vote, f64), the STFT export
 //   ctx_route.hpp   route400: which of them a batch runs on, its unit size and the name reported for it (no HIP: host-testable)
 //   fbank512.hip    the fused 512-point family: Kaldi fbank (melspec_fbank_*), NeMo frontend (melspec_blm_*), Whisper at n_fft = 512
+//   fused512_route.hpp  route512: which of its kernels a batch runs on, the list of its instantiations (no HIP: host-testable)
 //   pow2.hip        generic_frame_kernel / pow2_frame_kernel / generic_stft_kernel: every other geometry, f64
 //   aux.hip         batch planners, streaming bank, TGA quantiser, VAD columns, stand-alone mel helpers, synthetic PCM
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
@@ -39,6 +40,7 @@
 #include "stream_plan.hpp"
 #include "tables.hpp"
 #include "ctx_route.hpp"
+#include "fused512_route.hpp"
 
 namespace melspec {
 namespace host {
@@ -320,6 +322,55 @@ inline unsigned grid_for_xcd(uint64_t units, int cus, int per_cu) {
     const unsigned g = grid_for(units, cus, per_cu);
     if (off) return (g % 8 == 0 && g > 1) ? g - 1 : g;
     return (g + 7u) & ~7u;
+}
+
+// ---- host memory in, host memory out: what the objects' host entry points share ---------------------------------------------------------
+// One clip through an object's two staging buffers on its stream: in_bytes of samples up, run(d_in, d_out), need_elems elements of
+// out_elem_bytes down, then the stream is waited for.  Nothing to compute (need_elems == 0): MELSPEC_OK with nothing touched.
+template <class Run>
+int host_one_clip(int device, DevBuf &h2d, DevBuf &d2h, hipStream_t stream, const void *samples, size_t in_bytes, void *out, size_t out_capacity_elems,
+                  uint64_t need_elems, size_t out_elem_bytes, Run run) {
+    if (need_elems == 0) return MELSPEC_OK;
+    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+    if (out_capacity_elems < need_elems) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(device));
+    int rc;
+    if ((rc = h2d.ensure(in_bytes))) return rc;
+    if ((rc = d2h.ensure(need_elems * out_elem_bytes))) return rc;
+    HIP_TRY(hipMemcpyAsync(h2d.p, samples, in_bytes, hipMemcpyHostToDevice, stream));
+    if ((rc = run(h2d.p, d2h.p))) return rc;
+    HIP_TRY(hipMemcpyAsync(out, d2h.p, need_elems * out_elem_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return MELSPEC_OK;
+}
+// Many host clips in one call, first half: the checks of the arguments and the clips with rows to compute.  rows_of(len): the frames
+// (or padded columns) of a clip of len samples; clip i -> rows_of * n_mels floats at out + out_offsets[i] (NULL: packed in clip order).
+template <class Rows>
+int host_segments(const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips, float *out, const uint64_t *out_offsets,
+                  size_t out_capacity_floats, uint64_t nm, Rows rows_of, std::vector<HostSeg> &segs, uint64_t &total) {
+    total = 0;
+    if (n_clips == 0) return MELSPEC_OK;
+    if (!offsets || !lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
+    segs.reserve(n_clips);
+    uint64_t cursor = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) {
+        const uint64_t f = rows_of(lengths[i]);
+        const uint64_t oo = out_offsets ? out_offsets[i] : cursor;
+        if (f && oo + f * nm > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+        if (f && (!samples || !out)) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+        if (f) segs.push_back(HostSeg{samples + offsets[i], lengths[i], out + oo, f});
+        cursor += f * nm; total += f;
+    }
+    return MELSPEC_OK;
+}
+// ... second half: whole clips in chunks of ~16 MiB of PCM through the pinned, double-buffered pipeline of host_pipe.hpp, one ragged
+// launch (the object's ragged device call) per chunk
+template <class Ragged>
+int host_pipe_run(HostPipe &pipe, const std::vector<HostSeg> &segs, int n_mels, hipStream_t stream, Ragged ragged) {
+    const char *where = "";
+    const int rc = pipe.run(segs, n_mels, kPipeChunkSamples, stream, ragged, &where);
+    if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
+    return rc;
 }
 
 // ---- pow2.hip: every geometry off the fused kernels -------------------------------------------------------------------------------

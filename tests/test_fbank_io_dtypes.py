@@ -163,11 +163,11 @@ def test_uniform_bits_are_the_f32_calls(gpu, cmn):
 
 
 def takes_clip_kernel(n_clips, cus):
-    """fbank_launch's rule (mel_spec_amd/csrc/fbank512.hip) for a uniform batch of the default object with CMN: at least one clip per CU
+    """fbank_launch's rule (clip_uniform_ok, mel_spec_amd/csrc/fused512_route.hpp) for a uniform batch of the default object with CMN: at least one clip per CU
     and the last pass over the CUs at least 85 % full.
     A RESTATEMENT, and of a part only: the rule's other conditions (apply_cmn, use_power, eight waves, a 16-byte aligned output whose
     clip stride is a multiple of four elements: Fence's, behind GUARD = 4096 elements) hold for the batches below without being checked here, and nothing observes which kernel the f32 call really ran -- the library has no hook for
-    it.  If the rule in fbank512.hip changes, this function has to change with it; otherwise test_across_the_two_f32_paths goes on passing
+    it.  If the rule in fused512_route.hpp changes, this function has to change with it; otherwise test_across_the_two_f32_paths goes on passing
     while it compares the two-kernel path with itself."""
     passes = (n_clips + cus - 1) // cus
     return n_clips >= cus and n_clips * 100 >= passes * cus * 85

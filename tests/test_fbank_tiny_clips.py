@@ -8,7 +8,8 @@ the arrival), three to five clips per workgroup, and ragged batches that end in 
 
 References, none of them the kernel under test: the oracle (with apply_cmn = 0 for the rows before CMN), and the project's other kernel
 pair -- the same clips in launches too small for the clip kernel (fused wave kernel + cmn_kernel), whose bits a clip must keep whatever
-batch it is in.  The CPU test at the end keeps the Python mirror of the host's two dispatch rules in step with fbank512.hip."""
+batch it is in.  The CPU test at the end keeps the Python mirror of the host's two dispatch rules in step with fused512_route.hpp and
+fbank512.hip."""
 import os
 import re
 
@@ -23,7 +24,7 @@ FL, FS, FPU, WAVES = 400, 160, 4, 8      # frame length, shift (16 kHz), frames 
 SMALL = 40                               # clips per launch of the two-kernel reference path (fewer than any CU count here)
 
 
-# ---- the host's dispatch rules, mirrored (fbank512.hip: fbank_launch, melspec_fbank_compute_ragged_device) -------------------------
+# ---- the host's dispatch rules, mirrored (fused512_route.hpp: clip_shape_ok, clip_uniform_ok, clip_ragged_ok) ----------------------
 
 def takes_clip_kernel_uniform(n_clips, cus, n_mels):
     """a uniform batch with CMN (power spectra, aligned output) runs on fbank512_clip_kernel"""
@@ -281,25 +282,37 @@ def test_tiny_split_without_a_frame(gpu):
 
 # ---- C: the mirror against the source (CPU) ---------------------------------------------------------------------------------------
 
-def _host_source():
-    return open(os.path.join(ROOT, "mel_spec_amd", "csrc", "fbank512.hip")).read()
+def _host_source(name="fbank512.hip"):
+    return open(os.path.join(ROOT, "mel_spec_amd", "csrc", name)).read()
+
+
+def _body(src, head):
+    """the text of the function that begins with `head`, white space folded"""
+    body = src[src.index(head):]
+    return re.sub(r"\s+", " ", body[:body.index("\n}\n")])
 
 
 def test_tiny_clips_dispatch_mirror_matches_the_host():
-    """the constants takes_clip_kernel_uniform / _ragged rely on are still in fbank512.hip, and the A1 matrix reaches the clip kernel on
-    any CU count"""
-    src = _host_source()
-    launch = src[src.index("static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc /*"):]
-    launch = launch[:launch.index("\n}\n")]
-    uniform = re.sub(r"\s+", " ", launch)
-    for piece in ("nm % 4 == 0", "nm <= 89", "n_clips >= cus", "passes = (n_clips + cus - 1) / cus",
+    """the constants takes_clip_kernel_uniform / _ragged rely on are still in the host's rules (fused512_route.hpp; the alignment of the
+    output offsets in fbank512.hip), and the A1 matrix reaches the clip kernel on any CU count"""
+    route = _host_source("fused512_route.hpp")
+    shape = _body(route, "constexpr bool clip_shape_ok(const Fused512Shape &s, int nm) {")
+    for piece in ("nm % 4 == 0", "nm <= 89"):
+        assert piece in shape, f"clip_shape_ok no longer holds `{piece}`"
+    uniform = _body(route, "constexpr bool clip_uniform_ok(uint32_t n_clips, uint32_t cus) {")
+    for piece in ("n_clips >= cus", "passes = (n_clips + cus - 1) / cus",
                   "static_cast<uint64_t>(n_clips) * 100 >= static_cast<uint64_t>(passes) * cus * 85"):
-        assert piece in uniform, f"fbank_launch no longer holds `{piece}`"
-    rag = src[src.index("int melspec_fbank_compute_ragged_device(melspec_fbank *fb"):]
-    rag = re.sub(r"\s+", " ", rag[:rag.index("\n}\n")])
-    for piece in ("nm % 4 == 0", "nm <= 89", "n_clips >= 2u * static_cast<uint32_t>(fb->dev.cus)",
-                  "longest * 2 * static_cast<uint64_t>(fb->dev.cus) <= total", "h_out_offsets[i] % 4 == 0"):
-        assert piece in rag, f"melspec_fbank_compute_ragged_device no longer holds `{piece}`"
+        assert piece in uniform, f"clip_uniform_ok no longer holds `{piece}`"
+    rag = _body(route, "constexpr bool clip_ragged_ok(uint32_t n_clips, uint32_t cus, uint64_t longest, uint64_t total) {")
+    for piece in ("n_clips >= 2u * cus", "longest * 2 * static_cast<uint64_t>(cus) <= total"):
+        assert piece in rag, f"clip_ragged_ok no longer holds `{piece}`"
+    # both entry points ask the shared rules, with the object's CU count
+    launch = _body(_host_source(), "static int fbank_launch(melspec_fbank *fb, const BatchPlan &pl, uint32_t n_clips, uint64_t fpc, hipStream_t s, int io = 0,")
+    for piece in ("cus = static_cast<uint32_t>(fb->dev.cus)", "clip_shape_ok(shape, nm)", "clip_uniform_ok(n_clips, cus)"):
+        assert piece in launch, f"fbank_launch no longer holds `{piece}`"
+    ragged = _body(_host_source(), "static int fbank_ragged(melspec_fbank *fb")
+    for piece in ("clip_shape_ok(fbank_shape(fb), nm)", "clip_ragged_ok(n_clips, static_cast<uint32_t>(fb->dev.cus), longest, total)", "h_out_offsets[i] % 4 == 0"):
+        assert piece in ragged, f"fbank_ragged no longer holds `{piece}`"
     csrc = os.path.join(ROOT, "mel_spec_amd", "csrc")
     assert "constexpr int WAVES = 8, NT = WAVES * 64;" in open(os.path.join(csrc, "fbank512_kernels.hpp")).read()
     assert re.search(r"constexpr int kFbFPW = 4;", open(os.path.join(csrc, "fbank_wave.hpp")).read())

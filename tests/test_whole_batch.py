@@ -8,7 +8,7 @@ padding is exactly 0.0, the gaps between ragged outputs still hold the sentinel 
 Batch sizes are chosen at the edges of the run-per-wave partition of the plain kernels (ClipRun::init, kernels_common.hpp: each of
 grid x waves waves takes a contiguous run of ceil(units / (grid x waves)) units; grid_for_xcd, host_common.hpp): fewer units than
 waves, exactly grid x waves units, k x grid x waves + 1 units, and runs whose boundaries fall inside clips.  The CPU test at the end
-keeps the matrix in step with melspec_plain_kernel_name (ctx_route.hpp, fbank512.hip, pow2.hip): every name it can return has a row here."""
+keeps the matrix in step with melspec_plain_kernel_name (ctx_route.hpp, fused512_route.hpp, pow2.hip): every name it can return has a row here."""
 import os
 import re
 from concurrent.futures import ThreadPoolExecutor
@@ -673,7 +673,7 @@ def plain_kernel_name_literals():
     csrc = os.path.join(ROOT, "mel_spec_amd", "csrc")
     found = set()
     for file, heads in (("ctx_route.hpp", ("inline const char *route_name(F32Kernel k, bool guarded) {", "inline const char *route_name(F64Kernel k) {")),
-                        ("fbank512.hip", ("const char *whisper512_kernel_name(const melspec_ctx *c) {",)),
+                        ("fused512_route.hpp", ("inline const char *whisper512_kernel_name(const Fused512Shape &s) {",)),
                         ("pow2.hip", ("const char *generic_kernel_name(const GenericTables &gt) {",))):
         src = open(os.path.join(csrc, file)).read()
         for head in heads:

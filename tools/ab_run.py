@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of library variants (boxes differ by several percent, so variants are interleaved and repeated):
-tools/ab_run.py [--case cfg2|cfg4|f64|fbank|fbank_split|nemo|w512|mm] name1 name2 ...   (libraries mel_spec_amd/ab/lib_<name>.so).
+tools/ab_run.py [--case cfg2|cfg4|f64|fbank|fbank_split|fbank_1clip|nemo|nemo_1clip|w512|mm] name1 name2 ...   (libraries mel_spec_amd/ab/lib_<name>.so).
 Each measurement runs in its own process (MELSPEC_LIB), event-timed, after a spin-up; prints per variant min / median over reps."""
 import os, subprocess, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -82,6 +82,10 @@ elif case in ("nemo", "nemo_norm", "nemo_f32", "nemo_norm_f32", "nemo80", "nemo8
     if case.endswith("f32"): fe.set_precision("f32")
     out = M.DeviceBuffer(n_clips * (fe.num_frames(clip_len) + 16) * 128 * 4)
     ms = wall(lambda: fe.compute_uniform_device(pcm.ptr, clip_len, clip_len, n_clips, out.ptr), fe.synchronize, 100)
+elif case in ("fbank_1clip", "nemo_1clip"):          # launch-bound: one 1 s clip per call, host overhead per call in ms
+    obj = M.Fbank() if case == "fbank_1clip" else M.BatchLogMelSpectrogram(M.BatchLogMelConfig(n_mels=80))
+    out = M.DeviceBuffer(128 * 128 * 4)
+    ms = wall(lambda: obj.compute_uniform_device(pcm.ptr, 16000, 16000, 1, out.ptr), obj.synchronize, 4000)
 print("MS", ms)
 '''
 args = sys.argv[1:]
@@ -108,4 +112,4 @@ base = statistics.median(res[args[0]]) if res[args[0]] else 0
 for n in args:
     if res[n]:
         med = statistics.median(res[n])
-        print(f"{case:6s} {n:28s} min {min(res[n]):.4f}  median {med:.4f}  ({(med / base - 1) * 100:+.2f} % vs {args[0]})  {['%.4f' % v for v in res[n]]}", flush=True)
+        print(f"{case:6s} {n:28s} min {min(res[n]):.5f}  median {med:.5f}  ({(med / base - 1) * 100:+.2f} % vs {args[0]})  {['%.5f' % v for v in res[n]]}", flush=True)
