@@ -604,6 +604,48 @@ int melspec_stream_push_device_io(melspec_stream *st, const uint32_t *ids, const
                                   const uint32_t *lens, uint32_t n, void *d_out, int out_dtype, const uint64_t *out_offsets,
                                   uint32_t *frames_out, void *stream);
 
+/* ---- streaming Kaldi fbank: Fbank::compute (src/fbank.rs:141-236) fed chunk by chunk ---- */
+/* A bank of n_streams independent streams over one melspec_fbank (its geometry, tables and kernels).  For each stream, after any
+ * sequence of pushes whose chunks concatenate to x, the rows emitted so far are exactly the rows of Fbank::compute(x) with apply_cmn = 0:
+ * frame k is emitted by the push that brings the stream to k * shift + frame_len samples -- no warm-up skip and no flush (the reference
+ * drops the tail, and so does the bank).  The rows are the bits melspec_fbank_compute_host returns for x on an object with the same
+ * config and apply_cmn = 0, however x was cut into chunks.  A push always emits rows BEFORE CMN, whatever the object's apply_cmn is
+ * (the contract of melspec_fbank_compute_uniform_device_split carried over time); the bank keeps, per stream and mel bin, an f64 sum of
+ * the emitted rows -- a left fold in frame order, so a function of the stream's samples alone -- and the frame count:
+ * melspec_fbank_stream_stats_* return mean[bin] = (float)(sum / count) and count (zero means for count == 0).  At end of stream
+ * rows - mean is the reference's CMN output to within its own f32 fold error; before that, online cumulative mean normalisation.
+ * Per stream the device keeps the samples no emitted frame starts in (< frame_len) and, in front of them, the one sample the next
+ * frame's pre-emphasis reads (src/fbank.rs:177-181: samples[start - 1]; the Povey window is 0 there, so it matters for non-finite
+ * input only -- and there the rows follow the reference).  A stream that has emitted nothing has no such sample: what lay in its slot
+ * before a reset never reaches its frame 0.
+ * The handle is opaque and crosses the ABI as void *.  The fbank must outlive the bank; one bank per host thread, like the fbank.
+ * Needs melspec_fbank_uses_fast_path(fb) == 1 and frame_shift <= frame_length: otherwise MELSPEC_ERR_UNSUPPORTED at create -- and at a
+ * push after melspec_fbank_use_generic(fb, 1) -- with melspec_last_error naming the geometry.  n_streams == 0 or max_chunk == 0, a NULL
+ * handle (no device is touched), an id out of range or twice in one push: MELSPEC_ERR_INVALID_ARG; a chunk longer than max_chunk:
+ * MELSPEC_ERR_CAPACITY.  A push that fails leaves the bank, its state and its sums as they were. */
+int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_streams, uint32_t max_chunk);
+void melspec_fbank_stream_destroy(void *st);
+/* no history, no frames, zero sums for the listed streams; ids == NULL -> all */
+int melspec_fbank_stream_reset(void *st, const uint32_t *ids, uint32_t n);
+/* rows a push of n_new samples to stream id would emit now */
+size_t melspec_fbank_stream_frames_after(const void *st, uint32_t id, uint32_t n_new);
+/* Host chunks: samples holds the n chunks back to back (lens[i] elements of pcm_dtype -- MELSPEC_PCM_F32, or MELSPEC_PCM_S16 whose value is
+ * int16 * 2^-15, exactly, converted where the chunk is copied into the f32 state -- for stream ids[i]); out receives the emitted rows
+ * [frame][num_mel_bins] f32, back to back in entry order, frames_out[i] how many entry i emitted.  Synchronous. */
+int melspec_fbank_stream_push_host(void *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                   float *out, size_t out_capacity_floats, uint32_t *frames_out);
+/* Device producers: d_chunks != NULL: chunk i is d_chunks[h_src_offsets[i] .. + lens[i]) in elements of pcm_dtype (h_src_offsets == NULL:
+ * back to back), copied into the bank on `stream`; d_chunks == NULL: the chunks are already at melspec_fbank_stream_input_ptr(st, id)
+ * (fixed per stream, 16-byte aligned, room for max_chunk samples), in f32.  Rows go to d_out + h_out_offsets[i] floats (NULL: back to
+ * back).  The launches have completed on return, as for melspec_stream_push_device. */
+float *melspec_fbank_stream_input_ptr(void *st, uint32_t id);
+int melspec_fbank_stream_push_device(void *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                     const uint32_t *lens, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out,
+                                     void *stream);
+/* means: [n][num_mel_bins] f32 of the listed streams, counts: [n] rows emitted so far (may be NULL) */
+int melspec_fbank_stream_stats_host(void *st, const uint32_t *ids, uint32_t n, float *means, uint64_t *counts);
+int melspec_fbank_stream_stats_device(void *st, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream);
+
 /* ---- 8-bit quantisation + TGA container: replaces src/quant.rs ------------------------ */
 /* The reference's wire/disk format right after the mel path: a mel-major interleaved image
  * ([n_mels][width] f32, what melspec_compute_uniform_device_interleaved(.., major_column_order = 0, ..)

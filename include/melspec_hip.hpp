@@ -233,7 +233,57 @@ public:
     void release_scratch() { detail::check(melspec_fbank_release_scratch(fb_), false); }
 
 private:
+    friend class FbankStreamBank;
     melspec_fbank *fb_ = nullptr;
+};
+
+// Fbank::compute fed chunk by chunk (melspec_fbank_stream_*): after pushes whose chunks concatenate to x a stream has emitted exactly the
+// rows of compute(x) with apply_cmn off, before CMN whatever the object's setting; stats() gives the running column means of those rows.
+// The Fbank must outlive the bank.
+class FbankStreamBank {
+public:
+    FbankStreamBank(Fbank &fbank, std::size_t n_streams, std::size_t max_chunk) : n_mels_(static_cast<std::size_t>(melspec_fbank_num_mel_bins(fbank.fb_))) {
+        detail::check(melspec_fbank_stream_create(&st_, fbank.fb_, static_cast<std::uint32_t>(n_streams), static_cast<std::uint32_t>(max_chunk)), true);
+    }
+    ~FbankStreamBank() { melspec_fbank_stream_destroy(st_); }
+    FbankStreamBank(const FbankStreamBank &) = delete;
+    FbankStreamBank &operator=(const FbankStreamBank &) = delete;
+
+    void reset() { detail::check(melspec_fbank_stream_reset(st_, nullptr, 0), false); }
+    void reset(const std::vector<std::uint32_t> &ids) { detail::check(melspec_fbank_stream_reset(st_, ids.data(), static_cast<std::uint32_t>(ids.size())), false); }
+    std::size_t frames_after(std::uint32_t id, std::size_t n_new) const { return melspec_fbank_stream_frames_after(st_, id, static_cast<std::uint32_t>(n_new)); }
+    // one chunk for one stream: the rows it completes, (frames, num_mel_bins) row-major
+    Array2f push(std::uint32_t id, const std::vector<float> &chunk) { return push_typed(id, chunk.data(), MELSPEC_PCM_F32, chunk.size()); }
+    Array2f push(std::uint32_t id, const std::vector<std::int16_t> &chunk) { return push_typed(id, chunk.data(), MELSPEC_PCM_S16, chunk.size()); }
+    float *input_ptr(std::uint32_t id) { return melspec_fbank_stream_input_ptr(st_, id); }
+    void push_device(const std::vector<std::uint32_t> &ids, const void *d_chunks, int pcm_dtype, const std::uint64_t *src_offsets, const std::vector<std::uint32_t> &lens,
+                     float *d_out, const std::uint64_t *out_offsets, std::uint32_t *frames_out, void *stream = nullptr) {
+        detail::check(melspec_fbank_stream_push_device(st_, ids.data(), d_chunks, pcm_dtype, src_offsets, lens.data(), static_cast<std::uint32_t>(ids.size()), d_out,
+                                                       out_offsets, frames_out, stream), false);
+    }
+    // mean[bin] = float(f64 sum of the stream's rows / count); count = rows emitted so far
+    std::vector<float> stats(std::uint32_t id, std::uint64_t *count = nullptr) {
+        std::vector<float> means(n_mels_);
+        detail::check(melspec_fbank_stream_stats_host(st_, &id, 1, means.data(), count), false);
+        return means;
+    }
+    void stats_device(const std::vector<std::uint32_t> &ids, float *d_means, std::uint64_t *counts, void *stream = nullptr) {
+        detail::check(melspec_fbank_stream_stats_device(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_means, counts, stream), false);
+    }
+
+private:
+    Array2f push_typed(std::uint32_t id, const void *samples, int pcm_dtype, std::size_t n) {
+        Array2f a;
+        const std::uint32_t len = static_cast<std::uint32_t>(n);
+        a.cols = n_mels_;
+        a.data.assign(frames_after(id, n) * n_mels_, 0.0f);
+        std::uint32_t got = 0;
+        detail::check(melspec_fbank_stream_push_host(st_, &id, samples, pcm_dtype, &len, 1, a.data.data(), a.data.size(), &got), false);
+        a.rows = got;
+        return a;
+    }
+    void *st_ = nullptr;
+    std::size_t n_mels_;
 };
 
 struct BatchLogMelConfig : melspec_blm_config {

@@ -182,6 +182,38 @@ void plan_ragged_done(RaggedSlot *sl, hipStream_t stream) {
     if (sl && sl->ev && hipEventRecord(sl->ev, stream) == hipSuccess) sl->pending = true;
 }
 
+// ---- what the Kaldi fbank's stream bank (fbank512.hip) shares with the bank below: a table's trip to the device through a ring slot, and
+// the scatter / carry kernels (geometry-agnostic: they read the slot stride, in_off and the entries) ----
+// the next slot of the ring with room for `bytes` (a multiple of 16) on both sides; the caller fills sl->host, then table_slot_upload
+int table_slot_take(RaggedScratch &ring, size_t bytes, RaggedSlot *&sl) {
+    sl = &ring.slot[ring.next++ % RaggedScratch::kSlots];
+    if (!sl->ev) HIP_TRY(hipEventCreateWithFlags(&sl->ev, hipEventDisableTiming));
+    if (sl->pending) { HIP_TRY(hipEventSynchronize(sl->ev)); sl->pending = false; }
+    if (int rc = sl->ensure_host(bytes)) return rc;
+    return sl->dev.ensure(bytes);
+}
+// the copy kernel on the launch stream (no SDMA queue hand-over); afterwards the slot is in use until plan_ragged_done's event
+int table_slot_upload(RaggedSlot &sl, size_t bytes, hipStream_t s) {
+    const size_t n16 = bytes / 16;
+    const unsigned blocks = static_cast<unsigned>((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
+    hipLaunchKernelGGL(plan_upload_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, static_cast<const uint4 *>(sl.host), static_cast<uint4 *>(sl.dev.p), n16);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+int stream_scatter_launch(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *d_e, uint32_t n, const void *d_src, int pcm_dtype, hipStream_t s) {
+    if (pcm_dtype == MELSPEC_PCM_S16)
+        hipLaunchKernelGGL(stream_scatter_kernel<io_s16>, dim3(n), dim3(256), 0, s, state, stride, in_off, d_e, static_cast<const io_s16 *>(d_src));
+    else
+        hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(n), dim3(256), 0, s, state, stride, in_off, d_e, static_cast<const float *>(d_src));
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+int stream_carry_launch(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *d_e, uint32_t n, hipStream_t s) {
+    hipLaunchKernelGGL(stream_carry_kernel, dim3(n), dim3(256), 0, s, state, stride, in_off, d_e);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
 int plan_ragged_device(DevicePlan &dp, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *d_off, const uint64_t *d_len,
                        const uint64_t *d_out_off, uint32_t n_clips, uint64_t frame_len, uint64_t frame_shift, uint32_t words_per_frame,
                        int frames_per_unit, uint64_t max_total_frames, BatchPlan &pl) {

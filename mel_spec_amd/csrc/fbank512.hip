@@ -5,7 +5,9 @@
 #include "fbank512_io_kernels.hpp"
 #include "fbank512_kaldi_io_kernels.hpp"
 #include "fbank512_stats_kernels.hpp"
+#include "fbank512_stream_kernels.hpp"
 #include "blm_stats_plan.hpp"
+#include "fbank_stream_plan.hpp"
 
 namespace melspec {
 // emitted by fbank512_io.hip / fbank512_kaldi_io.hip: the NeMo frontend and the Kaldi fbank with int16 PCM in and / or f16, bf16 rows out
@@ -22,6 +24,10 @@ extern template __global__ void cmn_io_kernel<io_bf16>(const CmnIoParams);
 #define MS_STATS_EXTERN(name, T, W, N, L) extern template __global__ void fbank512_nemo_stats_kernel<T, W, N, L>(const FbankStatsParams);
 MS_K512_STATS(MS_STATS_EXTERN)
 #undef MS_STATS_EXTERN
+// emitted by fbank512_stream.hip: the Kaldi fbank's stream bank (the plain kernels with a "continues" flag per clip)
+#define MS_STREAM_EXTERN(name, T, W, N, L, R) extern template __global__ void fbank512_stream_kernel<T, W, N, L, R>(const FbankStreamParams);
+MS_K512_STREAM(MS_STREAM_EXTERN)
+#undef MS_STREAM_EXTERN
 }  // namespace melspec
 
 namespace {
@@ -38,25 +44,31 @@ MS_K512_WAVE(MS_WAVE)
 #define MS_CLIP(name, N, L, R) &fbank512_clip_kernel<N, L, R>,
 #define MS_STATS(name, T, W, N, L) &fbank512_nemo_stats_kernel<T, W, N, L>,
 #define MS_AUTO(name, T, W, N, L) &w512_auto_kernel<T, W, N, L>,
+#define MS_STREAM(name, T, W, N, L, R) &fbank512_stream_kernel<T, W, N, L, R>,
 void (*const kFastKernels[])(const FbankFastParams) = {MS_K512_WAVE(MS_WAVE) MS_K512_IO(MS_IO)};
 void (*const kClipKernels[])(const FbankClipParams) = {MS_K512_CLIP(MS_CLIP)};
 void (*const kStatsKernels[])(const FbankStatsParams) = {MS_K512_STATS(MS_STATS)};
 void (*const kAutoKernels[])(const W512AutoParams) = {MS_K512_AUTO(MS_AUTO)};
+void (*const kStreamKernels[])(const FbankStreamParams) = {MS_K512_STREAM(MS_STREAM)};
 #undef MS_WAVE
 #undef MS_IO
 #undef MS_CLIP
 #undef MS_STATS
 #undef MS_AUTO
+#undef MS_STREAM
 constexpr int idx(K512 k) { return static_cast<int>(k); }
 static_assert(sizeof(kFastKernels) / sizeof(kFastKernels[0]) == idx(K512::kClip80) && sizeof(kClipKernels) / sizeof(kClipKernels[0]) == idx(K512::kStats128) - idx(K512::kClip80) &&
               sizeof(kStatsKernels) / sizeof(kStatsKernels[0]) == idx(K512::kAuto80Vote) - idx(K512::kStats128) &&
-              sizeof(kAutoKernels) / sizeof(kAutoKernels[0]) == idx(K512::kCount) - idx(K512::kAuto80Vote), "one kernel per K512, in the order of the lists");
+              sizeof(kAutoKernels) / sizeof(kAutoKernels[0]) == idx(K512::kCount) - idx(K512::kAuto80Vote) &&
+              sizeof(kStreamKernels) / sizeof(kStreamKernels[0]) == idx(K512::kEnd) - idx(K512::kStream80) && idx(K512::kStream80) == idx(K512::kCount),
+              "one kernel per K512, in the order of the lists");
 static_assert(kFused512F32Waves == 12, "fused512_route.hpp spells the f32 kernels' waves out");
 
 inline auto kernel512(K512 k, const FbankFastParams &) { return is_fast(k) ? kFastKernels[idx(k)] : nullptr; }
 inline auto kernel512(K512 k, const FbankClipParams &) { return is_clip(k) ? kClipKernels[idx(k) - idx(K512::kClip80)] : nullptr; }
 inline auto kernel512(K512 k, const FbankStatsParams &) { return is_stats(k) ? kStatsKernels[idx(k) - idx(K512::kStats128)] : nullptr; }
 inline auto kernel512(K512 k, const W512AutoParams &) { return is_auto(k) ? kAutoKernels[idx(k) - idx(K512::kAuto80Vote)] : nullptr; }
+inline auto kernel512(K512 k, const FbankStreamParams &) { return is_stream(k) ? kStreamKernels[idx(k) - idx(K512::kStream80)] : nullptr; }
 inline const BatchDesc &batch_of(const FbankFastParams &p) { return p.b; }
 template <class P> const BatchDesc &batch_of(const P &q) { return q.f.b; }
 
@@ -80,14 +92,14 @@ unsigned grid512(const Launch512 &l, uint64_t n_units, int cus) {
 }
 const char *attr_name(K512 k) {
     return is_clip(k) ? "hipFuncSetAttribute(fbank512_clip_kernel)" : is_stats(k) ? "hipFuncSetAttribute(fbank512_nemo_stats_kernel)"
-         : is_auto(k) ? "hipFuncSetAttribute(w512_auto_kernel)" : k >= K512::kKaldiIo80 ? "hipFuncSetAttribute(fbank512_kaldi_io_kernel)"
+         : is_auto(k) ? "hipFuncSetAttribute(w512_auto_kernel)" : is_stream(k) ? "hipFuncSetAttribute(fbank512_stream_kernel)" : k >= K512::kKaldiIo80 ? "hipFuncSetAttribute(fbank512_kaldi_io_kernel)"
          : is_io(k) ? "hipFuncSetAttribute(fbank512_nemo_io_kernel)" : info_of(k).f32 ? "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)"
                     : "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)";
 }
 // one launch of a route with the parameters of its kernel's group; z: the object's LDS sizes
 template <class P>
 int launch512(const Launch512 &l, const P &p, const Lds512Sizes &z, int cus, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done[idx(K512::kCount)];          // one bit per device: function attributes are per device
+    static std::atomic<uint64_t> attr_done[idx(K512::kEnd)];          // one bit per device: function attributes are per device
     const auto kernel = kernel512(l.kernel, p);
     if (!kernel) return fail(MELSPEC_ERR_INTERNAL, "launch512: the object has no kernel for this batch");
     if (int rc = allow_big_lds_once(attr_done[idx(l.kernel)], attr_name(l.kernel), kernel)) return rc;
@@ -1260,6 +1272,280 @@ int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pc
     int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
     if (rc) return rc;
     return fbank_host(fb, samples, n_samples, out, out_capacity_elems, n_frames, io);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------
+// Kaldi fbank: the stream bank (melspec_fbank_stream_*): see include/melspec_hip.h.  Bookkeeping in fbank_stream_plan.hpp, kernels in
+// fbank512_stream_kernels.hpp; scatter, carry and the tables' trip to the device are the Whisper bank's (aux.hip).
+// ------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kFbankStreamMagic = 0x4b53424du;      // the handle crosses the ABI as void *: every call checks what it was given
+
+struct FbankStreamBank {
+    uint32_t magic = kFbankStreamMagic;
+    melspec_fbank *fb = nullptr;         // geometry, tables, kernels; not owned
+    FbankStreamGeom geom{};
+    FbankStreamBook book;                // total / emitted / pending per stream (host side of the state)
+    DevBuf state, sums, counts;          // [n_streams][stride] f32, [n_streams][bins] f64, [n_streams] u64
+    DevBuf staging, out, means;          // the host calls' buffers
+    RaggedScratch ring, plan_ring;       // per-push entry tables / ragged plans
+};
+
+FbankStreamBank *fbs_of(void *h) {
+    FbankStreamBank *st = static_cast<FbankStreamBank *>(h);
+    return st && st->magic == kFbankStreamMagic ? st : nullptr;
+}
+const FbankStreamBank *fbs_of(const void *h) { return fbs_of(const_cast<void *>(h)); }
+
+// the objects a bank can stand on: the fused 512-point path (every kernel of MS_K512_STREAM), frames that overlap or abut
+int fbs_supported(const melspec_fbank *fb) {
+    if (melspec_fbank_uses_fast_path(fb) && fb->frame_shift <= fb->frame_len) return MELSPEC_OK;
+    char geo[256];
+    std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d", fb->cfg.sample_rate,
+                  fb->frame_len, fb->frame_shift, fb->cfg.num_mel_bins);
+    g_last_error = std::string("the fbank stream bank runs on the fused fbank path (400-sample frames) with frame_shift <= frame_length; this object is ") + geo +
+                   (fb->use_generic ? " on the generic path (melspec_fbank_use_generic)" : (fb->fast ? "" : " (generic path)"));
+    return MELSPEC_ERR_UNSUPPORTED;
+}
+
+int fbs_plan(FbankStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, FbankStreamPlan &pl) {
+    const char *err = nullptr;
+    const int rc = fbank_stream_plan_push(st->geom, st->book, ids, lens, n, pl, &err);
+    if (rc == 1) return fail(MELSPEC_ERR_INVALID_ARG, err);
+    if (rc == 2) return fail(MELSPEC_ERR_CAPACITY, err);
+    return MELSPEC_OK;
+}
+
+inline size_t round16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
+
+// scatter (d_src != NULL) -> frames -> column sums -> carry, all on one stream; the launches have completed on return
+int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const void *d_src, int pcm_dtype, const uint64_t *h_src_off, float *d_out,
+            const uint64_t *h_out_off, hipStream_t s) {
+    melspec_fbank *fb = st->fb;
+    if (pl.total_frames && !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");      // before anything is queued
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    const int nm = fb->cfg.num_mel_bins;
+    // the entries and, behind them, the clips' continues flags travel like a ragged plan
+    struct SlotGuard { RaggedSlot *sl; hipStream_t s; ~SlotGuard() { plan_ragged_done(sl, s); } } slot_guard{nullptr, s};
+    const size_t ebytes = round16(static_cast<size_t>(n) * sizeof(StreamEntry)), bytes = ebytes + round16(static_cast<size_t>(n) * sizeof(uint32_t));
+    RaggedSlot *sl = nullptr;
+    int rc = table_slot_take(st->ring, bytes, sl);
+    if (rc) return rc;
+    StreamEntry *h_e = static_cast<StreamEntry *>(sl->host);
+    std::memcpy(h_e, pl.entries.data(), static_cast<size_t>(n) * sizeof(StreamEntry));
+    for (uint32_t i = 0; i < n; ++i) {
+        if (h_out_off) h_e[i].out_off = h_out_off[i];          // caller-placed rows: the column sums read them where they are
+        if (h_src_off) h_e[i].src_off = h_src_off[i];
+    }
+    std::memcpy(static_cast<char *>(sl->host) + ebytes, pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t));
+    slot_guard.sl = sl;
+    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
+    const StreamEntry *d_e = static_cast<const StreamEntry *>(sl->dev.p);
+    const uint32_t *d_cont = reinterpret_cast<const uint32_t *>(static_cast<const char *>(sl->dev.p) + ebytes);
+    float *state = static_cast<float *>(st->state.p);
+    if (d_src && (rc = stream_scatter_launch(state, st->geom.stride, st->geom.in_off, d_e, n, d_src, pcm_dtype, s))) return rc;
+    if (pl.total_frames) {
+        BatchPlan bp;
+        RaggedSlot *pslot = nullptr;
+        rc = plan_ragged(st->plan_ring, s, state, d_out, pl.off.data(), pl.frames, h_out_off ? h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
+        if (!rc) {
+            FbankStreamParams q{};
+            q.f = fbank_fast_params(fb, bp.desc);
+            q.d_cont = d_cont;
+            rc = launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, nm}, fb->dev.cus, s);
+        }
+        plan_ragged_done(pslot, s);
+        if (rc) return rc;
+        FbankStreamSumParams sp{};
+        sp.entries = d_e; sp.rows = d_out; sp.sums = static_cast<double *>(st->sums.p); sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
+        hipLaunchKernelGGL(fbank_stream_sum_kernel, dim3(n), dim3(kFbankStreamSumThreads), 0, s, sp);
+        HIP_TRY(hipGetLastError());
+    }
+    if ((rc = stream_carry_launch(state, st->geom.stride, st->geom.in_off, d_e, n, s))) return rc;
+    HIP_TRY(hipStreamSynchronize(s));
+    return MELSPEC_OK;
+}
+
+// what every push checks first: the handle, the dtype code, the object
+int fbs_push_args(FbankStreamBank *st, int pcm_dtype) {
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
+    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    return fbs_supported(st->fb);
+}
+}  // namespace
+
+extern "C" {
+
+int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_streams, uint32_t max_chunk) {
+    if (!out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
+    *out = nullptr;
+    if (n_streams == 0 || max_chunk == 0) return fail(MELSPEC_ERR_INVALID_ARG, "n_streams and max_chunk must be > 0");
+    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
+    if (int rc = fbs_supported(fb)) return rc;
+    FbankStreamBank *st = new (std::nothrow) FbankStreamBank();
+    if (!st) return fail(MELSPEC_ERR_INTERNAL, "out of host memory");
+    st->fb = fb;
+    st->geom = fbank_stream_geometry(static_cast<uint32_t>(fb->frame_len), static_cast<uint32_t>(fb->frame_shift), static_cast<uint32_t>(fb->cfg.num_mel_bins),
+                                     n_streams, max_chunk);
+    st->book.reset(n_streams);
+    auto bail = [&](int code) { melspec_fbank_stream_destroy(st); return code; };
+    if (hipSetDevice(fb->dev.device) != hipSuccess) return bail(fail(MELSPEC_ERR_UNAVAILABLE, "hipSetDevice failed"));
+    const size_t state_bytes = static_cast<size_t>(n_streams) * st->geom.stride * sizeof(float) + 64;
+    const size_t sum_bytes = static_cast<size_t>(n_streams) * st->geom.n_mels * sizeof(double), count_bytes = static_cast<size_t>(n_streams) * sizeof(unsigned long long);
+    int rc;
+    if ((rc = st->state.ensure(state_bytes)) || (rc = st->sums.ensure(sum_bytes)) || (rc = st->counts.ensure(count_bytes))) return bail(rc);
+    if (hipMemset(st->state.p, 0, state_bytes) != hipSuccess || hipMemset(st->sums.p, 0, sum_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess)
+        return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
+    *out = st;
+    return MELSPEC_OK;
+}
+
+void melspec_fbank_stream_destroy(void *h) {
+    FbankStreamBank *st = fbs_of(h);
+    if (!st) return;
+    if (st->fb) { (void)hipSetDevice(st->fb->dev.device); (void)hipStreamSynchronize(st->fb->stream); }
+    st->state.release(); st->sums.release(); st->counts.release(); st->staging.release(); st->out.release(); st->means.release();
+    st->ring.release(); st->plan_ring.release();
+    st->magic = 0;
+    delete st;
+}
+
+int melspec_fbank_stream_reset(void *h, const uint32_t *ids, uint32_t n) {
+    FbankStreamBank *st = fbs_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
+    const FbankStreamGeom &g = st->geom;
+    if (ids)
+        for (uint32_t i = 0; i < n; ++i)
+            if (ids[i] >= g.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
+    HIP_TRY(hipSetDevice(st->fb->dev.device));
+    hipStream_t s = st->fb->stream;
+    const size_t row = static_cast<size_t>(g.n_mels) * sizeof(double);
+    if (!ids) {
+        HIP_TRY(hipMemsetAsync(st->state.p, 0, static_cast<size_t>(g.n_streams) * g.stride * sizeof(float), s));
+        HIP_TRY(hipMemsetAsync(st->sums.p, 0, g.n_streams * row, s));
+        HIP_TRY(hipMemsetAsync(st->counts.p, 0, static_cast<size_t>(g.n_streams) * sizeof(unsigned long long), s));
+        st->book.reset(g.n_streams);
+    } else {
+        for (uint32_t i = 0; i < n; ++i) {
+            HIP_TRY(hipMemsetAsync(static_cast<float *>(st->state.p) + ids[i] * g.stride, 0, g.in_off * sizeof(float), s));
+            HIP_TRY(hipMemsetAsync(static_cast<char *>(st->sums.p) + ids[i] * row, 0, row, s));
+            HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
+            st->book.reset_one(ids[i]);
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return MELSPEC_OK;
+}
+
+size_t melspec_fbank_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) {
+    const FbankStreamBank *st = fbs_of(h);
+    if (!st || id >= st->geom.n_streams) return 0;
+    return fbank_stream_frames_after(st->geom, st->book, id, n_new);
+}
+
+float *melspec_fbank_stream_input_ptr(void *h, uint32_t id) {
+    FbankStreamBank *st = fbs_of(h);
+    if (!st || id >= st->geom.n_streams) return nullptr;
+    return static_cast<float *>(st->state.p) + id * st->geom.stride + st->geom.in_off;
+}
+
+int melspec_fbank_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
+                                   size_t out_capacity_floats, uint32_t *frames_out) {
+    FbankStreamBank *st = fbs_of(h);
+    if (int rc = fbs_push_args(st, pcm_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    FbankStreamPlan pl;
+    int rc = fbs_plan(st, ids, lens, n, pl);
+    if (rc) return rc;
+    const uint64_t need = pl.total_frames * static_cast<uint64_t>(st->geom.n_mels);
+    if (need > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    if (need && !out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n; ++i) total += lens[i];
+    if (total && !samples) return fail(MELSPEC_ERR_INVALID_ARG, "samples is NULL");
+    melspec_fbank *fb = st->fb;
+    hipStream_t s = fb->stream;
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    const size_t ssz = io_pcm_bytes(pcm_dtype);
+    if ((rc = st->staging.ensure(total * ssz + 16))) return rc;
+    if ((rc = st->out.ensure(need * sizeof(float) + 16))) return rc;
+    if (total) HIP_TRY(hipMemcpyAsync(st->staging.p, samples, total * ssz, hipMemcpyHostToDevice, s));
+    if ((rc = fbs_run(st, pl, n, total ? st->staging.p : nullptr, pcm_dtype, nullptr, static_cast<float *>(st->out.p), nullptr, s))) return rc;
+    if (need) {
+        HIP_TRY(hipMemcpyAsync(out, st->out.p, need * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
+    if (frames_out)
+        for (uint32_t i = 0; i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
+    return MELSPEC_OK;
+}
+
+int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                     uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    FbankStreamBank *st = fbs_of(h);
+    if (int rc = fbs_push_args(st, pcm_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
+        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
+    if ((reinterpret_cast<uintptr_t>(d_chunks) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    FbankStreamPlan pl;
+    int rc = fbs_plan(st, ids, lens, n, pl);
+    if (rc) return rc;
+    if ((rc = fbs_run(st, pl, n, d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
+                      stream ? static_cast<hipStream_t>(stream) : st->fb->stream))) return rc;
+    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
+    if (frames_out)
+        for (uint32_t i = 0; i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
+    return MELSPEC_OK;
+}
+
+int melspec_fbank_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream) {
+    FbankStreamBank *st = fbs_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
+    if (!d_means) return fail(MELSPEC_ERR_INVALID_ARG, "d_means is NULL");
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= st->geom.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
+    HIP_TRY(hipSetDevice(st->fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st->fb->stream;
+    const size_t bytes = round16(static_cast<size_t>(n) * sizeof(uint32_t));
+    RaggedSlot *sl = nullptr;
+    int rc = table_slot_take(st->ring, bytes, sl);
+    if (rc) return rc;
+    std::memcpy(sl->host, ids, static_cast<size_t>(n) * sizeof(uint32_t));
+    struct SlotGuard { RaggedSlot *sl; hipStream_t s; ~SlotGuard() { plan_ragged_done(sl, s); } } slot_guard{sl, s};
+    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
+    FbankStreamMeanParams mp{};
+    mp.ids = static_cast<const uint32_t *>(sl->dev.p); mp.sums = static_cast<const double *>(st->sums.p);
+    mp.counts = static_cast<const unsigned long long *>(st->counts.p); mp.means = d_means; mp.n = n; mp.n_mels = static_cast<int>(st->geom.n_mels);
+    const uint64_t total = static_cast<uint64_t>(n) * st->geom.n_mels;
+    hipLaunchKernelGGL(fbank_stream_mean_kernel, dim3(grid_for((total + kFbankStreamSumThreads - 1) / kFbankStreamSumThreads, st->fb->dev.cus, 8)),
+                       dim3(kFbankStreamSumThreads), 0, s, mp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_counts)
+        for (uint32_t i = 0; i < n; ++i) h_counts[i] = st->book.emitted[ids[i]];
+    return MELSPEC_OK;
+}
+
+int melspec_fbank_stream_stats_host(void *h, const uint32_t *ids, uint32_t n, float *means, uint64_t *counts) {
+    FbankStreamBank *st = fbs_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
+    if (n == 0) return MELSPEC_OK;
+    if (!means) return fail(MELSPEC_ERR_INVALID_ARG, "means is NULL");
+    HIP_TRY(hipSetDevice(st->fb->dev.device));
+    const size_t bytes = static_cast<size_t>(n) * st->geom.n_mels * sizeof(float);
+    if (int rc = st->means.ensure(bytes + 16)) return rc;
+    if (int rc = melspec_fbank_stream_stats_device(h, ids, n, static_cast<float *>(st->means.p), counts, st->fb->stream)) return rc;
+    HIP_TRY(hipMemcpy(means, st->means.p, bytes, hipMemcpyDeviceToHost));
+    return MELSPEC_OK;
 }
 
 }  // extern "C"

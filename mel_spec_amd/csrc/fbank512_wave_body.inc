@@ -3,6 +3,9 @@
 // flavour) and fbank512_kaldi_io_kernel (fbank512_kaldi_io_kernels.hpp: the same ends, Kaldi flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
 // MS_FB512_STATS (fbank512_nemo_stats_kernel, fbank512_stats_kernels.hpp: NeMo flavour, parameter q around p): the per-block partials of the
 // split output next to the rows; without the macro the text below is what it always was.
+// MS_FB512_CONTINUES (fbank512_stream_kernel, fbank512_stream_kernels.hpp: Kaldi flavour, parameter q around p): q.d_cont[clip] != 0 says
+// that the clip continues a stream -- the sample in front of its first frame exists and is that frame's predecessor (src/fbank.rs:177-181);
+// without the macro the text below is what it always was.
     using L = FbankLayout<T>;
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
     const int tid = threadIdx.x;
@@ -85,7 +88,11 @@
             // from ONE set of loads (fb_kaldi_input)
             if (act) {
                 cpx<T> x[16];
+#ifdef MS_FB512_CONTINUES
+                fb_kaldi_input<T>(frame, j, preemph, f0 + fl == 0 && !q.d_cont[loc.clip] && j == 0, tblob, x);
+#else
                 fb_kaldi_input<T>(frame, j, preemph, f0 + fl == 0 && j == 0, tblob, x);
+#endif
                 fb_column_finish<T>(x, j, tblob, slice + fl * L::kXStride);
             }
         } else if constexpr (FLAVOR == kFlavorWhisper) {

@@ -67,13 +67,24 @@ namespace host {
     X(kAuto80Gated, double, 8, kFbSlots, LensSlaney80W)          \
     X(kAuto128Vote, float, 12, kBlmSlots, LensSlaney128)         \
     X(kAuto128Gated, double, 8, kBlmSlots, LensSlaney128)
+// FbankStreamParams, fbank512_stream_kernel<T, WAVES, NSLOTS, LENS, RUNS> (fbank512_stream_kernels.hpp): the Kaldi flavour whose clips are
+// the pushes of the fbank stream bank, with a "continues" flag per clip.  One per kernel a plain batch of a Kaldi object can run on, with
+// that kernel's template arguments: X(name, T, WAVES, NSLOTS, LENS, RUNS)
+#define MS_K512_STREAM(X)                                        \
+    X(kStream80, double, 8, kFbSlots, LensKaldi80, true)         \
+    X(kStream40, double, 8, kFbSlots, LensKaldi40, true)         \
+    X(kStreamRt, double, 8, kFbSlots, LensRuntime, true)         \
+    X(kStreamRt4, double, 4, kFbSlots, LensRuntime, false)
 
 enum class K512 : int {
     kNone = -1,
 #define MS_X(name, ...) name,
     MS_K512_WAVE(MS_X) MS_K512_IO(MS_X) MS_K512_CLIP(MS_X) MS_K512_STATS(MS_X) MS_K512_AUTO(MS_X)
+    kCount,                    // the kernels of the batch calls end here; the stream bank's follow
+    kStreamBase = kCount - 1,
+    MS_K512_STREAM(MS_X)
 #undef MS_X
-    kCount,
+    kEnd,
 };
 constexpr K512 operator+(K512 k, int i) { return static_cast<K512>(static_cast<int>(k) + i); }
 
@@ -89,7 +100,9 @@ constexpr K512Info info_of(K512 k) {
 #define MS_X_IO(name, In, Out, fam, T, W, N, L) case K512::name: return {W, sizeof(T) == 4, k512_same(#fam, "kaldi"), false};   // (the Kaldi _io kernel has the RUNS body)
 #define MS_X_CLIP(name, N, L, R) case K512::name: return {8, false, false, k512_same(#L, "LensRuntime")};
 #define MS_X_T(name, T, W, N, L) case K512::name: return {W, sizeof(T) == 4, false, false};
-        MS_K512_WAVE(MS_X_WAVE) MS_K512_IO(MS_X_IO) MS_K512_CLIP(MS_X_CLIP) MS_K512_STATS(MS_X_T) MS_K512_AUTO(MS_X_T)
+#define MS_X_STREAM(name, T, W, N, L, R) case K512::name: return {W, sizeof(T) == 4, R, k512_same(#L, "LensRuntime")};
+        MS_K512_WAVE(MS_X_WAVE) MS_K512_IO(MS_X_IO) MS_K512_CLIP(MS_X_CLIP) MS_K512_STATS(MS_X_T) MS_K512_AUTO(MS_X_T) MS_K512_STREAM(MS_X_STREAM)
+#undef MS_X_STREAM
 #undef MS_X_WAVE
 #undef MS_X_IO
 #undef MS_X_CLIP
@@ -97,12 +110,13 @@ constexpr K512Info info_of(K512 k) {
         default: return {0, false, false, false};
     }
 }
-// the four groups, in the order of the lists
+// the groups, in the order of the lists
 constexpr bool is_fast(K512 k) { return k >= K512::kKaldi80 && k < K512::kClip80; }
 constexpr bool is_io(K512 k) { return k >= K512::kNemoIo128 && k < K512::kClip80; }
 constexpr bool is_clip(K512 k) { return k >= K512::kClip80 && k < K512::kStats128; }
 constexpr bool is_stats(K512 k) { return k >= K512::kStats128 && k < K512::kAuto80Vote; }
 constexpr bool is_auto(K512 k) { return k >= K512::kAuto80Vote && k < K512::kCount; }
+constexpr bool is_stream(K512 k) { return k >= K512::kStream80 && k < K512::kEnd; }
 
 // ---- one launch ---------------------------------------------------------------------------------------------------------------------
 // dynamic LDS of a launch: the object's f64 size, its f32 size, the f64 size plus the clip kernel's CMN block or plus RoundStats
@@ -146,6 +160,7 @@ enum class Batch512 {
     kStats,          // the NeMo frontend's split output: rows + the partials of the row statistics
     kClipUniform,    // Kaldi + CMN, a workgroup per clip: equal clips
     kClipRagged,     // ... clips of any length, handed out by the plan's d_order
+    kStream,         // Kaldi: the pushes of the fbank stream bank as a ragged plain batch, a "continues" flag per clip, rows before CMN
 };
 constexpr int kSyncKeep = -2;      // Route512::sync_rounds: what the plan or the caller chose stays
 
@@ -232,6 +247,8 @@ inline Route512 route512(const Fused512Shape &s, Batch512 kind, int io = 0) {
             if (!four) k = (kind == Batch512::kClipRagged ? K512::kClip80Ragged : K512::kClip80) + b;
         } else if (kind == Batch512::kIo) {
             if (kaldi_io_ok(s) && io_index(io) >= 0) k = K512::kKaldiIo80 + io_index(io);
+        } else if (kind == Batch512::kStream) {
+            k = four ? K512::kStreamRt4 : K512::kStream80 + b;          // the plain batch's kernel (below) with the flag: the same rows, bit for bit
         } else if (kind != Batch512::kStats) {
             k = four ? K512::kKaldiRt4 : K512::kKaldi80 + (2 * b + (plain ? 1 : 0));
         }

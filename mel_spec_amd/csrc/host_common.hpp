@@ -296,6 +296,12 @@ int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
                 int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order = false);
 void plan_ragged_done(RaggedSlot *sl, hipStream_t stream);
+// a table of a stream bank's push on its way to the device through a ring slot, and the launches of the scatter / carry kernels
+// (aux_kernels.hpp) for the banks outside aux.hip  (aux.hip)
+int table_slot_take(RaggedScratch &ring, size_t bytes, RaggedSlot *&sl);
+int table_slot_upload(RaggedSlot &sl, size_t bytes, hipStream_t s);
+int stream_scatter_launch(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *d_e, uint32_t n, const void *d_src, int pcm_dtype, hipStream_t s);
+int stream_carry_launch(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *d_e, uint32_t n, hipStream_t s);
 
 // Ragged plan built on the device from descriptors that live there (plan_ragged_device_kernel).  One buffer per object, used in
 // stream order (a call on another stream first waits for the stream that used it last).

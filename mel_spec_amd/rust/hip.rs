@@ -130,6 +130,19 @@ unsafe extern "C" {
     fn melspec_stream_push_device_io(st: *mut Stream, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
                                      lens: *const u32, n: u32, d_out: *mut c_void, out_dtype: c_int, out_offsets: *const u64,
                                      frames_out: *mut u32, stream: *mut c_void) -> c_int;
+    // Fbank::compute fed chunk by chunk: rows before CMN + running column means (the handle crosses the ABI as void *)
+    fn melspec_fbank_stream_create(out: *mut *mut c_void, fb: *mut FbankHandle, n_streams: u32, max_chunk: u32) -> c_int;
+    fn melspec_fbank_stream_destroy(st: *mut c_void);
+    fn melspec_fbank_stream_reset(st: *mut c_void, ids: *const u32, n: u32) -> c_int;
+    fn melspec_fbank_stream_frames_after(st: *const c_void, id: u32, n_new: u32) -> usize;
+    fn melspec_fbank_stream_push_host(st: *mut c_void, ids: *const u32, samples: *const c_void, pcm_dtype: c_int, lens: *const u32, n: u32,
+                                      out: *mut f32, out_capacity_floats: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_fbank_stream_input_ptr(st: *mut c_void, id: u32) -> *mut f32;
+    fn melspec_fbank_stream_push_device(st: *mut c_void, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
+                                        lens: *const u32, n: u32, d_out: *mut f32, h_out_offsets: *const u64, frames_out: *mut u32,
+                                        stream: *mut c_void) -> c_int;
+    fn melspec_fbank_stream_stats_host(st: *mut c_void, ids: *const u32, n: u32, means: *mut f32, counts: *mut u64) -> c_int;
+    fn melspec_fbank_stream_stats_device(st: *mut c_void, ids: *const u32, n: u32, d_means: *mut f32, h_counts: *mut u64, stream: *mut c_void) -> c_int;
 }
 
 #[repr(C)]

@@ -233,6 +233,99 @@ class StreamBank:
         return frames
 
 
+class FbankStreamBank:
+    """n_streams independent Fbank::compute streams (src/fbank.rs:141-236) on one Fbank's geometry (melspec_fbank_stream_*): after pushes
+    whose chunks concatenate to x a stream has emitted exactly the rows of Fbank::compute(x) with apply_cmn off -- the bits of
+    Fbank.compute on an apply_cmn = False twin, however x was cut -- and stats() returns the running column means of those rows.
+    The Fbank must be on the fused path (uses_fast_path) with frame_shift <= frame_length."""
+
+    def __init__(self, fbank, n_streams: int, max_chunk: int):
+        self._fbank = fbank                  # keeps the object alive
+        self._h = None
+        self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), fbank.num_mel_bins
+        h = C.c_void_p()
+        _check(lib().melspec_fbank_stream_create(C.byref(h), fbank._h, self.n_streams, self.max_chunk), construct=True)
+        self._h = h
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            lib().melspec_fbank_stream_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        """no history, no frames, zero sums for the listed streams (None: all)"""
+        if ids is None:
+            _check(lib().melspec_fbank_stream_reset(self._h, None, 0))
+        else:
+            a = _u32(ids)
+            _check(lib().melspec_fbank_stream_reset(self._h, a.ctypes.data_as(_u32p), a.shape[0]))
+
+    def frames_after(self, stream: int, n_new: int) -> int:
+        return int(lib().melspec_fbank_stream_frames_after(self._h, stream, n_new))
+
+    def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
+        """Append chunks[i] (any length <= max_chunk; np.int16 chunks are 16-bit PCM, value = sample / 32768 exactly, and all chunks of
+        one call have the same dtype) to stream ids[i]; returns the rows each stream emitted, [k_i, num_mel_bins], before CMN."""
+        a = _u32(ids)
+        arrs = [np.asarray(c) for c in chunks]
+        assert len(arrs) == a.shape[0]
+        s16 = [x.dtype == np.int16 for x in arrs]
+        if any(s16) and not all(s16):
+            raise ValueError("all chunks of one push must have the same dtype (np.int16, or float)")
+        pcm = PCM_S16 if arrs and all(s16) else PCM_F32
+        xs = [np.ascontiguousarray(x).ravel() if pcm == PCM_S16 else _f32(x).ravel() for x in arrs]
+        lens = _u32([x.shape[0] for x in xs])
+        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
+        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        out = np.empty((cap, self.n_mels), np.float32)
+        frames = np.zeros(a.shape[0], np.uint32)
+        _check(lib().melspec_fbank_stream_push_host(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
+                                                    a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
+        assert int(frames.sum()) == cap
+        res, cur = [], 0
+        for f in frames:
+            res.append(out[cur:cur + int(f)])
+            cur += int(f)
+        return res
+
+    def input_ptr(self, stream: int) -> int:
+        return int(lib().melspec_fbank_stream_input_ptr(self._h, stream) or 0)
+
+    def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, d_chunks: int = 0, pcm_dtype: int = PCM_F32,
+                    src_offsets=None, stream: int = 0) -> np.ndarray:
+        """d_chunks == 0: the chunks are at input_ptr, in f32; otherwise chunk i is lens[i] elements of pcm_dtype at d_chunks +
+        src_offsets[i] elements (None: back to back).  Rows go to d_out + out_offsets[i] floats (None: back to back)."""
+        a, ln = _u32(ids), _u32(lens)
+        frames = np.zeros(a.shape[0], np.uint32)
+        u64p = C.POINTER(C.c_uint64)
+        so = None if src_offsets is None else np.ascontiguousarray(src_offsets, np.uint64)
+        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
+        _check(lib().melspec_fbank_stream_push_device(self._h, a.ctypes.data_as(_u32p), C.c_void_p(d_chunks or None), int(pcm_dtype),
+                                                      None if so is None else so.ctypes.data_as(u64p), ln.ctypes.data_as(_u32p), a.shape[0],
+                                                      C.c_void_p(d_out or None), None if oo is None else oo.ctypes.data_as(u64p),
+                                                      frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
+    def stats(self, ids: Sequence[int]):
+        """(means [n, num_mel_bins] f32, counts [n] u64): mean[bin] = f32(f64 sum of the stream's emitted rows / their count), zeros for
+        a stream without a row"""
+        a = _u32(ids)
+        means = np.zeros((a.shape[0], self.n_mels), np.float32)
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(lib().melspec_fbank_stream_stats_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(means), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return means, counts
+
+    def stats_device(self, ids: Sequence[int], d_means: int, stream: int = 0) -> np.ndarray:
+        """the means to device memory at d_means ([n, num_mel_bins] f32); returns the counts"""
+        a = _u32(ids)
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(lib().melspec_fbank_stream_stats_device(self._h, a.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_means or None),
+                                                       counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream or None)))
+        return counts
+
+
 class RingBuffer:
     """One stream with the reference's interface (src/rb.rs:18-121): add_frame / add feed samples, maybe_mel
     returns one (n_mels, 1) column per completed hop or None.  Frames are computed on the device in batches
