@@ -2,6 +2,7 @@
 // (src/stft.rs:48-86, src/rb.rs:86-121), the TGA quantiser (src/quant.rs), the VAD column stencil (src/vad.rs:373-415), synthetic PCM.
 #include "host_common.hpp"
 #include "aux_kernels.hpp"
+#include "stream_bank.hpp"
 #include "mel_bank.hpp"
 #include "tga_quant.hpp"
 #include "vad_columns.hpp"
@@ -110,19 +111,14 @@ __global__ void plan_upload_kernel(const uint4 *src, uint4 *dst, size_t n16) {
 int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *h_off,
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
                 int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order) {
-    RaggedSlot &sl = rs.slot[rs.next++ % RaggedScratch::kSlots];
-    used = &sl;
-    if (!sl.ev) HIP_TRY(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-    if (sl.pending) { HIP_TRY(hipEventSynchronize(sl.ev)); sl.pending = false; }
     uint64_t units = 0;
     for (uint32_t c = 0; c < n_clips; ++c) units += (frames[c] + frames_per_unit - 1) / frames_per_unit;
     const uint64_t n_blocks = (units + kUnitBlock - 1) / kUnitBlock;
     const size_t words64 = static_cast<size_t>(n_clips) * 4 + 1;
     const size_t blk_words = static_cast<size_t>(n_blocks ? n_blocks : 1);
-    const size_t bytes = words64 * sizeof(uint64_t) + (blk_words + (want_order ? static_cast<size_t>(n_clips) + 1 : 0)) * sizeof(uint32_t);
-    int rc = sl.ensure_host((bytes + 15) & ~static_cast<size_t>(15));
-    if (rc) return rc;
-    if ((rc = sl.dev.ensure((bytes + 15) & ~static_cast<size_t>(15)))) return rc;
+    const size_t bytes = round16(words64 * sizeof(uint64_t) + (blk_words + (want_order ? static_cast<size_t>(n_clips) + 1 : 0)) * sizeof(uint32_t));
+    if (int rc = table_slot_take(rs, bytes, used)) return rc;
+    RaggedSlot &sl = *used;
     uint64_t *off = static_cast<uint64_t *>(sl.host), *fr = off + n_clips, *oo = fr + n_clips, *pre = oo + n_clips;
     uint32_t *blk = reinterpret_cast<uint32_t *>(off + words64);
     uint64_t cursor = 0, out_cursor = 0, total = 0;
@@ -154,15 +150,7 @@ int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float
         for (uint32_t i = n_clips; i > 0 && frames[ord[i - 1]] == 0; --i) ord[i - 1] = 0xffffffffu;
         ord[n_clips] = 0;       // the ticket counter
     }
-    // the upload is a kernel on the launch stream that reads the pinned slot over the bus: an SDMA copy sits in another
-    // hardware queue and the hand-over between the queues costs more than the copy
-    {
-        const size_t n16 = (bytes + 15) / 16;
-        const unsigned blocks = static_cast<unsigned>((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
-        hipLaunchKernelGGL(plan_upload_kernel, dim3(blocks), dim3(256), 0, stream, static_cast<const uint4 *>(sl.host),
-                           static_cast<uint4 *>(sl.dev.p), n16);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = table_slot_upload(sl, bytes, stream)) return rc;
     const uint64_t *d = static_cast<const uint64_t *>(sl.dev.p);
     BatchDesc &b = pl.desc;
     b = BatchDesc{};
@@ -182,8 +170,8 @@ void plan_ragged_done(RaggedSlot *sl, hipStream_t stream) {
     if (sl && sl->ev && hipEventRecord(sl->ev, stream) == hipSuccess) sl->pending = true;
 }
 
-// ---- what the Kaldi fbank's stream bank (fbank512.hip) shares with the bank below: a table's trip to the device through a ring slot, and
-// the scatter / carry kernels (geometry-agnostic: they read the slot stride, in_off and the entries) ----
+// ---- a table's trip to the device through a ring slot (the ragged plans above, the stream banks' entries: stream_bank.hpp), and the banks'
+// scatter / carry kernels (geometry-agnostic: they read the slot stride, in_off and the entries) ----
 // the next slot of the ring with room for `bytes` (a multiple of 16) on both sides; the caller fills sl->host, then table_slot_upload
 int table_slot_take(RaggedScratch &ring, size_t bytes, RaggedSlot *&sl) {
     sl = &ring.slot[ring.next++ % RaggedScratch::kSlots];
@@ -192,7 +180,8 @@ int table_slot_take(RaggedScratch &ring, size_t bytes, RaggedSlot *&sl) {
     if (int rc = sl->ensure_host(bytes)) return rc;
     return sl->dev.ensure(bytes);
 }
-// the copy kernel on the launch stream (no SDMA queue hand-over); afterwards the slot is in use until plan_ragged_done's event
+// the upload is a kernel on the launch stream that reads the pinned slot over the bus: an SDMA copy sits in another hardware queue and the
+// hand-over between the queues costs more than the copy.  Afterwards the slot is in use until plan_ragged_done's event
 int table_slot_upload(RaggedSlot &sl, size_t bytes, hipStream_t s) {
     const size_t n16 = bytes / 16;
     const unsigned blocks = static_cast<unsigned>((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
@@ -540,178 +529,119 @@ struct melspec_stream {
     melspec_ctx *ctx = nullptr;          // geometry, tables, kernels; not owned
     StreamGeom geom{};
     StreamBook book;                     // pending / idx per stream (host side of the state)
-    DevBuf state, staging, out;
-    RaggedScratch ring;                  // per-push entry tables
+    BankCore core;
     // the detector stage (melspec_stream_enable_vad): VoiceActivityDetector state per stream, in HBM
     bool vad_on = false;
     melspec_vad_settings vad{};
     DevBuf vad_state, vad_prev, vad_acts;
     std::vector<uint64_t> vad_count;     // host copy of StreamVadState::count (VoiceActivityDetector::frame_index)
-    // Steady state of a live bank: the same streams pushing the same number of samples from the same pending count, every stream past
-    // its first window.  Such a push has the entry table and the ragged plan of the previous one -- both are still on the device --
-    // so neither is built or uploaded again (4096 streams x 1 hop: 0.089 -> 0.05 ms per push).
-    struct PushCache {
-        bool valid = false;
-        uint32_t n = 0;
-        int fpu = 0;
-        int io = 0;                          // pcm | out << 4 of the push (the frame launch is the one of its row type)
-        const void *d_out = nullptr;
-        std::vector<uint32_t> ids, lens, pend;
-        std::vector<uint64_t> out_off;       // the caller's row offsets (empty: packed)
-        std::vector<uint64_t> src_off;       // a device producer's chunk offsets (empty: back to back -- they follow from lens)
+    // The plan of the last push, and -- while `key` is valid -- its entry table and ragged plan on the device: a push that repeats it
+    // (PushKey, stream_plan.hpp) builds and uploads neither again (4096 streams x 1 hop: 0.089 -> 0.05 ms per push).
+    struct {
+        PushKey key;
         StreamPlan pl;
-        const StreamEntry *d_e = nullptr;    // the entries in the ring slot of the push that filled the cache
+        const StreamEntry *d_e = nullptr;    // the entries in the ring slot of the push that filled the key
         BatchPlan plan;
     } cache;
-    RaggedScratch plan_ring;             // the ragged plans of the pushes (the context's own ring serves its other callers)
 };
 
 namespace {
-int stream_plan(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool flush, StreamPlan &pl) {
-    const char *err = nullptr;
-    const int rc = stream_plan_push(st->geom, st->book, ids, lens, n, flush, pl, &err);
-    if (rc == 1) return fail(MELSPEC_ERR_INVALID_ARG, err);
-    if (rc == 2) return fail(MELSPEC_ERR_CAPACITY, err);
-    return MELSPEC_OK;
-}
-void stream_commit(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool flush) {
-    stream_commit_push(st->geom, st->book, ids, lens, n, flush);
-}
-
 // what a push emits per frame: the mel row (Spectrogram::add + MelSpectrogram::add) or the spectrum (Spectrogram::add alone)
 struct StreamEmit {
     bool stft = false;
     int dtype = MELSPEC_STFT_F32, full = 0;
 };
 
-// scatter (optional) -> frames -> carry update, all on one stream
-// does this push repeat the cached one?  (ids / lens / pending before the push; every stream was past its first window when the cache
-// was filled and idx only grows, resets invalidate)
-// io / h_src_off: the element types of the push and a device producer's chunk offsets (the _io pushes) -- the cached entries hold the
-// chunk offsets, the cached plan the row offsets in elements of its row type
-bool stream_cache_hit(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, const void *d_out, const uint64_t *h_out_off,
-                      int io = 0, const uint64_t *h_src_off = nullptr) {
-    const melspec_stream::PushCache &k = st->cache;
-    if (!k.valid || k.n != n || k.d_out != d_out || k.out_off.empty() != (h_out_off == nullptr)) return false;
-    if (k.io != io || k.src_off.empty() != (h_src_off == nullptr)) return false;
-    if (k.fpu != ctx_frames_per_unit(st->ctx)) return false;            // AUTO changed its regime: another unit size
-    for (uint32_t i = 0; i < n; ++i)
-        if (ids[i] != k.ids[i] || lens[i] != k.lens[i] || st->book.pending[ids[i]] != k.pend[i]) return false;
-    if (h_src_off && std::memcmp(h_src_off, k.src_off.data(), static_cast<size_t>(n) * sizeof(uint64_t)) != 0) return false;
-    return h_out_off == nullptr || std::memcmp(h_out_off, k.out_off.data(), static_cast<size_t>(n) * sizeof(uint64_t)) == 0;
+// one push of the bank: q.io = pcm_dtype | out_dtype << 4 (stream_io_args) -- the scatter converts the chunks into the f32 state, which
+// is what the frame kernels read, so only the out half of the code reaches launch_ctx
+struct StreamPush {
+    PushQuery q;
+    bool flush = false;
+    StreamEmit emit;
+    bool want_acts = false;                      // the caller takes the detector's records: the host forms', in `acts`
+    melspec_vad_activity *acts = nullptr;
+    size_t acts_capacity = 0;
+    melspec_vad_activity *d_acts = nullptr;      // the detector's records on the device (NULL: the bank's own buffer)
+    bool hit = false;                            // the push repeats the cached one: decided by stream_prepare, nowhere else
+};
+
+// The plan of the push in st->cache.pl: the one that is there if the push repeats it, else a fresh one (the key goes first: the plan it
+// stood for is overwritten, and the ring slot its entries are in may be the next one taken).  A host push's q.d_out is the bank's out
+// buffer: a hit ran from that buffer with as many rows, so the push finds room in it and the pointer stays.
+int stream_prepare(melspec_stream *st, StreamPush &p, const uint32_t *ids, const uint32_t *lens, uint32_t n) {
+    p.q.ids = ids; p.q.lens = lens; p.q.n = n; p.q.fpu = ctx_frames_per_unit(st->ctx);
+    p.q.repeatable = !p.flush && !p.emit.stft;
+    if ((p.hit = st->cache.key.matches(st->book, p.q))) return MELSPEC_OK;
+    st->cache.key.invalidate();
+    const char *err = nullptr;
+    return plan_status(stream_plan_push(st->geom, st->book, p.q.ids, p.q.lens, p.q.n, p.flush, st->cache.pl, &err), err);
 }
 
-// reuse: `pl` is st->cache.pl and the device still holds its entries and plan (stream_cache_hit); ids / lens: the push's arguments,
-// for filling the cache (NULL: do not, e.g. a flush)
-// io = pcm_dtype | out_dtype << 4 (stream_io_args): d_src holds elements of the sample type, the scatter converts them into the f32 state;
-// the frame kernels read that state, so only the out half of the code reaches launch_ctx.  h_src_off: where a device producer's chunks
-// start in d_src, in elements (NULL: back to back, the plan's own offsets)
-int stream_run(melspec_stream *st, const StreamPlan &pl, uint32_t n, const void *d_src, void *d_out, const uint64_t *h_out_off,
-               hipStream_t s, const StreamEmit &emit = StreamEmit(), melspec_vad_activity *d_acts = nullptr, bool reuse = false,
-               const uint32_t *ids = nullptr, const uint32_t *lens = nullptr, int io = 0, const uint64_t *h_src_off = nullptr) {
+// the push is through: the book moves on
+void stream_commit(melspec_stream *st, const StreamPush &p, uint32_t *h_frames) {
+    const uint32_t *frames = st->cache.pl.frames.data();
+    stream_commit_push(st->geom, st->book, p.q.ids, p.q.lens, p.q.n, p.flush);
+    for (uint32_t i = 0; st->vad_on && i < p.q.n; ++i) st->vad_count[p.q.ids[i]] += frames[i];
+    if (h_frames) std::memcpy(h_frames, frames, static_cast<size_t>(p.q.n) * sizeof(uint32_t));
+}
+
+// the bank's frame stage behind core_run's scatter: spectra, or mel rows (planned, or the cached plan again) and the detector
+int stream_frames(melspec_stream *st, const StreamPush &p, const StreamEntry *d_e, hipStream_t s) {
     melspec_ctx *c = st->ctx;
-    HIP_TRY(hipSetDevice(c->dev.device));
-    if (pl.total_frames && !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");      // before anything is queued
-    if (st->vad_on && emit.stft) return fail(MELSPEC_ERR_UNSUPPORTED, "the detector stage is on: it needs the mel rows of every push");
-    if (st->vad_on && pl.total_frames && !d_acts) {                                             // records nobody asked for: internal buffer
-        const int rc0 = st->vad_acts.ensure(pl.total_frames * sizeof(melspec_vad_activity));
-        if (rc0) return rc0;
-        d_acts = static_cast<melspec_vad_activity *>(st->vad_acts.p);
-    }
-    int rc = MELSPEC_OK;
-    // the entries travel like a ragged plan: pinned slot, copy kernel on the launch stream (no SDMA queue hand-over)
-    struct SlotGuard { RaggedSlot *sl; hipStream_t s; ~SlotGuard() { plan_ragged_done(sl, s); } } slot_guard{nullptr, s};
-    const StreamEntry *d_e = st->cache.d_e;
-    if (!reuse) {
-        st->cache.valid = false;                     // whatever happens below, the slot the cache points into may be the next one taken
-        RaggedSlot &sl = st->ring.slot[st->ring.next++ % RaggedScratch::kSlots];
-        if (!sl.ev) HIP_TRY(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
-        if (sl.pending) { HIP_TRY(hipEventSynchronize(sl.ev)); sl.pending = false; }
-        const size_t ebytes = (static_cast<size_t>(n) * sizeof(StreamEntry) + 15) & ~static_cast<size_t>(15);
-        rc = sl.ensure_host(ebytes);
-        if (rc) return rc;
-        if ((rc = sl.dev.ensure(ebytes))) return rc;
-        std::memcpy(sl.host, pl.entries.data(), static_cast<size_t>(n) * sizeof(StreamEntry));
-        if (h_out_off)                                   // caller-placed rows: the detector stage reads them where they are
-            for (uint32_t i = 0; i < n; ++i) static_cast<StreamEntry *>(sl.host)[i].out_off = h_out_off[i];
-        if (h_src_off)
-            for (uint32_t i = 0; i < n; ++i) static_cast<StreamEntry *>(sl.host)[i].src_off = h_src_off[i];
-        // from here on the slot is in use by queued work: every exit records its event (the next user of the slot waits for it)
-        slot_guard.sl = &sl;
-        const size_t n16 = ebytes / 16;
-        const unsigned blocks = static_cast<unsigned>((n16 + 255) / 256 < 1024 ? (n16 + 255) / 256 : 1024);
-        hipLaunchKernelGGL(plan_upload_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, static_cast<const uint4 *>(sl.host),
-                           static_cast<uint4 *>(sl.dev.p), n16);
-        HIP_TRY(hipGetLastError());
-        d_e = static_cast<const StreamEntry *>(sl.dev.p);
-    }
-    float *state = static_cast<float *>(st->state.p);
-    bool any_fill = d_src != nullptr;
-    for (uint32_t i = 0; i < n && !any_fill; ++i) any_fill = pl.entries[i].zero_fill != 0;
-    if (any_fill) {
-        if ((io & 15) == MELSPEC_PCM_S16)
-            hipLaunchKernelGGL(stream_scatter_kernel<io_s16>, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e,
-                               static_cast<const io_s16 *>(d_src));
-        else
-            hipLaunchKernelGGL(stream_scatter_kernel<float>, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e,
-                               static_cast<const float *>(d_src));
-        HIP_TRY(hipGetLastError());
-    }
-    if (pl.total_frames && emit.stft) {
+    const StreamPlan &pl = st->cache.pl;
+    const PushQuery &q = p.q;
+    const uint32_t n = q.n;
+    float *state = static_cast<float *>(st->core.state.p);
+    if (p.emit.stft) {
         std::vector<uint64_t> oo(n);            // complex elements, entries back to back
         uint64_t cur = 0;
-        const uint64_t bins = melspec_stft_bins(c, emit.full);
+        const uint64_t bins = melspec_stft_bins(c, p.emit.full);
         for (uint32_t i = 0; i < n; ++i) { oo[i] = cur; cur += pl.frames[i] * bins; }
-        rc = melspec_stft_ragged_device(c, state, pl.off.data(), pl.len.data(), n, d_out, h_out_off ? h_out_off : oo.data(), emit.dtype, emit.full, s);
-        if (rc) return rc;
-    } else if (pl.total_frames) {
-        const int out_only_io = io & ~15;       // the frame kernel's PCM is the f32 state whatever the chunks were
-        if (reuse) {
-            rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
-        } else {
-            // melspec_compute_ragged_device with the plan kept: frames per entry are the plan's, the ring is the bank's own
-            std::vector<uint64_t> fr(n);
-            for (uint32_t i = 0; i < n; ++i) fr[i] = pl.frames[i];
-            RaggedSlot *pslot = nullptr;
-            const int fpu = ctx_frames_per_unit(c);
-            rc = plan_ragged(st->plan_ring, s, state, static_cast<float *>(d_out), pl.off.data(), fr, h_out_off ? h_out_off : pl.out_off.data(), n,
-                             c->n_mels, fpu, st->cache.plan, pslot);
-            if (!rc) rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
-            plan_ragged_done(pslot, s);
-            // a push that can come again: every stream past its first window (no skipped hops), not a flush
-            bool steady = !rc && ids != nullptr && lens != nullptr;
-            for (uint32_t i = 0; i < n && steady; ++i) steady = st->book.idx[ids[i]] >= st->geom.n_fft;
-            if (steady) {
-                melspec_stream::PushCache &k = st->cache;
-                k.n = n; k.fpu = fpu; k.io = io; k.d_out = d_out; k.d_e = d_e;
-                k.ids.assign(ids, ids + n); k.lens.assign(lens, lens + n);
-                k.pend.resize(n);
-                for (uint32_t i = 0; i < n; ++i) k.pend[i] = st->book.pending[ids[i]];
-                if (h_out_off) k.out_off.assign(h_out_off, h_out_off + n); else k.out_off.clear();
-                if (h_src_off) k.src_off.assign(h_src_off, h_src_off + n); else k.src_off.clear();
-                k.pl = pl;
-                k.valid = true;
-            }
-        }
-        if (rc) return rc;
-        if (st->vad_on) {
-            StreamVadParams vp{};
-            vp.entries = d_e; vp.rows = static_cast<const float *>(d_out);
-            vp.state = static_cast<StreamVadState *>(st->vad_state.p); vp.prev = static_cast<float *>(st->vad_prev.p);
-            vp.acts = reinterpret_cast<VadActivity *>(d_acts);
-            vp.n_mels = st->geom.n_mels; vp.min_mel = st->vad.min_mel; vp.min_y = st->vad.min_y; vp.min_x = st->vad.min_x;
-            vp.thr = st->vad.min_energy * st->vad.min_energy;
-            uint32_t most = 0;
-            for (uint32_t i = 0; i < n; ++i) most = std::max(most, pl.frames[i]);
-            hipLaunchKernelGGL(stream_vad_kernel, dim3(n), dim3(most <= 1 ? 64 : most <= 2 ? 128 : 256), 0, s, vp);
-            HIP_TRY(hipGetLastError());
-        }
+        return melspec_stft_ragged_device(c, state, pl.off.data(), pl.len.data(), n, const_cast<void *>(q.d_out), q.h_out_off ? q.h_out_off : oo.data(),
+                                          p.emit.dtype, p.emit.full, s);
     }
-    hipLaunchKernelGGL(stream_carry_kernel, dim3(n), dim3(256), 0, s, state, st->geom.stride, st->geom.in_off, d_e);
+    const int out_only_io = q.io & ~15;       // the frame kernel's PCM is the f32 state whatever the chunks were
+    int rc;
+    if (p.hit) {
+        rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
+    } else {
+        // melspec_compute_ragged_device with the plan kept: frames per entry are the plan's, the ring is the bank's own
+        std::vector<uint64_t> fr(pl.frames.begin(), pl.frames.end());
+        RaggedSlot *pslot = nullptr;
+        rc = plan_ragged(st->core.plan_ring, s, state, static_cast<float *>(const_cast<void *>(q.d_out)), pl.off.data(), fr,
+                         q.h_out_off ? q.h_out_off : pl.out_off.data(), n, c->n_mels, q.fpu, st->cache.plan, pslot);
+        if (!rc) rc = launch_ctx(c, st->cache.plan.desc, s, out_only_io);
+        plan_ragged_done(pslot, s);
+        if (!rc && st->cache.key.fill(st->geom, st->book, q)) st->cache.d_e = d_e;
+    }
+    if (rc || !st->vad_on) return rc;
+    StreamVadParams vp{};
+    vp.entries = d_e; vp.rows = static_cast<const float *>(q.d_out);
+    vp.state = static_cast<StreamVadState *>(st->vad_state.p); vp.prev = static_cast<float *>(st->vad_prev.p);
+    vp.acts = reinterpret_cast<VadActivity *>(p.d_acts);
+    vp.n_mels = st->geom.n_mels; vp.min_mel = st->vad.min_mel; vp.min_y = st->vad.min_y; vp.min_x = st->vad.min_x;
+    vp.thr = st->vad.min_energy * st->vad.min_energy;
+    uint32_t most = 0;
+    for (uint32_t i = 0; i < n; ++i) most = std::max(most, pl.frames[i]);
+    hipLaunchKernelGGL(stream_vad_kernel, dim3(n), dim3(most <= 1 ? 64 : most <= 2 ? 128 : 256), 0, s, vp);
     HIP_TRY(hipGetLastError());
-    // the contract of the push calls: the launches have completed on return (a device producer may refill its slot at once)
-    HIP_TRY(hipStreamSynchronize(s));
     return MELSPEC_OK;
+}
+
+// scatter (optional) -> frames -> carry update, all on one stream.  d_src: the chunks (NULL: in the slots already)
+int stream_run(melspec_stream *st, StreamPush &p, const void *d_src, hipStream_t s) {
+    const StreamPlan &pl = st->cache.pl;
+    if (st->vad_on && p.emit.stft) return fail(MELSPEC_ERR_UNSUPPORTED, "the detector stage is on: it needs the mel rows of every push");
+    if (st->vad_on && pl.total_frames && !p.d_acts) {                                           // records nobody asked for: internal buffer
+        HIP_TRY(hipSetDevice(st->core.device));
+        if (int rc = st->vad_acts.ensure(pl.total_frames * sizeof(melspec_vad_activity))) return rc;
+        p.d_acts = static_cast<melspec_vad_activity *>(st->vad_acts.p);
+    }
+    bool zero_fill = false;
+    for (uint32_t i = 0; p.flush && i < p.q.n && !zero_fill; ++i) zero_fill = pl.entries[i].zero_fill != 0;
+    const PushArgs a{d_src, p.q.io & 15, p.q.h_src_off, const_cast<void *>(p.q.d_out), p.q.h_out_off, s, zero_fill};
+    return core_run(st->core, pl.entries.data(), p.q.n, pl.total_frames, a, p.hit ? st->cache.d_e : nullptr, nullptr, 0,
+                    [&](const StreamEntry *d_e, const void *) { return stream_frames(st, p, d_e, s); });
 }
 }  // namespace
 
@@ -729,46 +659,38 @@ int melspec_stream_create(melspec_stream **out, melspec_ctx *ctx, uint32_t n_str
     st->geom = stream_geometry(static_cast<uint32_t>(ctx->fft_size), static_cast<uint32_t>(ctx->hop_size), static_cast<uint32_t>(ctx->n_mels),
                                n_streams, max_chunk);
     st->book.reset(n_streams);
-    if (hipSetDevice(ctx->dev.device) != hipSuccess) { delete st; return fail(MELSPEC_ERR_UNAVAILABLE, "hipSetDevice failed"); }
-    const size_t bytes = static_cast<size_t>(n_streams) * st->geom.stride * sizeof(float) + 64;
-    int rc = st->state.ensure(bytes);
-    if (rc) { delete st; return rc; }
-    if (hipMemset(st->state.p, 0, bytes) != hipSuccess) { st->state.release(); delete st; return fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"); }
+    if (int rc = core_create(st->core, ctx->dev.device, ctx->stream, n_streams, st->geom.stride, st->geom.in_off)) { melspec_stream_destroy(st); return rc; }
     *out = st;
     return MELSPEC_OK;
 }
 
 void melspec_stream_destroy(melspec_stream *st) {
     if (!st) return;
-    if (st->ctx) { (void)hipSetDevice(st->ctx->dev.device); (void)hipStreamSynchronize(st->ctx->stream); }
-    st->state.release(); st->ring.release(); st->staging.release(); st->out.release();
-    st->vad_state.release(); st->vad_prev.release(); st->vad_acts.release(); st->plan_ring.release();
+    core_destroy(st->core);
+    st->vad_state.release(); st->vad_prev.release(); st->vad_acts.release();
     delete st;
 }
 
 int melspec_stream_reset(melspec_stream *st, const uint32_t *ids, uint32_t n) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
-    st->cache.valid = false;
-    HIP_TRY(hipSetDevice(st->ctx->dev.device));
+    if (int rc = core_reset_slots(st->core, ids, n)) return rc;      // a bad id: nothing has been touched
+    st->cache.key.invalidate();
+    hipStream_t s = st->core.stream;
     if (!ids) {
-        HIP_TRY(hipMemsetAsync(st->state.p, 0, static_cast<size_t>(st->geom.n_streams) * st->geom.stride * sizeof(float), st->ctx->stream));
         st->book.reset(st->geom.n_streams);
         if (st->vad_on) {
-            HIP_TRY(hipMemsetAsync(st->vad_state.p, 0, static_cast<size_t>(st->geom.n_streams) * sizeof(StreamVadState), st->ctx->stream));
+            HIP_TRY(hipMemsetAsync(st->vad_state.p, 0, static_cast<size_t>(st->geom.n_streams) * sizeof(StreamVadState), s));
             std::fill(st->vad_count.begin(), st->vad_count.end(), 0ull);
         }
-    } else {
-        for (uint32_t i = 0; i < n; ++i) {
-            if (ids[i] >= st->geom.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
-            HIP_TRY(hipMemsetAsync(static_cast<float *>(st->state.p) + ids[i] * st->geom.stride, 0, st->geom.in_off * sizeof(float), st->ctx->stream));
-            st->book.pending[ids[i]] = 0; st->book.idx[ids[i]] = 0;
-            if (st->vad_on) {
-                HIP_TRY(hipMemsetAsync(static_cast<StreamVadState *>(st->vad_state.p) + ids[i], 0, sizeof(StreamVadState), st->ctx->stream));
-                st->vad_count[ids[i]] = 0;
-            }
+    }
+    for (uint32_t i = 0; ids && i < n; ++i) {
+        st->book.pending[ids[i]] = 0; st->book.idx[ids[i]] = 0;
+        if (st->vad_on) {
+            HIP_TRY(hipMemsetAsync(static_cast<StreamVadState *>(st->vad_state.p) + ids[i], 0, sizeof(StreamVadState), s));
+            st->vad_count[ids[i]] = 0;
         }
     }
-    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(s));
     return MELSPEC_OK;
 }
 
@@ -777,17 +699,9 @@ size_t melspec_stream_frames_after(const melspec_stream *st, uint32_t id, uint32
     return stream_frames_after(st->geom, st->book, id, n_new);
 }
 
-float *melspec_stream_input_ptr(melspec_stream *st, uint32_t id) {
-    if (!st || id >= st->geom.n_streams) return nullptr;
-    return static_cast<float *>(st->state.p) + id * st->geom.stride + st->geom.in_off;
-}
+float *melspec_stream_input_ptr(melspec_stream *st, uint32_t id) { return st ? core_input_ptr(st->core, id) : nullptr; }
 
 static_assert(sizeof(melspec_vad_activity) == 8 && sizeof(VadActivity) == 8, "the activity record is 8 bytes on both sides of the ABI");
-static void stream_vad_commit(melspec_stream *st, const uint32_t *ids, const StreamPlan &pl, uint32_t n) {
-    if (!st->vad_on) return;
-    for (uint32_t i = 0; i < n; ++i) st->vad_count[ids[i]] += pl.frames[i];
-}
-
 // io / d_chunks / h_src_offsets: melspec_stream_push_device_io -- the element types, and chunks that lie in the caller's own device
 // buffer (NULL: already in the slots, at melspec_stream_input_ptr)
 static int stream_push_device_impl(melspec_stream *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, void *d_out,
@@ -797,19 +711,14 @@ static int stream_push_device_impl(melspec_stream *st, const uint32_t *ids, cons
     if (want_acts && !st->vad_on) return fail(MELSPEC_ERR_INVALID_ARG, "the detector stage is off (melspec_stream_enable_vad)");
     if (n == 0) return MELSPEC_OK;
     if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    StreamPlan fresh;
-    if (!d_chunks) h_src_offsets = nullptr;
-    const bool reuse = stream_cache_hit(st, ids, lens, n, d_out, h_out_offsets, io, h_src_offsets);
-    int rc = reuse ? MELSPEC_OK : stream_plan(st, ids, lens, n, false, fresh);
+    StreamPush p;
+    p.q.io = io; p.q.d_out = d_out; p.q.h_out_off = h_out_offsets; p.q.h_src_off = d_chunks ? h_src_offsets : nullptr;
+    p.d_acts = d_acts;
+    int rc = stream_prepare(st, p, ids, lens, n);
     if (rc) return rc;
-    const StreamPlan &pl = reuse ? st->cache.pl : fresh;
-    if (want_acts && pl.total_frames && !d_acts) return fail(MELSPEC_ERR_INVALID_ARG, "d_acts is NULL");
-    rc = stream_run(st, pl, n, d_chunks, d_out, h_out_offsets, stream ? static_cast<hipStream_t>(stream) : st->ctx->stream, StreamEmit(), d_acts,
-                    reuse, ids, lens, io, h_src_offsets);
-    if (rc) return rc;
-    stream_commit(st, ids, lens, n, false);
-    stream_vad_commit(st, ids, pl, n);
-    if (h_frames) std::memcpy(h_frames, pl.frames.data(), static_cast<size_t>(n) * sizeof(uint32_t));
+    if (want_acts && st->cache.pl.total_frames && !d_acts) return fail(MELSPEC_ERR_INVALID_ARG, "d_acts is NULL");
+    if ((rc = stream_run(st, p, d_chunks, stream ? static_cast<hipStream_t>(stream) : st->core.stream))) return rc;
+    stream_commit(st, p, h_frames);
     return MELSPEC_OK;
 }
 
@@ -825,8 +734,8 @@ int melspec_stream_push_device_vad(melspec_stream *st, const uint32_t *ids, cons
 
 int melspec_stream_enable_vad(melspec_stream *st, const melspec_vad_settings *settings) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
-    HIP_TRY(hipSetDevice(st->ctx->dev.device));
-    HIP_TRY(hipStreamSynchronize(st->ctx->stream));
+    HIP_TRY(hipSetDevice(st->core.device));
+    HIP_TRY(hipStreamSynchronize(st->core.stream));
     if (!settings) { st->vad_on = false; return MELSPEC_OK; }
     if (settings->min_x > kStreamVadMaxX) return fail(MELSPEC_ERR_UNSUPPORTED, "min_x above 66: the column history of a stream is 64 bits");
     if (settings->min_x < 0 || settings->min_y < 0 || settings->min_mel < 0) return fail(MELSPEC_ERR_INVALID_ARG, "negative detection setting");
@@ -847,77 +756,68 @@ uint64_t melspec_stream_vad_frames(const melspec_stream *st, uint32_t id) {
     return st->vad_count[id];
 }
 
-// io (melspec_stream_push_host_io / _flush_host_io): samples holds elements of the sample type, out receives elements of the row type
+// p: what the push is besides its chunks -- a flush, spectra, typed ends (p.q.io, melspec_stream_push_host_io / _flush_host_io: samples
+// holds elements of the sample type, out receives elements of the row type), the caller's activity buffer
 static int stream_push_host_impl(melspec_stream *st, const uint32_t *ids, const void *samples, const uint32_t *lens, uint32_t n,
-                                 bool flush, void *out, size_t out_capacity, uint32_t *h_frames, const StreamEmit &emit = StreamEmit(),
-                                 melspec_vad_activity *acts = nullptr, size_t acts_capacity = 0, bool want_acts = false, int io = 0) {
+                                 void *out, size_t out_capacity, uint32_t *h_frames, StreamPush p = StreamPush()) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
-    if (want_acts && !st->vad_on) return fail(MELSPEC_ERR_INVALID_ARG, "the detector stage is off (melspec_stream_enable_vad)");
+    if (p.want_acts && !st->vad_on) return fail(MELSPEC_ERR_INVALID_ARG, "the detector stage is off (melspec_stream_enable_vad)");
     if (n == 0) return MELSPEC_OK;
-    if (!ids || (!flush && !lens)) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    StreamPlan fresh;
-    const bool reuse = !flush && !emit.stft && stream_cache_hit(st, ids, lens, n, st->out.p, nullptr, io);
-    int rc = reuse ? MELSPEC_OK : stream_plan(st, ids, lens, n, flush, fresh);
+    if (!ids || (!p.flush && !lens)) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    p.q.d_out = st->core.out.p;
+    int rc = stream_prepare(st, p, ids, lens, n);
     if (rc) return rc;
-    const StreamPlan &pl = reuse ? st->cache.pl : fresh;
+    const StreamPlan &pl = st->cache.pl;
+    if (p.want_acts && pl.total_frames > p.acts_capacity) return fail(MELSPEC_ERR_CAPACITY, "activity buffer too small");
+    if (p.want_acts && pl.total_frames && !p.acts) return fail(MELSPEC_ERR_INVALID_ARG, "acts is NULL");
+    const StreamEmit &e = p.emit;
     // elements the caller receives: floats (mel rows) or complex values (spectra)
-    const uint64_t need = pl.total_frames * (emit.stft ? melspec_stft_bins(st->ctx, emit.full) : static_cast<uint64_t>(st->ctx->n_mels));
-    const size_t esz = emit.stft ? (emit.dtype == MELSPEC_STFT_F64 ? 16 : 8) : (io >> 4) == MELSPEC_OUT_F32 ? sizeof(float) : 2;
-    const size_t ssz = (io & 15) == MELSPEC_PCM_S16 ? sizeof(io_s16) : sizeof(float);
-    if (need > out_capacity) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    if (need && !out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
-    if (want_acts && pl.total_frames > acts_capacity) return fail(MELSPEC_ERR_CAPACITY, "activity buffer too small");
-    if (want_acts && pl.total_frames && !acts) return fail(MELSPEC_ERR_INVALID_ARG, "acts is NULL");
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) total += pl.entries[i].len;
-    if (total && !samples) return fail(MELSPEC_ERR_INVALID_ARG, "samples is NULL");
-    hipStream_t s = st->ctx->stream;
-    HIP_TRY(hipSetDevice(st->ctx->dev.device));
-    if ((rc = st->staging.ensure(total * ssz + 16))) return rc;
-    if ((rc = st->out.ensure(need * esz + 16))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(st->staging.p, samples, total * ssz, hipMemcpyHostToDevice, s));
-    if (st->vad_on && pl.total_frames && (rc = st->vad_acts.ensure(pl.total_frames * sizeof(melspec_vad_activity)))) return rc;
-    // (st->out may have been re-allocated by the ensure above: the cache is keyed on its address, a stale one simply misses next time)
-    rc = stream_run(st, pl, n, total ? st->staging.p : nullptr, st->out.p, nullptr, s, emit,
-                    static_cast<melspec_vad_activity *>(st->vad_acts.p), reuse && st->cache.d_out == st->out.p, flush || emit.stft ? nullptr : ids,
-                    flush || emit.stft ? nullptr : lens, io);
+    const uint64_t need = pl.total_frames * (e.stft ? melspec_stft_bins(st->ctx, e.full) : static_cast<uint64_t>(st->ctx->n_mels));
+    const size_t esz = e.stft ? (e.dtype == MELSPEC_STFT_F64 ? 16 : 8) : (p.q.io >> 4) == MELSPEC_OUT_F32 ? sizeof(float) : 2;
+    const HostPush h{samples, out, out_capacity, need, (p.q.io & 15) == MELSPEC_PCM_S16 ? sizeof(io_s16) : sizeof(float), esz};
+    rc = core_push_host(st->core, pl.entries.data(), n, h, [&](const void *d_src, void *d_out, hipStream_t s) {
+        p.q.d_out = d_out;
+        if (int rc2 = stream_run(st, p, d_src, s)) return rc2;      // the records go to the bank's own buffer (p.d_acts is NULL)
+        if (p.want_acts && pl.total_frames) HIP_TRY(hipMemcpyAsync(p.acts, p.d_acts, pl.total_frames * sizeof(melspec_vad_activity), hipMemcpyDeviceToHost, s));
+        return static_cast<int>(MELSPEC_OK);
+    });
     if (rc) return rc;
-    if (need) {
-        HIP_TRY(hipMemcpyAsync(out, st->out.p, need * esz, hipMemcpyDeviceToHost, s));
-        if (want_acts) HIP_TRY(hipMemcpyAsync(acts, st->vad_acts.p, pl.total_frames * sizeof(melspec_vad_activity), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    stream_commit(st, ids, lens, n, flush);
-    stream_vad_commit(st, ids, pl, n);
-    if (h_frames) std::memcpy(h_frames, pl.frames.data(), static_cast<size_t>(n) * sizeof(uint32_t));
+    stream_commit(st, p, h_frames);
     return MELSPEC_OK;
 }
 
 int melspec_stream_push_host(melspec_stream *st, const uint32_t *ids, const float *samples, const uint32_t *lens, uint32_t n,
                              float *out, size_t out_capacity_floats, uint32_t *h_frames) {
-    return stream_push_host_impl(st, ids, samples, lens, n, false, out, out_capacity_floats, h_frames);
+    return stream_push_host_impl(st, ids, samples, lens, n, out, out_capacity_floats, h_frames);
 }
 
 int melspec_stream_push_host_stft(melspec_stream *st, const uint32_t *ids, const float *samples, const uint32_t *lens, uint32_t n,
                                   void *out, size_t out_capacity_complex, uint32_t *h_frames, int dtype, int full) {
     if (st) { const int rc = stft_args(st->ctx, dtype); if (rc) return rc; }
-    StreamEmit e; e.stft = true; e.dtype = dtype; e.full = full;
-    return stream_push_host_impl(st, ids, samples, lens, n, false, out, out_capacity_complex, h_frames, e);
+    StreamPush p;
+    p.emit.stft = true; p.emit.dtype = dtype; p.emit.full = full;
+    return stream_push_host_impl(st, ids, samples, lens, n, out, out_capacity_complex, h_frames, p);
 }
 
 int melspec_stream_flush_host(melspec_stream *st, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats,
                               uint32_t *h_frames) {
-    return stream_push_host_impl(st, ids, nullptr, nullptr, n, true, out, out_capacity_floats, h_frames);
+    StreamPush p;
+    p.flush = true;
+    return stream_push_host_impl(st, ids, nullptr, nullptr, n, out, out_capacity_floats, h_frames, p);
 }
 
 int melspec_stream_push_host_vad(melspec_stream *st, const uint32_t *ids, const float *samples, const uint32_t *lens, uint32_t n,
                                  float *out, size_t out_capacity_floats, uint32_t *h_frames, melspec_vad_activity *acts, size_t acts_capacity) {
-    return stream_push_host_impl(st, ids, samples, lens, n, false, out, out_capacity_floats, h_frames, StreamEmit(), acts, acts_capacity, true);
+    StreamPush p;
+    p.want_acts = true; p.acts = acts; p.acts_capacity = acts_capacity;
+    return stream_push_host_impl(st, ids, samples, lens, n, out, out_capacity_floats, h_frames, p);
 }
 
 int melspec_stream_flush_host_vad(melspec_stream *st, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats,
                                   uint32_t *h_frames, melspec_vad_activity *acts, size_t acts_capacity) {
-    return stream_push_host_impl(st, ids, nullptr, nullptr, n, true, out, out_capacity_floats, h_frames, StreamEmit(), acts, acts_capacity, true);
+    StreamPush p;
+    p.flush = p.want_acts = true; p.acts = acts; p.acts_capacity = acts_capacity;
+    return stream_push_host_impl(st, ids, nullptr, nullptr, n, out, out_capacity_floats, h_frames, p);
 }
 
 // ---- int16 PCM chunks in / f16, bf16 rows out -------------------------------------------------------------------------------------
@@ -952,16 +852,18 @@ int melspec_stream_push_host_io(melspec_stream *st, const uint32_t *ids, const v
                                 void *out, int out_dtype, size_t out_capacity_elems, uint32_t *h_frames) {
     int io, rc = stream_io_args(st, pcm_dtype, out_dtype, io);
     if (rc) return rc;
-    if (!io) return melspec_stream_push_host(st, ids, static_cast<const float *>(samples), lens, n, static_cast<float *>(out), out_capacity_elems, h_frames);
-    return stream_push_host_impl(st, ids, samples, lens, n, false, out, out_capacity_elems, h_frames, StreamEmit(), nullptr, 0, false, io);
+    StreamPush p;
+    p.q.io = io;
+    return stream_push_host_impl(st, ids, samples, lens, n, out, out_capacity_elems, h_frames, p);
 }
 
 int melspec_stream_flush_host_io(melspec_stream *st, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems,
                                  uint32_t *h_frames) {
     int io, rc = stream_io_args(st, MELSPEC_PCM_F32, out_dtype, io);
     if (rc) return rc;
-    if (!io) return melspec_stream_flush_host(st, ids, n, static_cast<float *>(out), out_capacity_elems, h_frames);
-    return stream_push_host_impl(st, ids, nullptr, nullptr, n, true, out, out_capacity_elems, h_frames, StreamEmit(), nullptr, 0, false, io);
+    StreamPush p;
+    p.flush = true; p.q.io = io;
+    return stream_push_host_impl(st, ids, nullptr, nullptr, n, out, out_capacity_elems, h_frames, p);
 }
 
 int melspec_stream_push_device_io(melspec_stream *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,

@@ -8,6 +8,7 @@
 #include "fbank512_stream_kernels.hpp"
 #include "blm_stats_plan.hpp"
 #include "fbank_stream_plan.hpp"
+#include "stream_bank.hpp"
 
 namespace melspec {
 // emitted by fbank512_io.hip / fbank512_kaldi_io.hip: the NeMo frontend and the Kaldi fbank with int16 PCM in and / or f16, bf16 rows out
@@ -1278,7 +1279,7 @@ int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pc
 
 // ------------------------------------------------------------------------------------
 // Kaldi fbank: the stream bank (melspec_fbank_stream_*): see include/melspec_hip.h.  Bookkeeping in fbank_stream_plan.hpp, kernels in
-// fbank512_stream_kernels.hpp; scatter, carry and the tables' trip to the device are the Whisper bank's (aux.hip).
+// fbank512_stream_kernels.hpp; everything a bank of live streams is besides its planner and its frame stage in stream_bank.hpp.
 // ------------------------------------------------------------------------------------
 namespace {
 constexpr uint32_t kFbankStreamMagic = 0x4b53424du;      // the handle crosses the ABI as void *: every call checks what it was given
@@ -1288,9 +1289,9 @@ struct FbankStreamBank {
     melspec_fbank *fb = nullptr;         // geometry, tables, kernels; not owned
     FbankStreamGeom geom{};
     FbankStreamBook book;                // total / emitted / pending per stream (host side of the state)
-    DevBuf state, sums, counts;          // [n_streams][stride] f32, [n_streams][bins] f64, [n_streams] u64
-    DevBuf staging, out, means;          // the host calls' buffers
-    RaggedScratch ring, plan_ring;       // per-push entry tables / ragged plans
+    BankCore core;
+    DevBuf sums, counts;                 // [n_streams][bins] f64, [n_streams] u64
+    DevBuf means;                        // the host stats call's buffer
 };
 
 FbankStreamBank *fbs_of(void *h) {
@@ -1310,61 +1311,42 @@ int fbs_supported(const melspec_fbank *fb) {
     return MELSPEC_ERR_UNSUPPORTED;
 }
 
-int fbs_plan(FbankStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, FbankStreamPlan &pl) {
-    const char *err = nullptr;
-    const int rc = fbank_stream_plan_push(st->geom, st->book, ids, lens, n, pl, &err);
-    if (rc == 1) return fail(MELSPEC_ERR_INVALID_ARG, err);
-    if (rc == 2) return fail(MELSPEC_ERR_CAPACITY, err);
-    return MELSPEC_OK;
-}
-
-inline size_t round16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
-
-// scatter (d_src != NULL) -> frames -> column sums -> carry, all on one stream; the launches have completed on return
-int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const void *d_src, int pcm_dtype, const uint64_t *h_src_off, float *d_out,
-            const uint64_t *h_out_off, hipStream_t s) {
+// the frame stage behind the core's scatter: the rows, then their column sums; the entries' tail is the clips' continues flags
+int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const PushArgs &a) {
     melspec_fbank *fb = st->fb;
-    if (pl.total_frames && !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");      // before anything is queued
-    HIP_TRY(hipSetDevice(fb->dev.device));
     const int nm = fb->cfg.num_mel_bins;
-    // the entries and, behind them, the clips' continues flags travel like a ragged plan
-    struct SlotGuard { RaggedSlot *sl; hipStream_t s; ~SlotGuard() { plan_ragged_done(sl, s); } } slot_guard{nullptr, s};
-    const size_t ebytes = round16(static_cast<size_t>(n) * sizeof(StreamEntry)), bytes = ebytes + round16(static_cast<size_t>(n) * sizeof(uint32_t));
-    RaggedSlot *sl = nullptr;
-    int rc = table_slot_take(st->ring, bytes, sl);
-    if (rc) return rc;
-    StreamEntry *h_e = static_cast<StreamEntry *>(sl->host);
-    std::memcpy(h_e, pl.entries.data(), static_cast<size_t>(n) * sizeof(StreamEntry));
-    for (uint32_t i = 0; i < n; ++i) {
-        if (h_out_off) h_e[i].out_off = h_out_off[i];          // caller-placed rows: the column sums read them where they are
-        if (h_src_off) h_e[i].src_off = h_src_off[i];
-    }
-    std::memcpy(static_cast<char *>(sl->host) + ebytes, pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t));
-    slot_guard.sl = sl;
-    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
-    const StreamEntry *d_e = static_cast<const StreamEntry *>(sl->dev.p);
-    const uint32_t *d_cont = reinterpret_cast<const uint32_t *>(static_cast<const char *>(sl->dev.p) + ebytes);
-    float *state = static_cast<float *>(st->state.p);
-    if (d_src && (rc = stream_scatter_launch(state, st->geom.stride, st->geom.in_off, d_e, n, d_src, pcm_dtype, s))) return rc;
-    if (pl.total_frames) {
+    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t),
+                    [&](const StreamEntry *d_e, const void *d_cont) {
         BatchPlan bp;
         RaggedSlot *pslot = nullptr;
-        rc = plan_ragged(st->plan_ring, s, state, d_out, pl.off.data(), pl.frames, h_out_off ? h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
+        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), static_cast<float *>(a.d_out), pl.off.data(), pl.frames,
+                             a.h_out_off ? a.h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
         if (!rc) {
             FbankStreamParams q{};
             q.f = fbank_fast_params(fb, bp.desc);
-            q.d_cont = d_cont;
-            rc = launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, nm}, fb->dev.cus, s);
+            q.d_cont = static_cast<const uint32_t *>(d_cont);
+            rc = launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, nm}, fb->dev.cus, a.stream);
         }
-        plan_ragged_done(pslot, s);
+        plan_ragged_done(pslot, a.stream);
         if (rc) return rc;
         FbankStreamSumParams sp{};
-        sp.entries = d_e; sp.rows = d_out; sp.sums = static_cast<double *>(st->sums.p); sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
-        hipLaunchKernelGGL(fbank_stream_sum_kernel, dim3(n), dim3(kFbankStreamSumThreads), 0, s, sp);
+        sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.sums = static_cast<double *>(st->sums.p);
+        sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
+        hipLaunchKernelGGL(fbank_stream_sum_kernel, dim3(n), dim3(kFbankStreamSumThreads), 0, a.stream, sp);
         HIP_TRY(hipGetLastError());
-    }
-    if ((rc = stream_carry_launch(state, st->geom.stride, st->geom.in_off, d_e, n, s))) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
+        return static_cast<int>(MELSPEC_OK);
+    });
+}
+
+// a push behind its argument checks: plan, run(plan) -- its launches have completed when it returns --, then the book moves on
+template <class Run>
+int fbs_push(FbankStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, uint32_t *frames_out, Run run) {
+    FbankStreamPlan pl;
+    const char *err = nullptr;
+    int rc = plan_status(fbank_stream_plan_push(st->geom, st->book, ids, lens, n, pl, &err), err);
+    if (rc || (rc = run(pl))) return rc;
+    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
+    for (uint32_t i = 0; frames_out && i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
     return MELSPEC_OK;
 }
 
@@ -1391,13 +1373,12 @@ int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_stream
                                      n_streams, max_chunk);
     st->book.reset(n_streams);
     auto bail = [&](int code) { melspec_fbank_stream_destroy(st); return code; };
-    if (hipSetDevice(fb->dev.device) != hipSuccess) return bail(fail(MELSPEC_ERR_UNAVAILABLE, "hipSetDevice failed"));
-    const size_t state_bytes = static_cast<size_t>(n_streams) * st->geom.stride * sizeof(float) + 64;
     const size_t sum_bytes = static_cast<size_t>(n_streams) * st->geom.n_mels * sizeof(double), count_bytes = static_cast<size_t>(n_streams) * sizeof(unsigned long long);
     int rc;
-    if ((rc = st->state.ensure(state_bytes)) || (rc = st->sums.ensure(sum_bytes)) || (rc = st->counts.ensure(count_bytes))) return bail(rc);
-    if (hipMemset(st->state.p, 0, state_bytes) != hipSuccess || hipMemset(st->sums.p, 0, sum_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess)
-        return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
+    if ((rc = core_create(st->core, fb->dev.device, fb->stream, n_streams, st->geom.stride, st->geom.in_off)) || (rc = st->sums.ensure(sum_bytes)) ||
+        (rc = st->counts.ensure(count_bytes)))
+        return bail(rc);
+    if (hipMemset(st->sums.p, 0, sum_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess) return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
     *out = st;
     return MELSPEC_OK;
 }
@@ -1405,9 +1386,8 @@ int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_stream
 void melspec_fbank_stream_destroy(void *h) {
     FbankStreamBank *st = fbs_of(h);
     if (!st) return;
-    if (st->fb) { (void)hipSetDevice(st->fb->dev.device); (void)hipStreamSynchronize(st->fb->stream); }
-    st->state.release(); st->sums.release(); st->counts.release(); st->staging.release(); st->out.release(); st->means.release();
-    st->ring.release(); st->plan_ring.release();
+    core_destroy(st->core);
+    st->sums.release(); st->counts.release(); st->means.release();
     st->magic = 0;
     delete st;
 }
@@ -1415,25 +1395,19 @@ void melspec_fbank_stream_destroy(void *h) {
 int melspec_fbank_stream_reset(void *h, const uint32_t *ids, uint32_t n) {
     FbankStreamBank *st = fbs_of(h);
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
+    if (int rc = core_reset_slots(st->core, ids, n)) return rc;      // a bad id: nothing has been touched
     const FbankStreamGeom &g = st->geom;
-    if (ids)
-        for (uint32_t i = 0; i < n; ++i)
-            if (ids[i] >= g.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
-    HIP_TRY(hipSetDevice(st->fb->dev.device));
-    hipStream_t s = st->fb->stream;
+    hipStream_t s = st->core.stream;
     const size_t row = static_cast<size_t>(g.n_mels) * sizeof(double);
     if (!ids) {
-        HIP_TRY(hipMemsetAsync(st->state.p, 0, static_cast<size_t>(g.n_streams) * g.stride * sizeof(float), s));
         HIP_TRY(hipMemsetAsync(st->sums.p, 0, g.n_streams * row, s));
         HIP_TRY(hipMemsetAsync(st->counts.p, 0, static_cast<size_t>(g.n_streams) * sizeof(unsigned long long), s));
         st->book.reset(g.n_streams);
-    } else {
-        for (uint32_t i = 0; i < n; ++i) {
-            HIP_TRY(hipMemsetAsync(static_cast<float *>(st->state.p) + ids[i] * g.stride, 0, g.in_off * sizeof(float), s));
-            HIP_TRY(hipMemsetAsync(static_cast<char *>(st->sums.p) + ids[i] * row, 0, row, s));
-            HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
-            st->book.reset_one(ids[i]);
-        }
+    }
+    for (uint32_t i = 0; ids && i < n; ++i) {
+        HIP_TRY(hipMemsetAsync(static_cast<char *>(st->sums.p) + ids[i] * row, 0, row, s));
+        HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
+        st->book.reset_one(ids[i]);
     }
     HIP_TRY(hipStreamSynchronize(s));
     return MELSPEC_OK;
@@ -1447,8 +1421,7 @@ size_t melspec_fbank_stream_frames_after(const void *h, uint32_t id, uint32_t n_
 
 float *melspec_fbank_stream_input_ptr(void *h, uint32_t id) {
     FbankStreamBank *st = fbs_of(h);
-    if (!st || id >= st->geom.n_streams) return nullptr;
-    return static_cast<float *>(st->state.p) + id * st->geom.stride + st->geom.in_off;
+    return st ? core_input_ptr(st->core, id) : nullptr;
 }
 
 int melspec_fbank_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
@@ -1457,31 +1430,12 @@ int melspec_fbank_stream_push_host(void *h, const uint32_t *ids, const void *sam
     if (int rc = fbs_push_args(st, pcm_dtype)) return rc;
     if (n == 0) return MELSPEC_OK;
     if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    FbankStreamPlan pl;
-    int rc = fbs_plan(st, ids, lens, n, pl);
-    if (rc) return rc;
-    const uint64_t need = pl.total_frames * static_cast<uint64_t>(st->geom.n_mels);
-    if (need > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    if (need && !out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n; ++i) total += lens[i];
-    if (total && !samples) return fail(MELSPEC_ERR_INVALID_ARG, "samples is NULL");
-    melspec_fbank *fb = st->fb;
-    hipStream_t s = fb->stream;
-    HIP_TRY(hipSetDevice(fb->dev.device));
-    const size_t ssz = io_pcm_bytes(pcm_dtype);
-    if ((rc = st->staging.ensure(total * ssz + 16))) return rc;
-    if ((rc = st->out.ensure(need * sizeof(float) + 16))) return rc;
-    if (total) HIP_TRY(hipMemcpyAsync(st->staging.p, samples, total * ssz, hipMemcpyHostToDevice, s));
-    if ((rc = fbs_run(st, pl, n, total ? st->staging.p : nullptr, pcm_dtype, nullptr, static_cast<float *>(st->out.p), nullptr, s))) return rc;
-    if (need) {
-        HIP_TRY(hipMemcpyAsync(out, st->out.p, need * sizeof(float), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
-    if (frames_out)
-        for (uint32_t i = 0; i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
-    return MELSPEC_OK;
+    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
+        const HostPush hp{samples, out, out_capacity_floats, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), sizeof(float)};
+        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
+            return fbs_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s});
+        });
+    });
 }
 
 int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
@@ -1494,15 +1448,10 @@ int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d
         return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
     if ((reinterpret_cast<uintptr_t>(d_chunks) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 3))
         return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    FbankStreamPlan pl;
-    int rc = fbs_plan(st, ids, lens, n, pl);
-    if (rc) return rc;
-    if ((rc = fbs_run(st, pl, n, d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
-                      stream ? static_cast<hipStream_t>(stream) : st->fb->stream))) return rc;
-    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
-    if (frames_out)
-        for (uint32_t i = 0; i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
-    return MELSPEC_OK;
+    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
+        return fbs_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
+                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream});
+    });
 }
 
 int melspec_fbank_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream) {
@@ -1517,10 +1466,10 @@ int melspec_fbank_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, 
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st->fb->stream;
     const size_t bytes = round16(static_cast<size_t>(n) * sizeof(uint32_t));
     RaggedSlot *sl = nullptr;
-    int rc = table_slot_take(st->ring, bytes, sl);
+    int rc = table_slot_take(st->core.ring, bytes, sl);
     if (rc) return rc;
     std::memcpy(sl->host, ids, static_cast<size_t>(n) * sizeof(uint32_t));
-    struct SlotGuard { RaggedSlot *sl; hipStream_t s; ~SlotGuard() { plan_ragged_done(sl, s); } } slot_guard{sl, s};
+    SlotGuard slot_guard{sl, s};
     if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
     FbankStreamMeanParams mp{};
     mp.ids = static_cast<const uint32_t *>(sl->dev.p); mp.sums = static_cast<const double *>(st->sums.p);

@@ -33,13 +33,11 @@ inline FbankStreamGeom fbank_stream_geometry(uint32_t frame_len, uint32_t shift,
     return g;
 }
 
-struct FbankStreamBook {
+struct FbankStreamBook : PushMarks {
     std::vector<uint64_t> total;         // samples received
     std::vector<uint64_t> emitted;       // rows emitted: frames(total)
     std::vector<uint32_t> pending;       // total - emitted * shift: the samples in the carry behind the predecessor (< frame_len)
-    std::vector<uint32_t> mark;          // duplicate detection inside one push
-    uint32_t epoch = 0;
-    void reset(uint32_t n) { total.assign(n, 0); emitted.assign(n, 0); pending.assign(n, 0); mark.assign(n, 0); epoch = 0; }
+    void reset(uint32_t n) { total.assign(n, 0); emitted.assign(n, 0); pending.assign(n, 0); PushMarks::reset(n); }
     void reset_one(uint32_t s) { total[s] = 0; emitted[s] = 0; pending[s] = 0; }
 };
 
@@ -58,30 +56,21 @@ inline uint64_t fbank_stream_frames(const FbankStreamGeom &g, uint64_t n) { retu
 inline int fbank_stream_plan_push(const FbankStreamGeom &g, FbankStreamBook &bk, const uint32_t *ids, const uint32_t *lens, uint32_t n,
                                   FbankStreamPlan &pl, const char **err) {
     pl.entries.resize(n); pl.off.resize(n); pl.out_off.resize(n); pl.frames.resize(n); pl.continues.resize(n);
-    if (++bk.epoch == 0) { std::fill(bk.mark.begin(), bk.mark.end(), 0u); bk.epoch = 1; }
-    uint64_t cursor = 0, src_cursor = 0;
+    PushAdmission adm(bk, g.n_streams, g.max_chunk, g.n_mels);
     for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t s = ids[i];
-        if (s >= g.n_streams) { *err = "stream id out of range"; return 1; }
-        if (bk.mark[s] == bk.epoch) { *err = "a stream may appear only once per push"; return 1; }
-        bk.mark[s] = bk.epoch;
-        const uint32_t len = lens[i];
-        if (len > g.max_chunk) { *err = "chunk longer than max_chunk"; return 2; }
+        const uint32_t s = ids[i], len = lens[i];
+        StreamEntry &e = pl.entries[i];
+        if (const int rc = adm.admit(s, len, e, err)) return rc;
         const uint64_t e0 = bk.emitted[s], e1 = fbank_stream_frames(g, bk.total[s] + len);
-        const uint32_t pend = bk.pending[s];
+        adm.place(e, e1 - e0);
         pl.frames[i] = e1 - e0;
         pl.continues[i] = e0 > 0 ? 1u : 0u;
-        pl.off[i] = static_cast<uint64_t>(s) * g.stride + g.in_off - pend;          // sample e0 * shift of the stream
-        pl.out_off[i] = cursor;
-        cursor += (e1 - e0) * g.n_mels;
-        StreamEntry &e = pl.entries[i];
-        e = StreamEntry{};
-        e.stream = s; e.len = len; e.src_off = src_cursor; e.out_off = pl.out_off[i]; e.frames = static_cast<uint32_t>(e1 - e0);
+        pl.off[i] = static_cast<uint64_t>(s) * g.stride + g.in_off - bk.pending[s];          // sample e0 * shift of the stream
+        pl.out_off[i] = e.out_off;
         // the carry after the push: the samples from e1 * shift on and, once a frame has been emitted, the one in front of them
         e.keep = static_cast<uint32_t>(bk.total[s] + len - e1 * g.shift) + (e1 > 0 ? 1u : 0u);
-        src_cursor += len;
     }
-    pl.total_frames = g.n_mels ? cursor / g.n_mels : 0;
+    pl.total_frames = adm.total_frames();
     return 0;
 }
 

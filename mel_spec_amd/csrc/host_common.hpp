@@ -8,6 +8,7 @@
 //   fused512_route.hpp  route512: which of its kernels a batch runs on, the list of its instantiations (no HIP: host-testable)
 //   pow2.hip        generic_frame_kernel / pow2_frame_kernel / generic_stft_kernel: every other geometry, f64
 //   aux.hip         batch planners, streaming bank, TGA quantiser, VAD columns, stand-alone mel helpers, synthetic PCM
+//   stream_bank.hpp BankCore: what the streaming bank (aux.hip) and the Kaldi fbank's stream bank (fbank512.hip) share; includes this header
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
 #pragma once
 #include <hip/hip_runtime.h>
@@ -296,8 +297,9 @@ int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
                 int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order = false);
 void plan_ragged_done(RaggedSlot *sl, hipStream_t stream);
-// a table of a stream bank's push on its way to the device through a ring slot, and the launches of the scatter / carry kernels
-// (aux_kernels.hpp) for the banks outside aux.hip  (aux.hip)
+// a table on its way to the device through a ring slot (plan_ragged, the stream banks' entries), and the launches of the banks' scatter /
+// carry kernels (aux_kernels.hpp): the one launch site of each, behind stream_bank.hpp's core_run  (aux.hip)
+inline size_t round16(size_t v) { return (v + 15) & ~static_cast<size_t>(15); }
 int table_slot_take(RaggedScratch &ring, size_t bytes, RaggedSlot *&sl);
 int table_slot_upload(RaggedSlot &sl, size_t bytes, hipStream_t s);
 int stream_scatter_launch(float *state, uint64_t stride, uint32_t in_off, const StreamEntry *d_e, uint32_t n, const void *d_src, int pcm_dtype, hipStream_t s);

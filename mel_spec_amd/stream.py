@@ -22,8 +22,67 @@ def _u32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.uint32)
 
 
-class StreamBank:
+class _Bank:
+    """What the banks of live streams share: the handle's life, and the calls that differ by the C symbols' prefix (_P) only."""
+    _P = ""
+
+    def _fn(self, name: str):
+        return getattr(lib(), self._P + name)
+
+    def close(self) -> None:
+        if getattr(self, "_h", None):
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        if ids is None:
+            _check(self._fn("reset")(self._h, None, 0))
+        else:
+            a = _u32(ids)
+            _check(self._fn("reset")(self._h, a.ctypes.data_as(_u32p), a.shape[0]))
+
+    def frames_after(self, stream: int, n_new: int) -> int:
+        return int(self._fn("frames_after")(self._h, stream, n_new))
+
+    def input_ptr(self, stream: int) -> int:
+        return int(self._fn("input_ptr")(self._h, stream) or 0)
+
+    def _collect(self, out: np.ndarray, frames: np.ndarray, cap: Optional[int] = None) -> List[np.ndarray]:
+        assert cap is None or int(frames.sum()) == cap
+        res, cur = [], 0
+        for f in frames:
+            res.append(out[cur:cur + int(f)])
+            cur += int(f)
+        return res
+
+    @staticmethod
+    def _dev(ids: Sequence[int], lens: Sequence[int], *offsets):
+        """a device push's arguments: (frames to fill, n, the pointers of ids, lens and each optional list of uint64 offsets, the arrays)"""
+        arrs = [_u32(ids), _u32(lens)] + [None if o is None else np.ascontiguousarray(o, np.uint64) for o in offsets]
+        ptrs = [None if x is None else x.ctypes.data_as(C.POINTER(C.c_uint64) if x.dtype == np.uint64 else _u32p) for x in arrs]
+        return np.zeros(arrs[0].shape[0], np.uint32), arrs[0].shape[0], ptrs, arrs
+
+    def _gather(self, ids: Sequence[int], chunks: Sequence, allow_s16: bool):
+        """a push's arguments: (ids, PCM code, the chunks back to back, their lengths, rows the push will emit, a frames array to fill)"""
+        a = _u32(ids)
+        arrs = [np.asarray(c) for c in chunks]
+        assert len(arrs) == a.shape[0]
+        s16 = [allow_s16 and x.dtype == np.int16 for x in arrs]
+        if any(s16) and not all(s16):
+            raise ValueError("all chunks of one push must have the same dtype (np.int16, or float)")
+        pcm = PCM_S16 if arrs and all(s16) else PCM_F32
+        xs = [np.ascontiguousarray(x).ravel() if pcm == PCM_S16 else _f32(x).ravel() for x in arrs]
+        lens = _u32([x.shape[0] for x in xs])
+        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
+        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        return a, pcm, flat, lens, cap, np.zeros(a.shape[0], np.uint32)
+
+
+class StreamBank(_Bank):
     """n_streams independent Spectrogram::add states (src/stft.rs:48-86) on one HipMelSpectrogram's geometry."""
+    _P = "melspec_stream_"
 
     def __init__(self, mel: HipMelSpectrogram, n_streams: int, max_chunk: int):
         self._mel = mel                      # keeps the ctx alive
@@ -32,67 +91,31 @@ class StreamBank:
         _check(lib().melspec_stream_create(C.byref(h), mel._h, self.n_streams, self.max_chunk), construct=True)
         self._h = h
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().melspec_stream_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
-        if ids is None:
-            _check(lib().melspec_stream_reset(self._h, None, 0))
-        else:
-            a = _u32(ids)
-            _check(lib().melspec_stream_reset(self._h, a.ctypes.data_as(_u32p), a.shape[0]))
-
-    def frames_after(self, stream: int, n_new: int) -> int:
-        return int(lib().melspec_stream_frames_after(self._h, stream, n_new))
-
-    def _collect(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
-        res, cur = [], 0
-        for f in frames:
-            res.append(out[cur:cur + int(f)])
-            cur += int(f)
-        return res
+    def _flush_args(self, ids: Sequence[int], dtype=np.float32):
+        a = _u32(ids)
+        return a, np.empty((a.shape[0], self.n_mels), dtype), np.zeros(a.shape[0], np.uint32)
 
     def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
         """Append chunks[i] (any length <= max_chunk) to stream ids[i]; returns the frames each stream emitted, [k_i, n_mels]."""
-        a = _u32(ids)
-        xs = [_f32(c).ravel() for c in chunks]
-        assert len(xs) == a.shape[0]
-        lens = _u32([x.shape[0] for x in xs])
-        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
-        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        a, _, flat, lens, cap, frames = self._gather(ids, chunks, False)
         out = np.empty((cap, self.n_mels), np.float32)
-        frames = np.zeros(a.shape[0], np.uint32)
         _check(lib().melspec_stream_push_host(self._h, a.ctypes.data_as(_u32p), _fp(flat), lens.ctypes.data_as(_u32p), a.shape[0],
                                               _fp(out), out.size, frames.ctypes.data_as(_u32p)))
-        assert int(frames.sum()) == cap
-        return self._collect(out, frames)
+        return self._collect(out, frames, cap)
 
     def push_stft(self, ids: Sequence[int], chunks: Sequence, dtype=np.complex128, full: bool = True) -> List[np.ndarray]:
         """push() emitting what Spectrogram::add returns (src/stft.rs:48-86): [k_i, bins] complex spectra per stream."""
-        a = _u32(ids)
-        xs = [_f32(c).ravel() for c in chunks]
-        lens = _u32([x.shape[0] for x in xs])
-        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
+        a, _, flat, lens, cap, frames = self._gather(ids, chunks, False)
         dt = np.dtype(dtype)
-        bins = self._mel.stft_bins(full)
-        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
-        out = np.empty((cap, bins), dt)
-        frames = np.zeros(a.shape[0], np.uint32)
+        out = np.empty((cap, self._mel.stft_bins(full)), dt)
         _check(lib().melspec_stream_push_host_stft(self._h, a.ctypes.data_as(_u32p), _fp(flat), lens.ctypes.data_as(_u32p), a.shape[0],
                                                    out.ctypes.data_as(C.c_void_p), out.size, frames.ctypes.data_as(_u32p),
                                                    int(dt == np.dtype(np.complex128)), int(full)))
-        assert int(frames.sum()) == cap
-        return self._collect(out, frames)
+        return self._collect(out, frames, cap)
 
     def flush(self, ids: Sequence[int]) -> List[np.ndarray]:
         """Spectrogram::add with the pending (< hop) samples: zero-padded, at most one more frame per stream."""
-        a = _u32(ids)
-        out = np.empty((a.shape[0], self.n_mels), np.float32)
-        frames = np.zeros(a.shape[0], np.uint32)
+        a, out, frames = self._flush_args(ids)
         _check(lib().melspec_stream_flush_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
         return self._collect(out, frames)
 
@@ -104,32 +127,18 @@ class StreamBank:
         """push() with typed ends: np.int16 chunks are 16-bit PCM (value = sample / 32768, exactly) and cross the bus as such -- all
         chunks of one call have the same dtype; out_dtype "f16" (or np.float16) returns np.float16 rows, "bf16" the bfloat16 bit
         patterns as np.uint16 (numpy has no bfloat16): the f32 rows of push() rounded to nearest even."""
-        a = _u32(ids)
-        arrs = [np.asarray(c) for c in chunks]
-        assert len(arrs) == a.shape[0]
-        s16 = [x.dtype == np.int16 for x in arrs]
-        if any(s16) and not all(s16):
-            raise ValueError("all chunks of one push must have the same dtype (np.int16, or float)")
-        pcm = PCM_S16 if arrs and all(s16) else PCM_F32
-        xs = [np.ascontiguousarray(x).ravel() if pcm == PCM_S16 else _f32(x).ravel() for x in arrs]
+        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
         out_code = _out_code(out_dtype)
-        lens = _u32([x.shape[0] for x in xs])
-        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
-        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
         out = np.empty((cap, self.n_mels), _OUT_NUMPY[out_code])
-        frames = np.zeros(a.shape[0], np.uint32)
         _check(lib().melspec_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm,
                                                  lens.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size,
                                                  frames.ctypes.data_as(_u32p)))
-        assert int(frames.sum()) == cap
-        return self._collect(out, frames)
+        return self._collect(out, frames, cap)
 
     def flush_io(self, ids: Sequence[int], out_dtype) -> List[np.ndarray]:
         """flush() whose rows have the type of push_io's out_dtype"""
-        a = _u32(ids)
         out_code = _out_code(out_dtype)
-        out = np.empty((a.shape[0], self.n_mels), _OUT_NUMPY[out_code])
-        frames = np.zeros(a.shape[0], np.uint32)
+        a, out, frames = self._flush_args(ids, _OUT_NUMPY[out_code])
         _check(lib().melspec_stream_flush_host_io(self._h, a.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code,
                                                   out.size, frames.ctypes.data_as(_u32p)))
         return self._collect(out, frames)
@@ -168,42 +177,26 @@ class StreamBank:
 
     def push_vad(self, ids: Sequence[int], chunks: Sequence):
         """push() that also returns, per stream, what add_activity gives for each emitted frame (None or VoiceActivity)."""
-        a = _u32(ids)
-        xs = [_f32(c).ravel() for c in chunks]
-        assert len(xs) == a.shape[0]
-        lens = _u32([x.shape[0] for x in xs])
-        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
-        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        a, _, flat, lens, cap, frames = self._gather(ids, chunks, False)
         first = [self.vad_frames(int(s)) for s in a]
         out = np.empty((cap, self.n_mels), np.float32)
         acts = np.zeros(cap, ACTIVITY_DTYPE)
-        frames = np.zeros(a.shape[0], np.uint32)
         _check(lib().melspec_stream_push_host_vad(self._h, a.ctypes.data_as(_u32p), _fp(flat), lens.ctypes.data_as(_u32p), a.shape[0],
                                                   _fp(out), out.size, frames.ctypes.data_as(_u32p), acts.ctypes.data_as(C.c_void_p), cap))
-        assert int(frames.sum()) == cap
-        return self._collect(out, frames), self._activities(a, first, acts, frames)
+        return self._collect(out, frames, cap), self._activities(a, first, acts, frames)
 
     def flush_vad(self, ids: Sequence[int]):
-        a = _u32(ids)
+        a, out, frames = self._flush_args(ids)
         first = [self.vad_frames(int(s)) for s in a]
-        out = np.empty((a.shape[0], self.n_mels), np.float32)
         acts = np.zeros(a.shape[0], ACTIVITY_DTYPE)
-        frames = np.zeros(a.shape[0], np.uint32)
         _check(lib().melspec_stream_flush_host_vad(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p),
                                                    acts.ctypes.data_as(C.c_void_p), acts.shape[0]))
         return self._collect(out, frames), self._activities(a, first, acts, frames)
 
-    # ---- device producers -----------------------------------------------------------------
-    def input_ptr(self, stream: int) -> int:
-        return int(lib().melspec_stream_input_ptr(self._h, stream) or 0)
-
+    # ---- device producers (input_ptr: where a stream's next chunk goes) ---------------------
     def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, stream: int = 0) -> np.ndarray:
-        a, ln = _u32(ids), _u32(lens)
-        frames = np.zeros(a.shape[0], np.uint32)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
-        _check(lib().melspec_stream_push_device(self._h, a.ctypes.data_as(_u32p), ln.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_out),
-                                                None if oo is None else oo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                frames.ctypes.data_as(_u32p), C.c_void_p(stream)))
+        frames, n, (p_ids, p_lens, p_oo), _arrs = self._dev(ids, lens, out_offsets)
+        _check(lib().melspec_stream_push_device(self._h, p_ids, p_lens, n, C.c_void_p(d_out), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream)))
         return frames
 
     def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
@@ -211,101 +204,53 @@ class StreamBank:
         """push_device with typed ends.  d_chunks != 0: chunk i is lens[i] elements of pcm_dtype (PCM_F32 / PCM_S16) at d_chunks +
         src_offsets[i] elements (None: back to back), anywhere in device memory; d_chunks == 0: the chunks are at input_ptr, in f32.
         Rows of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back)."""
-        a, ln = _u32(ids), _u32(lens)
-        frames = np.zeros(a.shape[0], np.uint32)
-        u64p = C.POINTER(C.c_uint64)
-        so = None if src_offsets is None else np.ascontiguousarray(src_offsets, np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
-        _check(lib().melspec_stream_push_device_io(self._h, a.ctypes.data_as(_u32p), C.c_void_p(d_chunks or None), int(pcm_dtype),
-                                                   None if so is None else so.ctypes.data_as(u64p), ln.ctypes.data_as(_u32p), a.shape[0],
-                                                   C.c_void_p(d_out or None), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p),
-                                                   frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
+        _check(lib().melspec_stream_push_device_io(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
+                                                   int(out_dtype), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
         return frames
 
     def push_device_vad(self, ids: Sequence[int], lens: Sequence[int], d_out: int, d_acts: int, out_offsets=None, stream: int = 0) -> np.ndarray:
         """push_device whose activity records (ACTIVITY_DTYPE, packed in entry order) go to device memory at d_acts."""
-        a, ln = _u32(ids), _u32(lens)
-        frames = np.zeros(a.shape[0], np.uint32)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
-        _check(lib().melspec_stream_push_device_vad(self._h, a.ctypes.data_as(_u32p), ln.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_out),
-                                                    None if oo is None else oo.ctypes.data_as(C.POINTER(C.c_uint64)),
-                                                    frames.ctypes.data_as(_u32p), C.c_void_p(d_acts), C.c_void_p(stream)))
+        frames, n, (p_ids, p_lens, p_oo), _arrs = self._dev(ids, lens, out_offsets)
+        _check(lib().melspec_stream_push_device_vad(self._h, p_ids, p_lens, n, C.c_void_p(d_out), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(d_acts),
+                                                    C.c_void_p(stream)))
         return frames
 
 
-class FbankStreamBank:
+class FbankStreamBank(_Bank):
     """n_streams independent Fbank::compute streams (src/fbank.rs:141-236) on one Fbank's geometry (melspec_fbank_stream_*): after pushes
     whose chunks concatenate to x a stream has emitted exactly the rows of Fbank::compute(x) with apply_cmn off -- the bits of
     Fbank.compute on an apply_cmn = False twin, however x was cut -- and stats() returns the running column means of those rows.
     The Fbank must be on the fused path (uses_fast_path) with frame_shift <= frame_length."""
+    _P = "melspec_fbank_stream_"
 
     def __init__(self, fbank, n_streams: int, max_chunk: int):
         self._fbank = fbank                  # keeps the object alive
-        self._h = None
         self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), fbank.num_mel_bins
         h = C.c_void_p()
         _check(lib().melspec_fbank_stream_create(C.byref(h), fbank._h, self.n_streams, self.max_chunk), construct=True)
         self._h = h
 
-    def close(self) -> None:
-        if getattr(self, "_h", None):
-            lib().melspec_fbank_stream_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
     def reset(self, ids: Optional[Sequence[int]] = None) -> None:
         """no history, no frames, zero sums for the listed streams (None: all)"""
-        if ids is None:
-            _check(lib().melspec_fbank_stream_reset(self._h, None, 0))
-        else:
-            a = _u32(ids)
-            _check(lib().melspec_fbank_stream_reset(self._h, a.ctypes.data_as(_u32p), a.shape[0]))
-
-    def frames_after(self, stream: int, n_new: int) -> int:
-        return int(lib().melspec_fbank_stream_frames_after(self._h, stream, n_new))
+        super().reset(ids)
 
     def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
         """Append chunks[i] (any length <= max_chunk; np.int16 chunks are 16-bit PCM, value = sample / 32768 exactly, and all chunks of
         one call have the same dtype) to stream ids[i]; returns the rows each stream emitted, [k_i, num_mel_bins], before CMN."""
-        a = _u32(ids)
-        arrs = [np.asarray(c) for c in chunks]
-        assert len(arrs) == a.shape[0]
-        s16 = [x.dtype == np.int16 for x in arrs]
-        if any(s16) and not all(s16):
-            raise ValueError("all chunks of one push must have the same dtype (np.int16, or float)")
-        pcm = PCM_S16 if arrs and all(s16) else PCM_F32
-        xs = [np.ascontiguousarray(x).ravel() if pcm == PCM_S16 else _f32(x).ravel() for x in arrs]
-        lens = _u32([x.shape[0] for x in xs])
-        flat = np.concatenate(xs) if xs else np.zeros(0, np.float32)
-        cap = sum(self.frames_after(int(s), int(n)) for s, n in zip(a, lens))
+        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
         out = np.empty((cap, self.n_mels), np.float32)
-        frames = np.zeros(a.shape[0], np.uint32)
         _check(lib().melspec_fbank_stream_push_host(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
                                                     a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
-        assert int(frames.sum()) == cap
-        res, cur = [], 0
-        for f in frames:
-            res.append(out[cur:cur + int(f)])
-            cur += int(f)
-        return res
-
-    def input_ptr(self, stream: int) -> int:
-        return int(lib().melspec_fbank_stream_input_ptr(self._h, stream) or 0)
+        return self._collect(out, frames, cap)
 
     def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, d_chunks: int = 0, pcm_dtype: int = PCM_F32,
                     src_offsets=None, stream: int = 0) -> np.ndarray:
         """d_chunks == 0: the chunks are at input_ptr, in f32; otherwise chunk i is lens[i] elements of pcm_dtype at d_chunks +
         src_offsets[i] elements (None: back to back).  Rows go to d_out + out_offsets[i] floats (None: back to back)."""
-        a, ln = _u32(ids), _u32(lens)
-        frames = np.zeros(a.shape[0], np.uint32)
-        u64p = C.POINTER(C.c_uint64)
-        so = None if src_offsets is None else np.ascontiguousarray(src_offsets, np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, np.uint64)
-        _check(lib().melspec_fbank_stream_push_device(self._h, a.ctypes.data_as(_u32p), C.c_void_p(d_chunks or None), int(pcm_dtype),
-                                                      None if so is None else so.ctypes.data_as(u64p), ln.ctypes.data_as(_u32p), a.shape[0],
-                                                      C.c_void_p(d_out or None), None if oo is None else oo.ctypes.data_as(u64p),
-                                                      frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
+        _check(lib().melspec_fbank_stream_push_device(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
+                                                      p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
         return frames
 
     def stats(self, ids: Sequence[int]):

@@ -1,6 +1,6 @@
 // stream_scatter_host.cpp -- the index arithmetic of the typed stream_scatter_kernel (mel_spec_amd/csrc/aux_kernels.hpp) on the host,
 // for a sanitizer: the plan is the bank's own (stream_plan.hpp), the staging buffer and the state are heap blocks of exactly the sizes
-// aux.hip allocates less its slack, and the loop below restates the kernel -- a block per entry, 256 lanes striding the chunk,
+// the bank allocates (csrc/stream_bank.hpp: core_create, core_push_host) less their slack, and the loop below restates the kernel -- a block per entry, 256 lanes striding the chunk,
 // source at src_off + i in ELEMENTS of the sample type, value int16 * 2^-15.  A read or write outside either block is an ASan report;
 // the state is compared with the same pushes of the converted f32 chunks.  Stand-alone, never loaded into Python, never on a GPU:
 //   c++ -std=c++17 -O1 -g -fsanitize=address,undefined -Imel_spec_amd/csrc tests/cpp/stream_scatter_host.cpp -o /tmp/stream_scatter_host && /tmp/stream_scatter_host

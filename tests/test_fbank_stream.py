@@ -335,3 +335,31 @@ def test_gpu_unsupported_objects(gpu, oracle, jfk):
     b = bank.push([0], [x2[300:800]])[0]
     assert a.shape[0] == 0 and np.array_equal(_bits(b), _bits(fb.compute(x2)))
     bank.close(); fb.close()
+
+
+@pytest.mark.gpu
+def test_gpu_reset_with_a_bad_id_resets_nothing(gpu, oracle, jfk):
+    """melspec_fbank_stream_reset checks every id before it touches anything: reset([0, 7]) on a bank of two streams is INVALID_ARG and
+    stream 0, listed in front of the bad id, goes on where it was -- both streams' rows are the batch call's rows of all six shifts,
+    bit for bit."""
+    from mel_spec_amd import _lib
+    fb = gpu.Fbank(gpu.FbankConfig(apply_cmn=False))
+    bank = gpu.FbankStreamBank(fb, 2, 400)
+    src = [np.ascontiguousarray(jfk[20000:20000 + 960]), np.ascontiguousarray(jfk[41000:41000 + 960])]
+    got = [[], []]
+
+    def push_shifts(first):
+        for k in range(first, first + 3):
+            for i, r in enumerate(bank.push([0, 1], [s[k * 160:(k + 1) * 160] for s in src])):
+                got[i].append(r)
+
+    push_shifts(0)
+    with pytest.raises(gpu.HipError) as e:
+        bank.reset([0, 7])
+    assert e.value.code == _lib.ERR_INVALID_ARG and "out of range" in str(e.value)
+    push_shifts(3)
+    for i in range(2):
+        want = fb.compute(src[i])
+        mine = np.concatenate(got[i])
+        assert want.shape[0] == 4 and mine.shape == want.shape and np.array_equal(_bits(mine), _bits(want)), i
+    bank.close(); fb.close()

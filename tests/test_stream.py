@@ -315,3 +315,31 @@ def test_gpu_steady_state_pushes_reuse_the_previous_plan(gpu, oracle, jfk):
         assert mine.shape == want.shape and np.abs(mine - want).max() <= TOL, i
         assert tail[i].shape[0] == 0                              # nothing pending: a flush emits nothing
     d_out.free(); bank.close(); m.close()
+
+
+@pytest.mark.gpu
+def test_gpu_reset_with_a_bad_id_resets_nothing(gpu, oracle, jfk):
+    """melspec_stream_reset checks every id before it touches anything: reset([0, 7]) on a bank of two streams is INVALID_ARG and stream 0,
+    listed in front of the bad id, goes on where it was -- both streams' rows are the reference's rows of all six hops."""
+    from mel_spec_amd import _lib
+    hop = 160
+    m = gpu.HipMelSpectrogram(400, hop, SR, 80)
+    bank = gpu.StreamBank(m, 2, 400)
+    src = [jfk[20000:20000 + 6 * hop], jfk[41000:41000 + 6 * hop]]
+    got = [[], []]
+
+    def push_hops(first):
+        for k in range(first, first + 3):
+            for i, r in enumerate(bank.push([0, 1], [s[k * hop:(k + 1) * hop] for s in src])):
+                got[i].append(r)
+
+    push_hops(0)
+    with pytest.raises(gpu.HipError) as e:
+        bank.reset([0, 7])
+    assert e.value.code == _lib.ERR_INVALID_ARG and "out of range" in str(e.value)
+    push_hops(3)
+    for i in range(2):
+        want = oracle.stream_mel(src[i], 400, hop, 80, SR)
+        mine = np.concatenate(got[i])
+        assert want.shape[0] == 4 and mine.shape == want.shape and np.abs(mine - want).max() <= TOL, i
+    bank.close(); m.close()
