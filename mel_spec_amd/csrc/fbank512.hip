@@ -130,13 +130,18 @@ void apply_route(const Route512 &r, FbankFastParams &fp, const Fused512F32 &f32)
     if (info_of(r.run.kernel).f32) set_tables(fp, f32.ft, f32.d_blob);
     if (r.sync_rounds != kSyncKeep) fp.b.sync_rounds = r.sync_rounds;
 }
-// the compile-time bank an object's tables have, of the two its flavour has kernels for
+// an object's shape from its tables (shape512) with the decision its create call made (lab builds: MELSPEC_RUNTIME_LENS=1 forces the run-time loop)
 template <class A, class B>
-Bank512 bank512(const MelSlots &ms, Bank512 a, Bank512 b) { return fb_lens_match<A>(ms) ? a : fb_lens_match<B>(ms) ? b : Bank512::kRuntime; }
+Fused512Shape shape_of(Flavor512 flavor, bool fused, int waves, const MelSlots &ms, Bank512 a, Bank512 b) {
+    Fused512Shape s = shape512<A, B>(flavor, Reach512{fused, waves, 0}, ms, a, b, kFbSlots);
+    if (lab_runtime_lens()) s.bank = Bank512::kRuntime;
+    return s;
+}
 
 Fused512Shape w512_shape(const melspec_ctx *c) {
-    return Fused512Shape{Flavor512::kWhisper, c->fast512, bank512<LensSlaney80W, LensSlaney128>(c->ft512.slots, Bank512::kSlaney80W, Bank512::kSlaney128),
-                         c->ft512.slots.n_slots <= kFbSlots, c->waves512, c->f512.ok, c->precision, c->fix.adaptive, c->fix.count.p != nullptr, false};
+    Fused512Shape s = shape_of<LensSlaney80W, LensSlaney128>(Flavor512::kWhisper, c->fast512, c->waves512, c->ft512.slots, Bank512::kSlaney80W, Bank512::kSlaney128);
+    s.f32_built = c->f512.ok; s.precision = c->precision; s.adaptive = c->fix.adaptive; s.auto_possible = c->fix.count.p != nullptr;
+    return s;
 }
 
 // MELSPEC_PRECISION_AUTO at n_fft = 512: the voting f32 launch and, gated on its verdict, the f64 launch (w512_auto_kernel)
@@ -270,10 +275,10 @@ int melspec_fbank_create(melspec_fbank **out, int device, const melspec_fbank_co
     fb->fast = frame_len == 400 && fft_size == 512 &&
                build_fbank_fast_tables<double>(cfg->sample_rate, cfg->num_mel_bins, cfg->low_freq, high, cfg->use_power != 0, fb->ft);
     if (fb->fast) {
-        const size_t slice_bytes = FbankLayout<double>::slice_elems() * sizeof(double);
-        fb->waves = fused512_waves(fb->ft.blob.size() * 4, slice_bytes);
-        fb->fast_lds = fb->ft.blob.size() * 4 + static_cast<size_t>(fb->waves) * slice_bytes;
-        if (fb->fast_lds > kLdsLimit) fb->fast = false;
+        const Reach512 reach = fused512_reach(Flavor512::kKaldi, fb->ft.blob.size() * 4);
+        fb->waves = reach.waves;
+        fb->fast_lds = reach.lds_bytes;
+        fb->fast = reach.fused;
     }
     if (fb->fast && (rc = upload(fb->d_blob, fb->ft.blob))) return bail(rc);
     const std::vector<double> dense = kaldi_mel_filterbank(cfg->sample_rate, fft_size, cfg->num_mel_bins, cfg->low_freq, high);
@@ -308,8 +313,9 @@ int melspec_fbank_use_generic(melspec_fbank *fb, int on) {
 static double fbank_floor(const melspec_fbank *fb) { return fb->cfg.energy_floor > 0.0 ? fb->cfg.energy_floor : static_cast<double>(FLT_EPSILON); }
 
 static Fused512Shape fbank_shape(const melspec_fbank *fb) {
-    return Fused512Shape{Flavor512::kKaldi, fb->fast && !fb->use_generic, bank512<LensKaldi80, LensKaldi40>(fb->ft.slots, Bank512::kKaldi80, Bank512::kKaldi40),
-                         fb->ft.slots.n_slots <= kFbSlots, fb->waves, false, MELSPEC_PRECISION_F64, false, false, fb->cfg.apply_cmn && fb->cfg.use_power};
+    Fused512Shape s = shape_of<LensKaldi80, LensKaldi40>(Flavor512::kKaldi, fb->fast && !fb->use_generic, fb->waves, fb->ft.slots, Bank512::kKaldi80, Bank512::kKaldi40);
+    s.cmn_power = fb->cfg.apply_cmn && fb->cfg.use_power;
+    return s;
 }
 
 // the fused kernels' parameters of a batch of this object
@@ -606,8 +612,9 @@ uint64_t blm_padded(const melspec_blm *b, uint64_t frames) {         // pad_len,
 }
 
 Fused512Shape blm_shape(const melspec_blm *b) {
-    return Fused512Shape{Flavor512::kNemo, b->fast, bank512<LensSlaney128, LensSlaney80>(b->ft.slots, Bank512::kSlaney128, Bank512::kSlaney80),
-                         b->ft.slots.n_slots <= kFbSlots, b->waves, b->f32.ok, b->precision, false, false, false};
+    Fused512Shape s = shape_of<LensSlaney128, LensSlaney80>(Flavor512::kNemo, b->fast, b->waves, b->ft.slots, Bank512::kSlaney128, Bank512::kSlaney80);
+    s.f32_built = b->f32.ok; s.precision = b->precision;
+    return s;
 }
 
 // ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io) ---------------------------------------------------------------------
@@ -856,10 +863,10 @@ int melspec_blm_create(melspec_blm **out, int device, const melspec_blm_config *
     b->fast = cfg->n_fft == 512 && cfg->win_length == 400 &&
               build_blm_fast_tables<double>(cfg->sample_rate, cfg->n_mels, cfg->f_min, f_max, cfg->htk != 0, cfg->norm != 0, b->ft);
     if (b->fast) {
-        const size_t slice_bytes = FbankLayout<double>::slice_elems() * sizeof(double);
-        b->waves = fused512_waves(b->ft.blob.size() * 4, slice_bytes);
-        b->fast_lds = b->ft.blob.size() * 4 + static_cast<size_t>(b->waves) * slice_bytes + 64;      // + RoundSync counters
-        if (b->fast_lds > kLdsLimit) b->fast = false;
+        const Reach512 reach = fused512_reach(Flavor512::kNemo, b->ft.blob.size() * 4);      // (the RoundSync counters are part of the 8-or-4 question)
+        b->waves = reach.waves;
+        b->fast_lds = reach.lds_bytes;
+        b->fast = reach.fused;
     }
     if (b->fast) {
         if ((rc = upload(b->d_blob, b->ft.blob))) return bail(rc);

@@ -1,8 +1,11 @@
 // fused512_route.hpp -- which kernel of the fused 512-point family (fbank512_kernels.hpp and its _io / stats siblings) a batch of the
 // Kaldi fbank object, the NeMo frontend or an n_fft = 512 Whisper context runs on, as one pure function of the object's shape and the
 // kind of batch.  The lists below name every instantiation the library has; fbank512.hip expands the same lists into its table of kernel
-// pointers, so the two cannot drift.  Nothing from HIP in here: tests/cpp/route512_host.cpp builds it with the host compiler.
+// pointers, so the two cannot drift.  The shape itself -- eight waves or four, the launch's LDS, fused or not, the bank -- comes from the
+// object's tables through reach512 / shape512 below.  Nothing from HIP in here: tests/cpp/route512_host.cpp and reach512_host.cpp build it
+// with the host compiler.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/melspec_hip.h"
@@ -146,7 +149,7 @@ struct Fused512Shape {
     bool fused;              // on the fused 512-point kernels at all
     Bank512 bank;
     bool small_slots;        // n_slots <= kFbSlots
-    int waves;               // of the f64 kernels: 8, or 4 when the tables leave no room for eight slices (fused512_waves)
+    int waves;               // of the f64 kernels: 8, or 4 when the tables leave no room for eight slices (reach512)
     bool f32_built;          // the f32 tables exist (Fused512F32::ok)
     int precision;           // MELSPEC_PRECISION_*
     bool adaptive;           // AUTO votes (melspec_set_auto_adaptive)
@@ -163,6 +166,50 @@ enum class Batch512 {
     kStream,         // Kaldi: the pushes of the fbank stream bank as a ragged plain batch, a "continues" flag per clip, rows before CMN
 };
 constexpr int kSyncKeep = -2;      // Route512::sync_rounds: what the plan or the caller chose stays
+
+// ---- the shape from the tables ------------------------------------------------------------------------------------------------------
+// Eight waves or four, the dynamic LDS of the f64 launch and whether the object is on the fused kernels at all: a function of the flavour
+// and the bytes of the table blob, the same for the three create calls (melspec_fbank_create, melspec_blm_create, melspec_create at
+// n_fft = 512) and for tests/cpp/reach512_host.cpp.  The blob grows with the length of the filters' intervals, so it is a bank of few, wide
+// filters that takes four waves (1 .. 4 bins at 16 kHz), not one of many narrow ones.
+constexpr size_t kLds512Limit = 160 * 1024;        // gfx950: one workgroup may use the whole LDS of a CU (kLdsLimit; fbank512.hip asserts the two agree)
+constexpr size_t kSlice512Bytes = 17408;           // a wave's f64 slice, FbankLayout<double>::slice_elems() * 8 (asserted there too)
+// what a flavour keeps in LDS besides the blob and the slices: the Whisper flavour 512 bytes of frame maxima per wave, the NeMo flavour
+// RoundSync's sixteen counter words behind the slices
+constexpr size_t lds512_per_wave(Flavor512 f) { return kSlice512Bytes + (f == Flavor512::kWhisper ? 512 : 0); }
+constexpr size_t lds512_tail(Flavor512 f) { return f == Flavor512::kNemo ? 64 : 0; }
+struct Reach512 {
+    bool fused;              // the launch fits: the object runs on the fused 512-point kernels
+    int waves;               // 8 or 4
+    size_t lds_bytes;        // of a launch of `waves` f64 waves
+};
+constexpr Reach512 reach512_at(Flavor512 f, size_t blob_bytes, int waves) {
+    const size_t lds = blob_bytes + static_cast<size_t>(waves) * lds512_per_wave(f) + lds512_tail(f);
+    return Reach512{lds <= kLds512Limit, waves, lds};
+}
+// eight waves (two per SIMD) when everything the launch needs fits beside eight slices -- the flavour's extras included: asking with
+// blob + 8 slices alone sent a NeMo bank of exactly 24 576 bytes to eight waves, 64 bytes over, and from there off the fused path --
+// else four
+constexpr Reach512 reach512(Flavor512 f, size_t blob_bytes) {
+    return reach512_at(f, blob_bytes, 8).fused ? reach512_at(f, blob_bytes, 8) : reach512_at(f, blob_bytes, 4);
+}
+// do the tables' slots (a MelSlots) have exactly the compile-time slot lengths of Lens (fbank_wave.hpp)?
+template <class Lens, class Slots>
+bool lens_match512(const Slots &ms) {
+    if (ms.n_slots != Lens::kSlots) return false;
+    for (int i = 0; i < Lens::kSlots; ++i)
+        if (ms.len[i] != Lens::len(i) || ms.woff[i] != Lens::woff(i)) return false;
+    return true;
+}
+// the compile-time bank the tables have, of the two (A -> a, B -> b) the flavour has kernels for
+template <class A, class B, class Slots>
+Bank512 bank512(const Slots &ms, Bank512 a, Bank512 b) { return lens_match512<A>(ms) ? a : lens_match512<B>(ms) ? b : Bank512::kRuntime; }
+// an object's shape as its tables give it: flavour, fused, bank, slots, waves; the precision, AUTO's and the CMN fields are the object's own
+// state and start as a Kaldi object has them (f64, no f32 tables, no vote).  small_cap: kFbSlots
+template <class A, class B, class Slots>
+Fused512Shape shape512(Flavor512 f, const Reach512 &reach, const Slots &ms, Bank512 a, Bank512 b, int small_cap) {
+    return Fused512Shape{f, reach.fused, bank512<A, B>(ms, a, b), ms.n_slots <= small_cap, reach.waves, false, MELSPEC_PRECISION_F64, false, false, false};
+}
 
 struct Route512 {
     Launch512 run;           // the batch's mel kernel

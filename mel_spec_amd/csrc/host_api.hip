@@ -107,10 +107,10 @@ int create_ctx(melspec_ctx **out, int device, int fft_size, int hop_size, double
         else c->pt = std::move(pt);
     }
     if (!c->fast && fft_size == 512 && lab_int("MELSPEC_W512", 1, 0, 1) != 0 && build_whisper512_tables<double>(c->dense, n_mels, c->ft512)) {
-        const size_t slice_bytes = FbankLayout<double>::slice_elems() * sizeof(double) + 512;      // + the frame maxima
-        c->waves512 = fused512_waves(c->ft512.blob.size() * 4, slice_bytes);
-        c->lds512 = c->ft512.blob.size() * 4 + static_cast<size_t>(c->waves512) * slice_bytes;
-        c->fast512 = c->lds512 <= kLdsLimit;
+        const Reach512 reach = fused512_reach(Flavor512::kWhisper, c->ft512.blob.size() * 4);      // (a wave's slice + its frame maxima)
+        c->waves512 = reach.waves;
+        c->lds512 = reach.lds_bytes;
+        c->fast512 = reach.fused;
         if (c->fast512 && (rc = upload(c->d_blob512, c->ft512.blob))) return bail(rc);
         if (c->fast512 && w512_f32_bank(c->ft512.slots) && build_whisper512_tables<float>(c->dense, n_mels, c->f512.ft) && (rc = c->f512.finish(512))) return bail(rc);
         // MELSPEC_PRECISION_AUTO on the pair of 512-point kernels (round 6): the statistics words, the vote's tally and verdicts

@@ -388,21 +388,20 @@ int launch_generic(const GenericTables &gt, const BatchDesc &desc, int hop, int 
 int generic_allow_lds();          // hipFuncSetAttribute(generic_frame_kernel): once per context that runs on it
 
 // ---- fbank512.hip: the fused 512-point family -------------------------------------------------------------------------------------
-// Waves per workgroup of the fused 512-point kernels: 8 (two per SIMD, one workgroup per CU) when the tables
-// and eight 18.5 KB slices fit in LDS, else 4.
-inline int fused512_waves(size_t blob_bytes, size_t slice_bytes) {
-    if (lab_int("MELSPEC_FB_WAVES", 8, 4, 8) == 4) return 4;
-    return blob_bytes + 8 * slice_bytes <= kLdsLimit ? 8 : 4;
+// Waves per workgroup of the fused 512-point kernels (8: two per SIMD, one workgroup per CU; else 4), the launch's LDS and whether the
+// object is on them at all: reach512 (fused512_route.hpp).  Lab builds: MELSPEC_FB_WAVES=4 puts an eight-wave object on four.
+static_assert(kLds512Limit == kLdsLimit && kSlice512Bytes == FbankLayout<double>::slice_elems() * sizeof(double), "fused512_route.hpp spells the LDS sizes out");
+inline Reach512 fused512_reach(Flavor512 flavor, size_t blob_bytes) {
+    if (lab_int("MELSPEC_FB_WAVES", 8, 4, 8) == 4) return reach512_at(flavor, blob_bytes, 4);
+    return reach512(flavor, blob_bytes);
 }
 // does the context's bank have exactly the compile-time slot lengths of Lens?  (lab builds: MELSPEC_RUNTIME_LENS=1 forces the run-time loop)
-template <class Lens>
-bool fb_lens_match(const MelSlots &ms) {
+inline bool lab_runtime_lens() {
     static const bool off = lab_int("MELSPEC_RUNTIME_LENS", 0, 0, 1) != 0;
-    if (off || ms.n_slots != Lens::kSlots) return false;
-    for (int i = 0; i < Lens::kSlots; ++i)
-        if (ms.len[i] != Lens::len(i) || ms.woff[i] != Lens::woff(i)) return false;
-    return true;
+    return off;
 }
+template <class Lens>
+bool fb_lens_match(const MelSlots &ms) { return !lab_runtime_lens() && lens_match512<Lens>(ms); }
 
 // The f32 side of a fused 512-point context (MELSPEC_PRECISION_F32; NeMo / Whisper-512 with one of the compile-time banks).
 constexpr int kFused512F32Waves = 12;

@@ -1261,7 +1261,8 @@ def _ragged_set(oracle, jfk, seed, n=57, fft=400):
 
 
 @pytest.mark.parametrize("fft,hop,n_mels,mode", [(400, 160, 80, "auto"), (400, 160, 128, "auto"), (400, 160, 80, "f64"), (512, 160, 80, "auto"), (256, 100, 40, "auto"),
-                                                  (512, 160, 140, "auto")])      # 140 mels: tables too large for the 8-wave shape -> the 4-wave, round-robin 512-point kernel
+                                                  (512, 160, 140, "auto"),       # 140 mels: ten slots of run-time lengths on eight waves (kWRt10Runs); many narrow filters make a small blob
+                                                  (512, 160, 8, "auto")])        # 8 mels: few wide filters, a blob too large for eight slices -> the four-wave 512-point kernel (kWRt6x4)
 def test_ragged_batch_with_the_clip_table_in_device_memory(gpu, oracle, jfk, fft, hop, n_mels, mode):
     """melspec_compute_ragged_device_desc: offsets / lengths / output offsets are device arrays and the plan is built by a kernel;
     same bits as the host-table call, packed and scattered outputs, a generous and a tight frame bound."""
