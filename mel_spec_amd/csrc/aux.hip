@@ -773,8 +773,8 @@ static int stream_push_host_impl(melspec_stream *st, const uint32_t *ids, const 
     const StreamEmit &e = p.emit;
     // elements the caller receives: floats (mel rows) or complex values (spectra)
     const uint64_t need = pl.total_frames * (e.stft ? melspec_stft_bins(st->ctx, e.full) : static_cast<uint64_t>(st->ctx->n_mels));
-    const size_t esz = e.stft ? (e.dtype == MELSPEC_STFT_F64 ? 16 : 8) : (p.q.io >> 4) == MELSPEC_OUT_F32 ? sizeof(float) : 2;
-    const HostPush h{samples, out, out_capacity, need, (p.q.io & 15) == MELSPEC_PCM_S16 ? sizeof(io_s16) : sizeof(float), esz};
+    const size_t esz = e.stft ? (e.dtype == MELSPEC_STFT_F64 ? 16 : 8) : io_out_bytes(p.q.io >> 4);
+    const HostPush h{samples, out, out_capacity, need, io_pcm_bytes(p.q.io & 15), esz};
     rc = core_push_host(st->core, pl.entries.data(), n, h, [&](const void *d_src, void *d_out, hipStream_t s) {
         p.q.d_out = d_out;
         if (int rc2 = stream_run(st, p, d_src, s)) return rc2;      // the records go to the bank's own buffer (p.d_acts is NULL)
@@ -826,10 +826,7 @@ int melspec_stream_flush_host_vad(melspec_stream *st, const uint32_t *ids, uint3
 // 0: go on (io = pcm_dtype | out_dtype << 4); otherwise the status to return.  Nothing is queued and the bank is untouched on a refusal.
 static int stream_io_args(const melspec_stream *st, int pcm_dtype, int out_dtype, int &io) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "stream bank is NULL");
-    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
-        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
-    io = pcm_dtype | out_dtype << 4;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     if (out_dtype == MELSPEC_OUT_F32) return MELSPEC_OK;
     const melspec_ctx *c = st->ctx;
     if (!ctx_supports_io(c)) {
@@ -843,8 +840,7 @@ static int stream_io_args(const melspec_stream *st, int pcm_dtype, int out_dtype
 }
 
 int melspec_stream_supports_io(const melspec_stream *st, int pcm_dtype, int out_dtype) {
-    if (!st || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    if (!st || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
     return out_dtype == MELSPEC_OUT_F32 || ctx_supports_io(st->ctx) ? 1 : 0;
 }
 
@@ -874,7 +870,7 @@ int melspec_stream_push_device_io(melspec_stream *st, const uint32_t *ids, const
     if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
         return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
     if (!io && !d_chunks) return melspec_stream_push_device(st, ids, lens, n, static_cast<float *>(d_out), h_out_offsets, h_frames, stream);
-    if ((reinterpret_cast<uintptr_t>(d_chunks) & (pcm_dtype == MELSPEC_PCM_S16 ? 1 : 3)) || (reinterpret_cast<uintptr_t>(d_out) & (out_dtype == MELSPEC_OUT_F32 ? 3 : 1)))
+    if (io_misaligned(d_chunks, d_out, io))
         return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     return stream_push_device_impl(st, ids, lens, n, d_out, h_out_offsets, h_frames, nullptr, false, stream, io, d_chunks, h_src_offsets);
 }

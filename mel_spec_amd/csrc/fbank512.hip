@@ -189,24 +189,6 @@ int launch_whisper512(melspec_ctx *c, const BatchDesc &desc, hipStream_t stream)
 }  // namespace host
 }  // namespace melspec
 
-namespace {
-// ---- int16 PCM in / f16, bf16 rows out (melspec_blm_compute_*_io, melspec_fbank_compute_*_io): what the two objects share ----
-inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
-inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
-inline bool io_pcm_known(int t) { return t == MELSPEC_PCM_F32 || t == MELSPEC_PCM_S16; }
-inline bool io_out_known(int t) { return t == MELSPEC_OUT_F32 || t == MELSPEC_OUT_F16 || t == MELSPEC_OUT_BF16; }
-// 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
-int io_dtypes(int pcm_dtype, int out_dtype, int &io) {
-    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
-    if (!io_out_known(out_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
-    io = pcm_dtype | out_dtype << 4;
-    return MELSPEC_OK;
-}
-bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
-    return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
-}
-}  // namespace
-
 // ------------------------------------------------------------------------------------
 // Kaldi fbank context
 // ------------------------------------------------------------------------------------
@@ -1453,7 +1435,7 @@ int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d
     if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
     if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
         return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
-    if ((reinterpret_cast<uintptr_t>(d_chunks) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & 3))
+    if (io_misaligned(d_chunks, d_out, pcm_dtype))       // (the rows are f32: the out half of the code is 0)
         return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
         return fbs_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,

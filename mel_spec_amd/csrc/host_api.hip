@@ -290,21 +290,83 @@ int melspec_auto_state(melspec_ctx *c, int *heavy, double *fraction) {
     return MELSPEC_OK;
 }
 
-int melspec_compute_uniform_device(melspec_ctx *c, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
-                                   uint32_t n_clips, float *d_out, void *stream) {
+}  // extern "C"
+
+namespace {
+// each clip's frames and their total
+uint64_t count_frames(const melspec_ctx *c, const uint64_t *lengths, uint32_t n_clips, std::vector<uint64_t> &frames) {
+    frames.resize(n_clips);
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) { ctx_num_frames(c, lengths[i], frames[i]); total += frames[i]; }
+    return total;
+}
+
+// ---- int16 PCM in / f16, bf16 rows out ----------------------------------------------------------------------------------------------
+// 0: go on (io = the launch's code, 0 for (F32, F32)); otherwise the status to return
+int io_args(const melspec_ctx *c, int pcm_dtype, int out_dtype, int &io) {
     if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
+    if (io && !ctx_supports_io(c)) {
+        g_last_error = "int16 PCM / f16, bf16 rows are computed by the n_fft = 400 contexts with Whisper's 80- or 128-mel bank only; this context is n_fft = " +
+                       std::to_string(c->fft_size) + ", hop = " + std::to_string(c->hop_size) + ", n_mels = " + std::to_string(c->n_mels) +
+                       (c->fast ? " (another filterbank)" : "");
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    return MELSPEC_OK;
+}
+
+// The uniform batch of melspec_compute_uniform_device and of its _io form.  io = pcm_dtype | out_dtype << 4 (io_args): 0 is the f32 call and
+// launches exactly what it always did; otherwise vd_pcm / vd_out are int16 samples / f16, bf16 rows.  The plan counts elements either way;
+// the kernels read the two base addresses as their own types (BatchDesc).
+int ctx_uniform(melspec_ctx *c, const void *vd_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, void *vd_out, void *stream, int io) {
     if (n_clips == 0) return MELSPEC_OK;
     uint64_t fpc; ctx_num_frames(c, clip_len, fpc);
     if (fpc == 0) return MELSPEC_OK;   // empty output, like src/cuda.rs:91-93
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
     if (n_clips > 1 && clip_stride < clip_len && clip_stride != 0)
         return fail(MELSPEC_ERR_INVALID_ARG, "clip_stride smaller than clip_len");
     HIP_TRY(hipSetDevice(c->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    const BatchPlan pl = plan_uniform(d_pcm, d_out, clip_stride, fpc, n_clips, c->n_mels, ctx_frames_per_unit(c));
-    return launch_ctx(c, pl.desc, s);
+    const BatchPlan pl = plan_uniform(static_cast<const float *>(vd_pcm), static_cast<float *>(vd_out), clip_stride, fpc, n_clips, c->n_mels, ctx_frames_per_unit(c));
+    return launch_ctx(c, pl.desc, s, io);
 }
 
+// The ragged batch of melspec_compute_ragged_device and of its _io form (io: as in ctx_uniform); the host pipeline's launch too.
+int ctx_ragged(melspec_ctx *c, const void *vd_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips, void *vd_out,
+               const uint64_t *h_out_offsets, void *stream, int io) {
+    if (n_clips == 0) return MELSPEC_OK;
+    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
+    std::vector<uint64_t> frames;
+    if (count_frames(c, h_lengths, n_clips, frames) == 0) return MELSPEC_OK;
+    if (!vd_pcm || !vd_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    if (io && io_misaligned(vd_pcm, vd_out, io)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    HIP_TRY(hipSetDevice(c->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    int rc = plan_ragged(c->ragged, s, static_cast<const float *>(vd_pcm), static_cast<float *>(vd_out), h_offsets, frames, h_out_offsets, n_clips, c->n_mels,
+                         ctx_frames_per_unit(c), pl, slot);
+    if (!rc) rc = launch_ctx(c, pl.desc, s, io);
+    plan_ragged_done(slot, s);
+    return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int melspec_compute_uniform_device(melspec_ctx *c, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
+                                   uint32_t n_clips, float *d_out, void *stream) {
+    if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
+    return ctx_uniform(c, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, 0);
+}
+
+int melspec_compute_uniform_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                      uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
+    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return ctx_uniform(c, d_pcm, clip_stride, clip_len, n_clips, d_out, stream, io);
+}
 
 size_t melspec_interleaved_width(const melspec_ctx *c, size_t n_samples, size_t min_width) {
     if (!c) return 0;
@@ -332,22 +394,14 @@ int melspec_compute_ragged_device(melspec_ctx *c, const float *d_pcm, const uint
                                   const uint64_t *h_lengths, uint32_t n_clips, float *d_out,
                                   const uint64_t *h_out_offsets, void *stream) {
     if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    std::vector<uint64_t> frames(n_clips);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) { ctx_num_frames(c, h_lengths[i], frames[i]); total += frames[i]; }
-    if (total == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    HIP_TRY(hipSetDevice(c->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    BatchPlan pl;
-    RaggedSlot *slot = nullptr;
-    int rc = plan_ragged(c->ragged, s, d_pcm, d_out, h_offsets, frames, h_out_offsets, n_clips, c->n_mels,
-                         ctx_frames_per_unit(c), pl, slot);
-    if (!rc) rc = launch_ctx(c, pl.desc, s);
-    plan_ragged_done(slot, s);
-    return rc;
+    return ctx_ragged(c, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, 0);
+}
+
+int melspec_compute_ragged_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                     uint32_t n_clips, void *d_out, int out_dtype, const uint64_t *h_out_offsets, void *stream) {
+    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
+    if (rc) return rc;
+    return ctx_ragged(c, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, io);
 }
 
 int melspec_compute_ragged_device_desc(melspec_ctx *c, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths,
@@ -424,159 +478,68 @@ int melspec_synchronize(melspec_ctx *c, void *stream) {
 
 namespace {
 
-// clip (src, n) -> its frames at dst, cut into frame-aligned pieces of at most kPipeChunkSamples samples
-void push_segments(const melspec_ctx *c, const float *src, uint64_t n, float *dst, uint64_t frames, std::vector<HostSeg> &segs) {
+// clip (src, n) -> its frames at dst, cut into frame-aligned pieces of at most kPipeChunkSamples samples; ib / ob: the bytes of a sample and of
+// an output element (HostSeg's pointers are addresses only: the pipeline copies bytes)
+void push_segments(const melspec_ctx *c, const void *src, uint64_t n, void *dst, uint64_t frames, size_t ib, size_t ob, std::vector<HostSeg> &segs) {
     if (frames == 0) return;
     const uint64_t fft = static_cast<uint64_t>(c->fft_size), hop = static_cast<uint64_t>(c->hop_size);
-    if (n <= kPipeChunkSamples) { segs.push_back(HostSeg{src, n, dst, frames}); return; }
+    const char *s = static_cast<const char *>(src);
+    char *d = static_cast<char *>(dst);
+    auto seg = [&](uint64_t s0, uint64_t ns, uint64_t f0, uint64_t nf) {
+        segs.push_back(HostSeg{reinterpret_cast<const float *>(s + s0 * ib), ns, reinterpret_cast<float *>(d + f0 * static_cast<uint64_t>(c->n_mels) * ob), nf});
+    };
+    if (n <= kPipeChunkSamples) { seg(0, n, 0, frames); return; }
     const uint64_t per = (kPipeChunkSamples - fft) / hop + 1;      // frames per piece
     for (uint64_t f0 = 0; f0 < frames; f0 += per) {
         const uint64_t nf = frames - f0 < per ? frames - f0 : per;
-        segs.push_back(HostSeg{src + f0 * hop, (nf - 1) * hop + fft, dst + f0 * static_cast<uint64_t>(c->n_mels), nf});
+        seg(f0 * hop, (nf - 1) * hop + fft, f0, nf);
     }
 }
 
-int run_host_pipe(melspec_ctx *c, const std::vector<HostSeg> &segs) {
+int run_host_pipe(melspec_ctx *c, const std::vector<HostSeg> &segs, int io) {
     const char *where = "";
     const int rc = c->pipe.run(segs, c->n_mels, kPipeChunkSamples, c->stream,
-                               [c](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out,
-                                   const uint64_t *ooffs, hipStream_t s) {
-                                   return melspec_compute_ragged_device(c, d_in, offs, lens, n, d_out, ooffs, s);
-                               }, &where);
+                               [c, io](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out,
+                                       const uint64_t *ooffs, hipStream_t s) {
+                                   return ctx_ragged(c, d_in, offs, lens, n, d_out, ooffs, s, io);
+                               }, &where, io_pcm_bytes(io & 15), io_out_bytes(io >> 4));
     if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
     return rc;
+}
+
+// melspec_compute_host and its _io form (io: as in ctx_uniform): one clip, or frame-aligned pieces of a long one, through the host pipeline
+// (host_pipe.hpp; calls up to 32 MB take its single-chunk path: one copy each way by the runtime, one launch, one synchronise)
+int ctx_host(melspec_ctx *c, const void *samples, size_t n_samples, void *out, size_t out_capacity_elems, size_t *n_frames, int io) {
+    if (n_frames) *n_frames = 0;
+    uint64_t frames; ctx_num_frames(c, n_samples, frames);
+    if (frames == 0) return MELSPEC_OK;            // Ok(Vec::new()), src/cuda.rs:91-93
+    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
+    if (out_capacity_elems < frames * static_cast<uint64_t>(c->n_mels)) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(c->dev.device));
+    std::vector<HostSeg> segs;
+    push_segments(c, samples, n_samples, out, frames, io_pcm_bytes(io & 15), io_out_bytes(io >> 4), segs);
+    if (int rc = run_host_pipe(c, segs, io)) return rc;
+    if (n_frames) *n_frames = static_cast<size_t>(frames);
+    return MELSPEC_OK;
 }
 }  // namespace
 
 int melspec_compute_host(melspec_ctx *c, const float *samples, size_t n_samples, float *out,
                          size_t out_capacity_floats, size_t *n_frames) {
     if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
-    if (n_frames) *n_frames = 0;
-    uint64_t frames; ctx_num_frames(c, n_samples, frames);
-    if (frames == 0) return MELSPEC_OK;            // Ok(Vec::new()), src/cuda.rs:91-93
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    const uint64_t need = frames * static_cast<uint64_t>(c->n_mels);
-    if (out_capacity_floats < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(c->dev.device));
-    int rc;
-    // one clip, or frame-aligned pieces of a long one, through the host pipeline (host_pipe.hpp; calls up to 32 MB take its
-    // single-chunk path: one copy each way by the runtime, one launch, one synchronise)
-    std::vector<HostSeg> segs;
-    push_segments(c, samples, n_samples, out, frames, segs);
-    if ((rc = run_host_pipe(c, segs))) return rc;
-    if (n_frames) *n_frames = static_cast<size_t>(frames);
-    return MELSPEC_OK;
+    return ctx_host(c, samples, n_samples, out, out_capacity_floats, n_frames, 0);
 }
-
-// ---- int16 PCM in / f16, bf16 rows out ----------------------------------------------------------------------------------------------
-namespace {
-inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
-inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
-// 0: go on (io = the launch's code, 0 for (F32, F32)); otherwise the status to return
-int io_args(const melspec_ctx *c, int pcm_dtype, int out_dtype, int &io) {
-    if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
-    if (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16)
-        return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
-    io = pcm_dtype | out_dtype << 4;
-    if (io && !ctx_supports_io(c)) {
-        g_last_error = "int16 PCM / f16, bf16 rows are computed by the n_fft = 400 contexts with Whisper's 80- or 128-mel bank only; this context is n_fft = " +
-                       std::to_string(c->fft_size) + ", hop = " + std::to_string(c->hop_size) + ", n_mels = " + std::to_string(c->n_mels) +
-                       (c->fast ? " (another filterbank)" : "");
-        return MELSPEC_ERR_UNSUPPORTED;
-    }
-    return MELSPEC_OK;
-}
-}  // namespace
 
 int melspec_supports_io(const melspec_ctx *c, int pcm_dtype, int out_dtype) {
-    if (!c || (pcm_dtype != MELSPEC_PCM_F32 && pcm_dtype != MELSPEC_PCM_S16)) return 0;
-    if (out_dtype != MELSPEC_OUT_F32 && out_dtype != MELSPEC_OUT_F16 && out_dtype != MELSPEC_OUT_BF16) return 0;
+    if (!c || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
     return (pcm_dtype == MELSPEC_PCM_F32 && out_dtype == MELSPEC_OUT_F32) || ctx_supports_io(c) ? 1 : 0;
-}
-
-int melspec_compute_uniform_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
-                                      uint32_t n_clips, void *d_out, int out_dtype, void *stream) {
-    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
-    if (rc) return rc;
-    if (!io) return melspec_compute_uniform_device(c, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_out), stream);
-    if (n_clips == 0) return MELSPEC_OK;
-    uint64_t fpc; ctx_num_frames(c, clip_len, fpc);
-    if (fpc == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if ((reinterpret_cast<uintptr_t>(d_pcm) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (io_out_bytes(out_dtype) - 1)))
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    if (n_clips > 1 && clip_stride < clip_len && clip_stride != 0)
-        return fail(MELSPEC_ERR_INVALID_ARG, "clip_stride smaller than clip_len");
-    HIP_TRY(hipSetDevice(c->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    // the plan counts elements; the kernels read the two base addresses as their own types (BatchDesc)
-    const BatchPlan pl = plan_uniform(static_cast<const float *>(d_pcm), static_cast<float *>(d_out), clip_stride, fpc, n_clips, c->n_mels, ctx_frames_per_unit(c));
-    return launch_ctx(c, pl.desc, s, io);
-}
-
-int melspec_compute_ragged_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths,
-                                     uint32_t n_clips, void *d_out, int out_dtype, const uint64_t *h_out_offsets, void *stream) {
-    int io, rc = io_args(c, pcm_dtype, out_dtype, io);
-    if (rc) return rc;
-    if (!io) return melspec_compute_ragged_device(c, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_out), h_out_offsets, stream);
-    if (n_clips == 0) return MELSPEC_OK;
-    if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    std::vector<uint64_t> frames(n_clips);
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) { ctx_num_frames(c, h_lengths[i], frames[i]); total += frames[i]; }
-    if (total == 0) return MELSPEC_OK;
-    if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
-    if ((reinterpret_cast<uintptr_t>(d_pcm) & (io_pcm_bytes(pcm_dtype) - 1)) || (reinterpret_cast<uintptr_t>(d_out) & (io_out_bytes(out_dtype) - 1)))
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    HIP_TRY(hipSetDevice(c->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
-    BatchPlan pl;
-    RaggedSlot *slot = nullptr;
-    rc = plan_ragged(c->ragged, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_out), h_offsets, frames, h_out_offsets, n_clips, c->n_mels,
-                     ctx_frames_per_unit(c), pl, slot);
-    if (!rc) rc = launch_ctx(c, pl.desc, s, io);
-    plan_ragged_done(slot, s);
-    return rc;
 }
 
 int melspec_compute_host_io(melspec_ctx *c, const void *samples, int pcm_dtype, size_t n_samples, void *out, int out_dtype,
                             size_t out_capacity_elems, size_t *n_frames) {
     int io, rc = io_args(c, pcm_dtype, out_dtype, io);
     if (rc) return rc;
-    if (!io) return melspec_compute_host(c, static_cast<const float *>(samples), n_samples, static_cast<float *>(out), out_capacity_elems, n_frames);
-    if (n_frames) *n_frames = 0;
-    uint64_t frames; ctx_num_frames(c, n_samples, frames);
-    if (frames == 0) return MELSPEC_OK;
-    if (!samples || !out) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-    if (out_capacity_elems < frames * static_cast<uint64_t>(c->n_mels)) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
-    HIP_TRY(hipSetDevice(c->dev.device));
-    // push_segments' cut (the same sample count per piece), in bytes of the two element types
-    const size_t ib = io_pcm_bytes(pcm_dtype), ob = io_out_bytes(out_dtype);
-    const uint64_t fft = static_cast<uint64_t>(c->fft_size), hop = static_cast<uint64_t>(c->hop_size);
-    const char *src = static_cast<const char *>(samples);
-    char *dst = static_cast<char *>(out);
-    std::vector<HostSeg> segs;
-    auto seg = [&](uint64_t s0, uint64_t n, uint64_t f0, uint64_t nf) {
-        segs.push_back(HostSeg{reinterpret_cast<const float *>(src + s0 * ib), n, reinterpret_cast<float *>(dst + f0 * static_cast<uint64_t>(c->n_mels) * ob), nf});
-    };
-    if (n_samples <= kPipeChunkSamples) seg(0, n_samples, 0, frames);
-    else {
-        const uint64_t per = (kPipeChunkSamples - fft) / hop + 1;      // frames per piece
-        for (uint64_t f0 = 0; f0 < frames; f0 += per) {
-            const uint64_t nf = frames - f0 < per ? frames - f0 : per;
-            seg(f0 * hop, (nf - 1) * hop + fft, f0, nf);
-        }
-    }
-    const char *where = "";
-    rc = c->pipe.run(segs, c->n_mels, kPipeChunkSamples, c->stream,
-                     [c, pcm_dtype, out_dtype](const float *d_in, const uint64_t *offs, const uint64_t *lens, uint32_t n, float *d_out, const uint64_t *ooffs, hipStream_t s) {
-                         return melspec_compute_ragged_device_io(c, d_in, pcm_dtype, offs, lens, n, d_out, out_dtype, ooffs, s);
-                     }, &where, ib, ob);
-    if (rc > 0 && where[0] && std::strcmp(where, "kernel launch") != 0) return fail_hip(static_cast<hipError_t>(rc), where);
-    if (rc) return rc;
-    if (n_frames) *n_frames = static_cast<size_t>(frames);
-    return MELSPEC_OK;
+    return ctx_host(c, samples, n_samples, out, out_capacity_elems, n_frames, io);
 }
 
 int melspec_compute_batch_host(melspec_ctx *c, const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips,
@@ -587,20 +550,22 @@ int melspec_compute_batch_host(melspec_ctx *c, const float *samples, const uint6
     if (!offsets || !lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
     std::vector<HostSeg> segs;
     segs.reserve(n_clips);
-    uint64_t total = 0, cursor = 0;
+    std::vector<uint64_t> frames;
+    const uint64_t total = count_frames(c, lengths, n_clips, frames);
+    uint64_t cursor = 0;
     for (uint32_t i = 0; i < n_clips; ++i) {
-        uint64_t f; ctx_num_frames(c, lengths[i], f);
+        const uint64_t f = frames[i];
         const uint64_t oo = out_offsets ? out_offsets[i] : cursor;
         const uint64_t fl = f * static_cast<uint64_t>(c->n_mels);
         if (f && oo + fl > out_capacity_floats) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
         if (f && (!samples || !out)) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
-        push_segments(c, samples + offsets[i], lengths[i], out + oo, f, segs);
-        cursor += fl; total += f;
+        push_segments(c, samples + offsets[i], lengths[i], out + oo, f, sizeof(float), sizeof(float), segs);
+        cursor += fl;
     }
     if (total_frames) *total_frames = total;
     if (total == 0) return MELSPEC_OK;
     HIP_TRY(hipSetDevice(c->dev.device));
-    return run_host_pipe(c, segs);
+    return run_host_pipe(c, segs, 0);
 }
 
 
@@ -631,10 +596,8 @@ int melspec_stft_ragged_device(melspec_ctx *c, const float *d_pcm, const uint64_
     if (rc) return rc;
     if (n_clips == 0) return MELSPEC_OK;
     if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
-    std::vector<uint64_t> frames(n_clips), oo;
-    uint64_t total = 0;
-    for (uint32_t i = 0; i < n_clips; ++i) { ctx_num_frames(c, h_lengths[i], frames[i]); total += frames[i]; }
-    if (total == 0) return MELSPEC_OK;
+    std::vector<uint64_t> frames, oo;
+    if (count_frames(c, h_lengths, n_clips, frames) == 0) return MELSPEC_OK;
     if (!d_pcm || !d_out) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
     HIP_TRY(hipSetDevice(c->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;

@@ -64,6 +64,22 @@ inline int fail_hip(hipError_t e, const char *where) {
         if (e_ != hipSuccess) return fail_hip(e_, #expr);     \
     } while (0)
 
+// ---- int16 PCM in / f16, bf16 rows out: the dtype codes of every _io entry point (the ctx's, the fbank's, the blm's, the stream banks') ----
+inline size_t io_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
+inline size_t io_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
+inline bool io_pcm_known(int t) { return t == MELSPEC_PCM_F32 || t == MELSPEC_PCM_S16; }
+inline bool io_out_known(int t) { return t == MELSPEC_OUT_F32 || t == MELSPEC_OUT_F16 || t == MELSPEC_OUT_BF16; }
+// 0: go on (io = pcm_dtype | out_dtype << 4, 0 for (F32, F32)); otherwise the status to return
+inline int io_dtypes(int pcm_dtype, int out_dtype, int &io) {
+    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    if (!io_out_known(out_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16");
+    io = pcm_dtype | out_dtype << 4;
+    return MELSPEC_OK;
+}
+inline bool io_misaligned(const void *vd_pcm, const void *vd_out, int io) {
+    return (reinterpret_cast<uintptr_t>(vd_pcm) & (io_pcm_bytes(io & 15) - 1)) || (reinterpret_cast<uintptr_t>(vd_out) & (io_out_bytes(io >> 4) - 1));
+}
+
 constexpr int kGenericNT = 256;
 constexpr int kMaxGenericFft = 4096;
 constexpr int kMaxGenericMels = 1024;

@@ -147,8 +147,168 @@ def device_synchronize() -> None:
     _check(lib().melspec_device_synchronize())
 
 
-class HipMelSpectrogram:
+def _u64_tables(*tables):
+    """the offset / length tables of a ragged call -> (their uint64 arrays, for the caller to hold during the call; the arrays' pointers);
+    None stays None"""
+    arrs = [None if t is None else np.ascontiguousarray(t, dtype=np.uint64) for t in tables]
+    return arrs, [None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint64)) for a in arrs]
+
+
+def _flatten(clips):
+    """list of 1-D host arrays of any lengths -> (the clips back to back, their offsets, their lengths)"""
+    arrs = [_f32(c).reshape(-1) for c in clips]
+    lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
+    return np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32), offs, lens
+
+
+def _split(out: np.ndarray, shapes) -> list:
+    """a flat, packed result -> one array per clip, of the clips' shapes"""
+    res, cur = [], 0
+    for r, c in shapes:
+        res.append(out[cur:cur + r * c].reshape(r, c))
+        cur += r * c
+    return res
+
+
+def _pcm_clip(samples):
+    """one host clip of a *_host_io call -> (flat samples, PCM code): an np.int16 array is 16-bit PCM and stays as it is, anything else f32"""
+    a = np.asarray(samples)
+    pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+    return np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1), pcm
+
+
+class _Frontend:
+    """What the three frontends share: the handle's life, and the calls that differ only by the C symbols' prefix (_P) and by the shape of
+    one clip's result (_clip_shape: rows x features, or features x columns)."""
+    _P = ""
+    _MIN_OUT = 1          # floats compute_batch_host allocates at least
+
+    def _fn(self, name: str):
+        return getattr(lib(), self._P + name)
+
+    def _clip_shape(self, n_samples: int) -> tuple:
+        raise NotImplementedError
+
+    def _packed(self, lens):
+        """the shapes of the clips' results and the floats they take, packed"""
+        shapes = [self._clip_shape(int(n)) for n in lens]
+        return shapes, sum(r * c for r, c in shapes)
+
+    def num_frames(self, n_samples: int) -> int:
+        return int(self._fn("num_frames")(self._h, n_samples))
+
+    def compute_uniform_device(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int,
+                               stream: int = 0) -> None:
+        """Device pointers in, device pointers out, asynchronous on `stream`."""
+        _check(self._fn("compute_uniform_device")(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
+                                                  C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def compute_ragged_device(self, d_pcm: int, offsets, lengths, d_out: int, out_offsets=None, stream: int = 0) -> None:
+        """clip i = d_pcm[offsets[i] : + lengths[i]] -> its result at d_out + out_offsets[i] floats (None = packed)"""
+        tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+        _check(self._fn("compute_ragged_device")(self._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0],
+                                                 C.c_void_p(d_out), p_out, C.c_void_p(stream)))
+
+    def _compute_ragged_device_desc(self, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
+                                    max_total_frames: int, stream: int = 0) -> None:
+        """*_compute_ragged_device_desc: the clip table (u64 offsets / lengths / output offsets) lives in device memory"""
+        _check(self._fn("compute_ragged_device_desc")(self._h, C.c_void_p(d_pcm), C.c_void_p(d_offsets), C.c_void_p(d_lengths), n_clips,
+                                                      C.c_void_p(d_out), C.c_void_p(d_out_offsets) if d_out_offsets else None,
+                                                      max_total_frames, C.c_void_p(stream)))
+
+    # -- 16-bit ends: int16 PCM in, f16 / bf16 rows out (melspec_hip.h; codes PCM_* / OUT_* of this module) ---------------------------
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(self._fn("supports_io")(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
+                                  stream: int = 0) -> None:
+        """compute_uniform_device on int16 samples and / or into f16 / bf16 rows; strides count elements."""
+        _check(self._fn("compute_uniform_device_io")(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
+                                                     C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
+
+    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
+                                 stream: int = 0) -> None:
+        """compute_ragged_device on int16 samples and / or into f16 / bf16 rows; offsets and lengths count elements."""
+        tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+        _check(self._fn("compute_ragged_device_io")(self._h, C.c_void_p(d_pcm), int(pcm_dtype), p_off, p_len, tabs[0].shape[0],
+                                                    C.c_void_p(d_out), int(out_dtype), p_out, C.c_void_p(stream)))
+
+    def synchronize(self, stream: int = 0) -> None:
+        _check(self._fn("synchronize")(self._h, C.c_void_p(stream)))
+
+    def release_scratch(self) -> None:
+        """give the object's grow-only scratch back (pipeline / staging buffers, ragged plans); the next call re-allocates"""
+        _check(self._fn("release_scratch")(self._h))
+
+    def compute_batch_host(self, flat: np.ndarray, offsets, lengths, out: np.ndarray | None = None, out_offsets=None):
+        """*_compute_batch_host: clip i = flat[offsets[i] : offsets[i] + lengths[i]] -> its result at out[out_offsets[i]:] (floats; None =
+        packed), whole clips through the chunked host pipeline.  Returns (out, total frames / columns).  flat / out may be pinned
+        (HostBuffer.array)."""
+        x = flat if isinstance(flat, np.ndarray) and flat.dtype == np.float32 and flat.flags.c_contiguous else _f32(flat).reshape(-1)
+        tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+        if out is None:
+            out = np.empty(max(self._packed(tabs[1])[1], self._MIN_OUT), np.float32)
+        total = C.c_uint64(0)
+        _check(self._fn("compute_batch_host")(self._h, _fp(x.reshape(-1)), p_off, p_len, tabs[0].shape[0],
+                                              _fp(out.reshape(-1)), p_out, out.size, C.byref(total)))
+        return out, int(total.value)
+
+    def _compute_many(self, clips) -> list:
+        """list of 1-D host arrays of any lengths -> list of the clips' results, one call of the host pipeline"""
+        flat, offs, lens = _flatten(clips)
+        out, _ = self.compute_batch_host(flat, offs, lens)
+        return _split(out, self._packed(lens)[0])
+
+    def compute_ragged(self, clips) -> list:
+        """list of 1-D host arrays of any lengths -> list of the clips' results, one launch"""
+        flat, offs, lens = _flatten(clips)
+        shapes, total = self._packed(lens)
+        din, dout = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * 4, 16))
+        try:
+            din.upload(flat)
+            self.compute_ragged_device(din.ptr, offs, lens, dout.ptr)
+            self.synchronize()
+            out = dout.download((max(total, 1),))[:total]
+        finally:
+            din.free(); dout.free()
+        return _split(out, shapes)
+
+    def compute_batch(self, clips) -> np.ndarray:
+        """[n_clips, clip_len] host f32 -> [n_clips, *the shape of a clip's result] host f32, one launch"""
+        x = _f32(clips)
+        n_clips, clip_len = x.shape
+        shape = (n_clips,) + self._clip_shape(clip_len)
+        if 0 in shape:
+            return np.zeros(shape, np.float32)
+        din, dout = DeviceBuffer(x.nbytes), DeviceBuffer(int(np.prod(shape)) * 4)
+        try:
+            din.upload(x)
+            self.compute_uniform_device(din.ptr, clip_len, clip_len, n_clips, dout.ptr)
+            self.synchronize()
+            return dout.download(shape)
+        finally:
+            din.free(); dout.free()
+
+    def close(self) -> None:
+        if self._h is not None:
+            self._fn("destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class HipMelSpectrogram(_Frontend):
     """MI355X twin of CudaMelSpectrogram (src/cuda.rs:27-140)."""
+    _P = "melspec_"
+    _MIN_OUT = 0          # compute_batch_host allocates exactly the batch's floats
+
+    def _clip_shape(self, n_samples: int) -> tuple:
+        return self.num_frames(n_samples), self.n_mels
 
     def __init__(self, fft_size: int, hop_size: int, sampling_rate: float, n_mels: int, device: int = -1, filterbank=None):
         """filterbank: None = MelSpectrogram::new's mel(sr, fft, n_mels, None, None, false, true); a dict(f_min=, f_max=, htk=, norm=)
@@ -183,11 +343,9 @@ class HipMelSpectrogram:
         Additive: an np.int16 array is taken as 16-bit PCM (value = sample / 32768, exactly) and crosses the bus as such; out_dtype
         "f16" (or np.float16) returns np.float16 rows, "bf16" the bfloat16 bit patterns as np.uint16 (numpy has no bfloat16) -- the f32
         row values rounded to nearest even (melspec_compute_host_io)."""
-        a = np.asarray(samples)
-        pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        x, pcm = _pcm_clip(samples)
         out = _out_code(out_dtype)
         if pcm != PCM_F32 or out != OUT_F32:
-            x = np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1)
             nf = self.num_frames(x.shape[0])
             res = np.empty((nf, self.n_mels), _OUT_NUMPY[out])
             got = C.c_size_t(0)
@@ -195,7 +353,6 @@ class HipMelSpectrogram:
                                                  res.size, C.byref(got)))
             assert got.value == nf
             return res
-        x = _f32(samples).reshape(-1)
         nf = self.num_frames(x.shape[0])
         out = np.empty((nf, self.n_mels), np.float32)
         got = C.c_size_t(0)
@@ -204,9 +361,6 @@ class HipMelSpectrogram:
         return out
 
     # -- additive surface ---------------------------------------------------------------
-    def num_frames(self, n_samples: int) -> int:
-        return int(lib().melspec_num_frames(self._h, n_samples))
-
     @property
     def uses_fast_path(self) -> bool:
         return bool(lib().melspec_uses_fast_path(self._h))
@@ -270,15 +424,9 @@ class HipMelSpectrogram:
                                                  C.c_void_p(stream)))
 
     def stft_ragged_device(self, d_pcm: int, offsets, lengths, d_out: int, out_offsets=None, f64: bool = False, full: bool = False, stream: int = 0) -> None:
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_stft_ragged_device(self._h, C.c_void_p(d_pcm), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-                                                C.c_void_p(d_out), None if oo is None else oo.ctypes.data_as(u64p), int(f64), int(full), C.c_void_p(stream)))
-
-    def release_scratch(self) -> None:
-        _check(lib().melspec_release_scratch(self._h))
+        tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+        _check(lib().melspec_stft_ragged_device(self._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0],
+                                                C.c_void_p(d_out), p_out, int(f64), int(full), C.c_void_p(stream)))
 
     def plain_kernel_name(self) -> str:
         return (lib().melspec_plain_kernel_name(self._h) or b"").decode()
@@ -307,12 +455,6 @@ class HipMelSpectrogram:
         self._guard_seen = total
         return last
 
-    def compute_uniform_device(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int,
-                               stream: int = 0) -> None:
-        """Device pointers in, device pointers out, asynchronous on `stream`."""
-        _check(lib().melspec_compute_uniform_device(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
-                                                    C.c_void_p(d_out), C.c_void_p(stream)))
-
     def interleaved_width(self, n_samples: int, min_width: int = 0) -> int:
         return int(lib().melspec_interleaved_width(self._h, n_samples, min_width))
 
@@ -338,45 +480,7 @@ class HipMelSpectrogram:
         finally:
             din.free(); dout.free()
 
-    def compute_ragged_device(self, d_pcm: int, offsets, lengths, d_out: int, out_offsets=None, stream: int = 0) -> None:
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_compute_ragged_device(
-            self._h, C.c_void_p(d_pcm), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-            C.c_void_p(d_out), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
-
-    # -- 16-bit ends: int16 PCM in, f16 / bf16 rows out (melspec_hip.h; codes PCM_* / OUT_* of this module) ---------------------------
-    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
-        return bool(lib().melspec_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
-
-    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
-                                  stream: int = 0) -> None:
-        """compute_uniform_device on int16 samples and / or into f16 / bf16 rows; strides count elements."""
-        _check(lib().melspec_compute_uniform_device_io(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
-                                                       C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
-
-    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
-                                 stream: int = 0) -> None:
-        """compute_ragged_device on int16 samples and / or into f16 / bf16 rows; offsets and lengths count elements."""
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_compute_ragged_device_io(
-            self._h, C.c_void_p(d_pcm), int(pcm_dtype), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-            C.c_void_p(d_out), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
-
-    def compute_ragged_device_desc(self, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
-                                   max_total_frames: int, stream: int = 0) -> None:
-        """melspec_compute_ragged_device_desc: the clip table (u64 offsets / lengths / output offsets) lives in device memory"""
-        _check(lib().melspec_compute_ragged_device_desc(self._h, C.c_void_p(d_pcm), C.c_void_p(d_offsets), C.c_void_p(d_lengths), n_clips,
-                                                        C.c_void_p(d_out), C.c_void_p(d_out_offsets) if d_out_offsets else None,
-                                                        max_total_frames, C.c_void_p(stream)))
-
-    def synchronize(self, stream: int = 0) -> None:
-        _check(lib().melspec_synchronize(self._h, C.c_void_p(stream)))
+    compute_ragged_device_desc = _Frontend._compute_ragged_device_desc
 
     def time_uniform_device(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int,
                             warmup: int = 3, iters: int = 20) -> float:
@@ -393,22 +497,6 @@ class HipMelSpectrogram:
         _check(lib().melspec_time_first_kernel(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips, C.c_void_p(d_out), warmup, iters, C.byref(ms)))
         return float(ms.value)
 
-    def compute_batch_host(self, flat: np.ndarray, offsets, lengths, out: np.ndarray | None = None, out_offsets=None):
-        """melspec_compute_batch_host: clip i = flat[offsets[i] : offsets[i] + lengths[i]] -> its frames at out[out_offsets[i]:]
-        (floats; None = packed).  Returns (out, total_frames).  flat / out may be pinned (HostBuffer.array)."""
-        x = flat if isinstance(flat, np.ndarray) and flat.dtype == np.float32 and flat.flags.c_contiguous else _f32(flat).reshape(-1)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        frames = np.array([self.num_frames(int(n)) for n in ln], dtype=np.uint64)
-        if out is None:
-            out = np.empty(int(frames.sum()) * self.n_mels, np.float32)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        total = C.c_uint64(0)
-        _check(lib().melspec_compute_batch_host(self._h, _fp(x.reshape(-1)), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-                                                _fp(out.reshape(-1)), None if oo is None else oo.ctypes.data_as(u64p), out.size, C.byref(total)))
-        return out, int(total.value)
-
     def compute_batch(self, clips) -> np.ndarray:
         """[n_clips, clip_len] host f32 -> [n_clips, frames, n_mels] host f32 through the chunked host pipeline."""
         x = _f32(clips)
@@ -424,28 +512,7 @@ class HipMelSpectrogram:
 
     def compute_ragged(self, clips) -> list:
         """List of 1-D host arrays of any lengths -> list of [frames_i, n_mels] arrays, one call of the host pipeline."""
-        arrs = [_f32(c).reshape(-1) for c in clips]
-        lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
-        frames = [self.num_frames(int(n)) for n in lens]
-        flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32)
-        out, _ = self.compute_batch_host(flat, offs, lens)
-        res, cur = [], 0
-        for f in frames:
-            res.append(out[cur:cur + f * self.n_mels].reshape(f, self.n_mels))
-            cur += f * self.n_mels
-        return res
-
-    def close(self) -> None:
-        if self._h is not None:
-            lib().melspec_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._compute_many(clips)
 
 
 @dataclass
@@ -481,8 +548,12 @@ class FbankConfig:
         return p
 
 
-class Fbank:
+class Fbank(_Frontend):
     """MI355X twin of Fbank (src/fbank.rs:85-247)."""
+    _P = "melspec_fbank_"
+
+    def _clip_shape(self, n_samples: int) -> tuple:
+        return self.num_frames(n_samples), self.num_mel_bins
 
     def __init__(self, config: FbankConfig | None = None, device: int = -1):
         self._h = None
@@ -492,9 +563,6 @@ class Fbank:
         _check(lib().melspec_fbank_create(C.byref(h), device, C.byref(cc)), construct=True)
         self._h = h
         self.num_mel_bins = self.config.num_mel_bins
-
-    def num_frames(self, n_samples: int) -> int:
-        return int(lib().melspec_fbank_num_frames(self._h, n_samples))
 
     def dense_filterbank(self) -> np.ndarray:
         """dense_filterbank (src/fbank.rs:244-246): the Kaldi weights [num_mel_bins, fft_size/2 + 1] the projection is built from
@@ -506,70 +574,11 @@ class Fbank:
     def uses_fast_path(self) -> bool:
         return bool(lib().melspec_fbank_uses_fast_path(self._h))
 
-    def compute_ragged_device(self, d_pcm: int, offsets, lengths, d_out: int, out_offsets=None, stream: int = 0) -> None:
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_fbank_compute_ragged_device(self._h, C.c_void_p(d_pcm), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-                                                         C.c_void_p(d_out), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
-
-    def compute_ragged_device_desc(self, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
-                                   max_total_frames: int, stream: int = 0) -> None:
-        _check(lib().melspec_fbank_compute_ragged_device_desc(self._h, C.c_void_p(d_pcm), C.c_void_p(d_offsets), C.c_void_p(d_lengths), n_clips,
-                                                              C.c_void_p(d_out), C.c_void_p(d_out_offsets) if d_out_offsets else None,
-                                                              max_total_frames, C.c_void_p(stream)))
-
-    def compute_ragged(self, clips) -> list:
-        """list of 1-D host arrays of any lengths -> list of [frames_i, num_mel_bins] arrays (Fbank::compute per clip), one launch"""
-        arrs = [_f32(c).reshape(-1) for c in clips]
-        lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
-        frames = [self.num_frames(int(n)) for n in lens]
-        total = sum(frames) * self.num_mel_bins
-        flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32)
-        din, dout = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * 4, 16))
-        try:
-            din.upload(flat)
-            self.compute_ragged_device(din.ptr, offs, lens, dout.ptr)
-            self.synchronize()
-            out = dout.download((max(total, 1),))[:total]
-        finally:
-            din.free(); dout.free()
-        res, cur = [], 0
-        for f in frames:
-            res.append(out[cur:cur + f * self.num_mel_bins].reshape(f, self.num_mel_bins))
-            cur += f * self.num_mel_bins
-        return res
-
-    def compute_batch_host(self, flat: np.ndarray, offsets, lengths, out: np.ndarray | None = None, out_offsets=None):
-        """melspec_fbank_compute_batch_host: clip i = flat[offsets[i] : + lengths[i]] -> its [frames_i, num_mel_bins] rows at
-        out[out_offsets[i]:] (floats; None = packed), whole clips through the chunked host pipeline.  Returns (out, total_frames)."""
-        x = flat if isinstance(flat, np.ndarray) and flat.dtype == np.float32 and flat.flags.c_contiguous else _f32(flat).reshape(-1)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        if out is None:
-            out = np.empty(max(sum(self.num_frames(int(n)) for n in ln) * self.num_mel_bins, 1), np.float32)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        total = C.c_uint64(0)
-        _check(lib().melspec_fbank_compute_batch_host(self._h, _fp(x.reshape(-1)), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-                                                      _fp(out.reshape(-1)), None if oo is None else oo.ctypes.data_as(u64p), out.size, C.byref(total)))
-        return out, int(total.value)
+    compute_ragged_device_desc = _Frontend._compute_ragged_device_desc
 
     def compute_many(self, clips) -> list:
         """list of 1-D host arrays -> list of [frames_i, num_mel_bins] arrays (Fbank::compute per clip) through the host pipeline"""
-        arrs = [_f32(c).reshape(-1) for c in clips]
-        lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
-        flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32)
-        out, _ = self.compute_batch_host(flat, offs, lens)
-        res, cur = [], 0
-        for n in lens:
-            f = self.num_frames(int(n))
-            res.append(out[cur:cur + f * self.num_mel_bins].reshape(f, self.num_mel_bins))
-            cur += f * self.num_mel_bins
-        return res
+        return self._compute_many(clips)
 
     def use_generic(self, on: bool = True) -> None:
         """run on the generic f64 direct-DFT kernel (the on-device cross-check of the fused kernel)"""
@@ -585,45 +594,17 @@ class Fbank:
         assert got.value == nf
         return out
 
-    def compute_uniform_device(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int,
-                               stream: int = 0) -> None:
-        _check(lib().melspec_fbank_compute_uniform_device(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
-                                                          C.c_void_p(d_out), C.c_void_p(stream)))
-
     def compute_uniform_device_split(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int, d_means: int,
                                      stream: int = 0) -> None:
         """melspec_fbank_compute_uniform_device_split (additive): the rows before CMN + the [clip][num_mel_bins] means CMN subtracts"""
         _check(lib().melspec_fbank_compute_uniform_device_split(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
                                                                 C.c_void_p(d_rows), C.c_void_p(d_means), C.c_void_p(stream)))
 
-    # -- 16-bit ends: int16 PCM in, f16 / bf16 features out (melspec_hip.h; codes PCM_* / OUT_* of this module) ------------------------
-    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
-        return bool(lib().melspec_fbank_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
-
-    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
-                                  stream: int = 0) -> None:
-        """compute_uniform_device on int16 samples and / or into f16 / bf16 features; strides count elements."""
-        _check(lib().melspec_fbank_compute_uniform_device_io(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
-                                                             C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
-
-    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
-                                 stream: int = 0) -> None:
-        """compute_ragged_device on int16 samples and / or into f16 / bf16 features; offsets and lengths count elements."""
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_fbank_compute_ragged_device_io(
-            self._h, C.c_void_p(d_pcm), int(pcm_dtype), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-            C.c_void_p(d_out), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
-
     def compute_host_io(self, samples, out_dtype=None) -> np.ndarray:
         """compute on one host clip with 16-bit ends: an np.int16 array is taken as 16-bit PCM (value = sample / 32768, exactly);
         out_dtype "f16" (or np.float16) returns np.float16 features, "bf16" the bfloat16 bit patterns as np.uint16."""
-        a = np.asarray(samples)
-        pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        x, pcm = _pcm_clip(samples)
         out = _out_code(out_dtype)
-        x = np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1)
         nf = self.num_frames(x.shape[0])
         res = np.zeros((nf, self.num_mel_bins), _OUT_NUMPY[out])
         got = C.c_size_t(0)
@@ -631,41 +612,6 @@ class Fbank:
                                                    res.size, C.byref(got)))
         assert got.value == nf
         return res
-
-    def synchronize(self, stream: int = 0) -> None:
-        _check(lib().melspec_fbank_synchronize(self._h, C.c_void_p(stream)))
-
-    def release_scratch(self) -> None:
-        """give the object's grow-only scratch back (pipeline / staging buffers, ragged plans); the next call re-allocates"""
-        _check(lib().melspec_fbank_release_scratch(self._h))
-
-    def compute_batch(self, clips) -> np.ndarray:
-        x = _f32(clips)
-        n_clips, clip_len = x.shape
-        nf = self.num_frames(clip_len)
-        out = np.zeros((n_clips, nf, self.num_mel_bins), np.float32)
-        if out.size == 0:
-            return out
-        din, dout = DeviceBuffer(x.nbytes), DeviceBuffer(out.nbytes)
-        try:
-            din.upload(x)
-            self.compute_uniform_device(din.ptr, clip_len, clip_len, n_clips, dout.ptr)
-            self.synchronize()
-            out = dout.download(out.shape)
-        finally:
-            din.free(); dout.free()
-        return out
-
-    def close(self) -> None:
-        if self._h is not None:
-            lib().melspec_fbank_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class BatchLogMelError(HipError):
@@ -696,8 +642,12 @@ class BatchLogMelConfig:
                           int(self.center), self.log_zero_guard, self.pad_to, int(self.normalize_per_feature))
 
 
-class BatchLogMelSpectrogram:
+class BatchLogMelSpectrogram(_Frontend):
     """MI355X twin of BatchLogMelSpectrogram (src/mel.rs:239-396): NeMo/Parakeet-style frontend."""
+    _P = "melspec_blm_"
+
+    def _clip_shape(self, n_samples: int) -> tuple:
+        return self.config.n_mels, self.padded_frames(n_samples)
 
     def __init__(self, config: BatchLogMelConfig | None = None, device: int = -1):
         self._h = None
@@ -719,9 +669,6 @@ class BatchLogMelSpectrogram:
     def precision(self) -> str:
         """what the next call computes in: 'f32' or 'f64'"""
         return "f32" if int(lib().melspec_blm_precision(self._h)) == 2 else "f64"
-
-    def num_frames(self, n_samples: int) -> int:
-        return int(lib().melspec_blm_num_frames(self._h, n_samples))
 
     def padded_frames(self, n_samples: int) -> int:
         return int(lib().melspec_blm_padded_frames(self._h, n_samples))
@@ -747,10 +694,6 @@ class BatchLogMelSpectrogram:
         assert r.value == self.config.n_mels and c.value == cols
         return out
 
-    def compute_uniform_device(self, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, stream: int = 0) -> None:
-        _check(lib().melspec_blm_compute_uniform_device(self._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips,
-                                                        C.c_void_p(d_out), C.c_void_p(stream)))
-
     # -- split output: un-normalised rows + per-feature mean and 1 / (std + 1e-5) (melspec_hip.h) ---------------------------------------
     def supports_split(self) -> bool:
         return bool(lib().melspec_blm_supports_split(self._h))
@@ -773,34 +716,11 @@ class BatchLogMelSpectrogram:
         assert r.value == nm and c.value == cols
         return rows, mean, inv_std
 
-    # -- 16-bit ends: int16 PCM in, f16 / bf16 features out (melspec_hip.h; codes PCM_* / OUT_* of this module) ------------------------
-    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
-        return bool(lib().melspec_blm_supports_io(self._h, int(pcm_dtype), int(out_dtype)))
-
-    def compute_uniform_device_io(self, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
-                                  stream: int = 0) -> None:
-        """compute_uniform_device on int16 samples and / or into f16 / bf16 features; strides count elements."""
-        _check(lib().melspec_blm_compute_uniform_device_io(self._h, C.c_void_p(d_pcm), int(pcm_dtype), clip_stride, clip_len, n_clips,
-                                                           C.c_void_p(d_out), int(out_dtype), C.c_void_p(stream)))
-
-    def compute_ragged_device_io(self, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, out_offsets=None,
-                                 stream: int = 0) -> None:
-        """melspec_blm_compute_ragged_device on int16 samples and / or into f16 / bf16 features; offsets and lengths count elements."""
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        _check(lib().melspec_blm_compute_ragged_device_io(
-            self._h, C.c_void_p(d_pcm), int(pcm_dtype), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-            C.c_void_p(d_out), int(out_dtype), None if oo is None else oo.ctypes.data_as(u64p), C.c_void_p(stream)))
-
     def compute_host_io(self, samples, out_dtype=None) -> np.ndarray:
         """compute on one host clip with 16-bit ends: an np.int16 array is taken as 16-bit PCM (value = sample / 32768, exactly);
         out_dtype "f16" (or np.float16) returns np.float16 features, "bf16" the bfloat16 bit patterns as np.uint16."""
-        a = np.asarray(samples)
-        pcm = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        x, pcm = _pcm_clip(samples)
         out = _out_code(out_dtype)
-        x = np.ascontiguousarray(a if pcm == PCM_S16 else _f32(a)).reshape(-1)
         cols = self.padded_frames(x.shape[0])
         res = np.zeros((self.config.n_mels, cols), _OUT_NUMPY[out])
         r, c = C.c_size_t(0), C.c_size_t(0)
@@ -809,93 +729,9 @@ class BatchLogMelSpectrogram:
         assert r.value == self.config.n_mels and c.value == cols
         return res
 
-    def synchronize(self, stream: int = 0) -> None:
-        _check(lib().melspec_blm_synchronize(self._h, C.c_void_p(stream)))
-
-    def release_scratch(self) -> None:
-        _check(lib().melspec_blm_release_scratch(self._h))
-
-    def compute_batch_host(self, flat: np.ndarray, offsets, lengths, out: np.ndarray | None = None, out_offsets=None):
-        """melspec_blm_compute_batch_host: clip i -> [n_mels, cols_i] floats at out[out_offsets[i]:] (None = packed), whole clips
-        through the chunked host pipeline.  Returns (out, total_columns)."""
-        x = flat if isinstance(flat, np.ndarray) and flat.dtype == np.float32 and flat.flags.c_contiguous else _f32(flat).reshape(-1)
-        off = np.ascontiguousarray(offsets, dtype=np.uint64)
-        ln = np.ascontiguousarray(lengths, dtype=np.uint64)
-        if out is None:
-            out = np.empty(max(sum(self.padded_frames(int(n)) for n in ln) * self.config.n_mels, 1), np.float32)
-        oo = None if out_offsets is None else np.ascontiguousarray(out_offsets, dtype=np.uint64)
-        u64p = C.POINTER(C.c_uint64)
-        total = C.c_uint64(0)
-        _check(lib().melspec_blm_compute_batch_host(self._h, _fp(x.reshape(-1)), off.ctypes.data_as(u64p), ln.ctypes.data_as(u64p), off.shape[0],
-                                                    _fp(out.reshape(-1)), None if oo is None else oo.ctypes.data_as(u64p), out.size, C.byref(total)))
-        return out, int(total.value)
-
     def compute_many(self, clips) -> list:
         """list of 1-D host arrays -> list of [n_mels, cols_i] arrays (BatchLogMelSpectrogram::compute per clip) through the host pipeline"""
-        arrs = [_f32(c).reshape(-1) for c in clips]
-        lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
-        flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32)
-        out, _ = self.compute_batch_host(flat, offs, lens)
-        nm = self.config.n_mels
-        res, cur = [], 0
-        for n in lens:
-            c = self.padded_frames(int(n))
-            res.append(out[cur:cur + c * nm].reshape(nm, c))
-            cur += c * nm
-        return res
-
-    def compute_ragged(self, clips) -> list:
-        """list of 1-D host arrays of any lengths -> list of [n_mels, cols_i] arrays (BatchLogMelSpectrogram::compute per clip), one launch"""
-        arrs = [_f32(c).reshape(-1) for c in clips]
-        lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
-        offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
-        cols = [self.padded_frames(int(n)) for n in lens]
-        nm = self.config.n_mels
-        total = sum(cols) * nm
-        flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, np.float32)
-        din, dout = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * 4, 16))
-        u64p = C.POINTER(C.c_uint64)
-        try:
-            din.upload(flat)
-            _check(lib().melspec_blm_compute_ragged_device(self._h, C.c_void_p(din.ptr), offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p), len(arrs),
-                                                           C.c_void_p(dout.ptr), None, None))
-            self.synchronize()
-            out = dout.download((max(total, 1),))[:total]
-        finally:
-            din.free(); dout.free()
-        res, cur = [], 0
-        for c in cols:
-            res.append(out[cur:cur + c * nm].reshape(nm, c))
-            cur += c * nm
-        return res
-
-    def compute_batch(self, clips) -> np.ndarray:
-        x = _f32(clips)
-        n_clips, clip_len = x.shape
-        cols = self.padded_frames(clip_len)
-        shape = (n_clips, self.config.n_mels, cols)
-        if cols == 0:
-            return np.zeros(shape, np.float32)
-        din, dout = DeviceBuffer(x.nbytes), DeviceBuffer(int(np.prod(shape)) * 4)
-        try:
-            din.upload(x)
-            self.compute_uniform_device(din.ptr, clip_len, clip_len, n_clips, dout.ptr)
-            self.synchronize()
-            return dout.download(shape)
-        finally:
-            din.free(); dout.free()
-
-    def close(self) -> None:
-        if self._h is not None:
-            lib().melspec_blm_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._compute_many(clips)
 
 
 class SparseMelFilterbank:

@@ -412,6 +412,134 @@ def test_config2_at_size_s16_f16(gpu, oracle):
     m.close()
 
 
+@pytest.mark.gpu
+def test_ctx_entries_share_their_checks(gpu):
+    """The f32 entry, the _io entry with (F32, F32) and the _io entry with (S16, F16) of each kind of batch (uniform, ragged, host) run one
+    body (ctx_uniform / ctx_ragged / ctx_host): one list of calls walked through the three doors gives one status per call.  The typed door
+    alone checks the alignment of the two device pointers -- the f32 entry and (F32, F32) never did, so no misaligned pointer is passed
+    through them: such a call would reach a kernel.  Every output is fenced; a refused or empty call leaves every sentinel in place."""
+    lib = gpu._lib.lib()
+    m = gpu.HipMelSpectrogram(400, 160, SR, 80)
+    n, nf, nm = 400 + 20 * 160, 21, 80
+    assert m.num_frames(n) == nf and m.num_frames(399) == 0
+    x16 = np.stack([s16_noise(1, n), s16_noise(2, n)])
+    u64p, f32p = C.POINTER(C.c_uint64), C.POINTER(C.c_float)
+    dev = lambda p: None if p is None else C.c_void_p(p)                    # a device address, None = NULL
+    tab = lambda a: None if a is None else a.ctypes.data_as(u64p)
+    OK = 0
+
+    class Door:
+        def __init__(self, name, typed, pcm, out):
+            self.name, self.typed, self.pcm, self.out = name, typed, pcm, out
+            self.host_in = x16 if pcm == PCM_S16 else to_f32(x16)
+            self.src = _upload(gpu, self.host_in)
+            self.fence = Fence(gpu, 2 * nf * nm, out)                       # where the refused and the empty calls point
+            self.host_out = np.full(nf * nm, SENTINEL[out], OUT_NP[out])
+
+        def uniform(self, pcm_ptr, stride, clip_len, n_clips, out_ptr):
+            if not self.typed:
+                return lib.melspec_compute_uniform_device(m._h, dev(pcm_ptr), stride, clip_len, n_clips, dev(out_ptr), None)
+            return lib.melspec_compute_uniform_device_io(m._h, dev(pcm_ptr), self.pcm, stride, clip_len, n_clips, dev(out_ptr), self.out, None)
+
+        def ragged(self, pcm_ptr, offs, lens, n_clips, out_ptr):
+            if not self.typed:
+                return lib.melspec_compute_ragged_device(m._h, dev(pcm_ptr), tab(offs), tab(lens), n_clips, dev(out_ptr), None, None)
+            return lib.melspec_compute_ragged_device_io(m._h, dev(pcm_ptr), self.pcm, tab(offs), tab(lens), n_clips, dev(out_ptr), self.out, None, None)
+
+        def host(self, samples, n_samples, out, capacity):
+            """-> (status, n_frames)"""
+            got = C.c_size_t(77)
+            if not self.typed:
+                rc = lib.melspec_compute_host(m._h, None if samples is None else samples.ctypes.data_as(f32p), n_samples,
+                                              None if out is None else out.ctypes.data_as(f32p), capacity, C.byref(got))
+            else:
+                rc = lib.melspec_compute_host_io(m._h, None if samples is None else samples.ctypes.data_as(C.c_void_p), self.pcm, n_samples,
+                                                 None if out is None else out.ctypes.data_as(C.c_void_p), self.out, capacity, C.byref(got))
+            return rc, got.value
+
+    doors = [Door("f32 entry", False, PCM_F32, OUT_F32), Door("_io (F32, F32)", True, PCM_F32, OUT_F32), Door("_io (S16, F16)", True, PCM_S16, OUT_F16)]
+    zero, one_n, one_399 = np.array([0], np.uint64), np.array([n], np.uint64), np.array([399], np.uint64)
+    calls = [
+        ("uniform: no clips, NULL pointers", lambda d: d.uniform(None, n, n, 0, None), OK),
+        ("uniform: one clip of 399 samples, NULL pointers", lambda d: d.uniform(None, 399, 399, 1, None), OK),
+        ("uniform: NULL samples", lambda d: d.uniform(None, n, n, 1, d.fence.ptr), ERR_INVALID_ARG),
+        ("uniform: NULL output", lambda d: d.uniform(d.src.ptr, n, n, 1, None), ERR_INVALID_ARG),
+        ("uniform: two clips, clip_stride = clip_len - 1", lambda d: d.uniform(d.src.ptr, n - 1, n, 2, d.fence.ptr), ERR_INVALID_ARG),
+        ("ragged: no clips, NULL pointers", lambda d: d.ragged(None, None, None, 0, None), OK),
+        ("ragged: one clip of 399 samples, NULL device pointers", lambda d: d.ragged(None, zero, one_399, 1, None), OK),
+        ("ragged: NULL samples", lambda d: d.ragged(None, zero, one_n, 1, d.fence.ptr), ERR_INVALID_ARG),
+        ("ragged: NULL output", lambda d: d.ragged(d.src.ptr, zero, one_n, 1, None), ERR_INVALID_ARG),
+        ("ragged: NULL offsets", lambda d: d.ragged(d.src.ptr, None, one_n, 1, d.fence.ptr), ERR_INVALID_ARG),
+        ("ragged: NULL lengths", lambda d: d.ragged(d.src.ptr, zero, None, 1, d.fence.ptr), ERR_INVALID_ARG),
+        ("host: 399 samples, NULL pointers", lambda d: d.host(None, 399, None, 0), (OK, 0)),
+        ("host: NULL samples", lambda d: d.host(None, n, d.host_out, d.host_out.size), (ERR_INVALID_ARG, 0)),
+        ("host: NULL output", lambda d: d.host(d.host_in[0], n, None, nf * nm), (ERR_INVALID_ARG, 0)),
+        ("host: capacity one element short", lambda d: d.host(d.host_in[0], n, d.host_out, nf * nm - 1), (ERR_CAPACITY, 0)),
+    ]
+    for what, call, want in calls:
+        got = [call(d) for d in doors]
+        assert got == [want] * 3, f"{what}: {dict(zip((d.name for d in doors), got))}, expected {want} from every door"
+    typed = doors[2]
+    for what, got in (("uniform: samples at an odd byte address", typed.uniform(typed.src.ptr + 1, n, n, 1, typed.fence.ptr)),
+                      ("uniform: rows at an odd byte address", typed.uniform(typed.src.ptr, n, n, 1, typed.fence.ptr + 1)),
+                      ("ragged: samples at an odd byte address", typed.ragged(typed.src.ptr + 1, zero, one_n, 1, typed.fence.ptr)),
+                      ("ragged: rows at an odd byte address", typed.ragged(typed.src.ptr, zero, one_n, 1, typed.fence.ptr + 1))):
+        assert got == ERR_INVALID_ARG, f"{what} through {typed.name}: {got}"
+    m.synchronize()
+    for d in doors:
+        assert np.all(d.host_out == SENTINEL[d.out]), f"{d.name}: a refused host call wrote into the output"
+        assert np.all(d.fence.bits() == d.fence.s), f"{d.name}: a refused or empty call wrote into the output"
+    # two clips with clip_stride = 0: every clip is the first one -- accepted by every door, and both outputs are clip 0's rows
+    rows = []
+    for d in doors:
+        f = Fence(gpu, 2 * nf * nm, d.out)
+        assert d.uniform(d.src.ptr, 0, n, 2, f.ptr) == OK, d.name
+        m.synchronize()
+        bits = f.bits().reshape(2, nf * nm)
+        assert not np.any(bits == f.s) and np.array_equal(bits[0], bits[1]), d.name
+        rows.append(bits)
+        d.src.free()
+    assert np.array_equal(rows[0], rows[1])
+    m.close()
+
+
+@pytest.mark.gpu
+def test_f32_through_io_is_the_plain_call_ragged_and_host(gpu):
+    """(F32, F32) through melspec_compute_ragged_device_io / melspec_compute_host_io gives the bits of melspec_compute_ragged_device /
+    melspec_compute_host: three clips of 399, 400 and 400 + 7 * 160 + 1 samples (no frame, one frame, a tail of one sample behind the last
+    frame), packed and at output offsets that leave gaps; the host pair on the third clip.  (test_refusals compares the uniform pair.)"""
+    lib = gpu._lib.lib()
+    m = gpu.HipMelSpectrogram(400, 160, SR, 80)
+    lens = [399, 400, 400 + 7 * 160 + 1]
+    frames = [m.num_frames(k) for k in lens]
+    assert frames == [0, 1, 8]
+    clips = [to_f32(s16_noise(20 + c, k)) for c, k in enumerate(lens)]
+    offs = np.array([0, 399, 799], np.uint64)
+    d = _upload(gpu, np.concatenate(clips))
+    for oo in (None, np.array([3, 8, 8 + 80 + 5], np.uint64)):
+        total = 9 * 80 if oo is None else int(oo[2]) + 8 * 80 + 7
+        got = []
+        for plain in (True, False):
+            f = Fence(gpu, total, OUT_F32)
+            if plain:
+                m.compute_ragged_device(d.ptr, offs, lens, f.ptr, oo)
+            else:
+                m.compute_ragged_device_io(d.ptr, PCM_F32, offs, lens, f.ptr, OUT_F32, oo)
+            m.synchronize()
+            got.append(f.bits())
+            assert int(np.sum(got[-1] != f.s)) == 9 * 80, "nine frames are written, and nothing between them"
+        assert np.array_equal(got[0], got[1]), "ragged (F32, F32) through the _io call is the plain call"
+    d.free()
+    x = clips[2]
+    a = m.compute_mel_spectrogram(x)                                         # melspec_compute_host
+    b = np.full((8, 80), SENTINEL[OUT_F32], np.uint32)
+    n_frames = C.c_size_t(0)
+    assert lib.melspec_compute_host_io(m._h, x.ctypes.data_as(C.c_void_p), PCM_F32, x.size, b.ctypes.data_as(C.c_void_p), OUT_F32, b.size, C.byref(n_frames)) == 0
+    assert n_frames.value == 8 and a.shape == (8, 80)
+    assert np.array_equal(a.view(np.uint32), b), "host (F32, F32) through the _io call is the plain call"
+    m.close()
+
+
 # ---- CPU ---------------------------------------------------------------------------------------------------------------------------
 
 def test_io_symbols_everywhere():

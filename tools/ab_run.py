@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of library variants (boxes differ by several percent, so variants are interleaved and repeated):
-tools/ab_run.py [--case cfg2|cfg4|f64|fbank|fbank_split|fbank_1clip|nemo|nemo_1clip|w512|mm] name1 name2 ...   (libraries mel_spec_amd/ab/lib_<name>.so).
+tools/ab_run.py [--case cfg2|cfg4|f64|fbank|fbank_split|fbank_1clip|nemo|nemo_1clip|ctx_1clip|ctx_1clip_io|w512|mm] name1 name2 ...   (libraries mel_spec_amd/ab/lib_<name>.so).
 Each measurement runs in its own process (MELSPEC_LIB), event-timed, after a spin-up; prints per variant min / median over reps."""
 import os, subprocess, sys, statistics
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -86,6 +86,13 @@ elif case in ("fbank_1clip", "nemo_1clip"):          # launch-bound: one 1 s cli
     obj = M.Fbank() if case == "fbank_1clip" else M.BatchLogMelSpectrogram(M.BatchLogMelConfig(n_mels=80))
     out = M.DeviceBuffer(128 * 128 * 4)
     ms = wall(lambda: obj.compute_uniform_device(pcm.ptr, 16000, 16000, 1, out.ptr), obj.synchronize, 4000)
+elif case in ("ctx_1clip", "ctx_1clip_io"):          # the same through the 80-mel log-mel context: the f32 entry, and the typed entry with (S16, F16) (the
+    m = M.HipMelSpectrogram(400, 160, 16000.0, 80)     # buffer's bytes read as int16: any samples do for the host time of a call)
+    out = M.DeviceBuffer(128 * 128 * 4)
+    if case == "ctx_1clip":
+        ms = wall(lambda: m.compute_uniform_device(pcm.ptr, 16000, 16000, 1, out.ptr), m.synchronize, 4000)
+    else:
+        ms = wall(lambda: m.compute_uniform_device_io(pcm.ptr, M.hip.PCM_S16, 16000, 16000, 1, out.ptr, M.hip.OUT_F16), m.synchronize, 4000)
 print("MS", ms)
 '''
 args = sys.argv[1:]
@@ -105,8 +112,7 @@ for r in range(reps):
         p = subprocess.run([sys.executable, "-c", WORKER, ROOT, case], env=env, capture_output=True, text=True, timeout=600)
         ms = [float(l.split()[1]) for l in p.stdout.splitlines() if l.startswith("MS")]
         if not ms:
-            print(n, "FAILED", p.stderr[-600:])
-            continue
+            sys.exit(f"{n} FAILED (nothing more is started on a device a worker may have faulted) {p.stderr[-600:]}")
         res[n].append(ms[0])
 base = statistics.median(res[args[0]]) if res[args[0]] else 0
 for n in args:
