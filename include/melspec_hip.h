@@ -646,6 +646,67 @@ int melspec_fbank_stream_push_device(void *st, const uint32_t *ids, const void *
 int melspec_fbank_stream_stats_host(void *st, const uint32_t *ids, uint32_t n, float *means, uint64_t *counts);
 int melspec_fbank_stream_stats_device(void *st, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream);
 
+/* ---- streaming NeMo / Parakeet log-mel: BatchLogMelSpectrogram::compute (src/mel.rs) fed chunk by chunk ---- */
+/* A bank of n_streams independent streams over one melspec_blm (its geometry, tables and kernels).  For each stream, after any sequence
+ * of pushes whose chunks concatenate to x, followed by one finish, the columns emitted so far, concatenated in time, are exactly the
+ * columns melspec_blm_compute_host returns for x from a context with the same config, normalize_per_feature = 0 and the same precision
+ * mode (read at each push from melspec_blm_precision); pad_to is ignored.  Bit for bit, however x was cut into chunks.
+ *   center = 1: frame k reads samples [k * hop - 200, k * hop + 200); a push emits it as soon as the stream holds k * hop + 200 samples,
+ *     so every tap is a real sample.  finish emits the remaining frames up to k = total / hop with the reference's zero padding on the
+ *     right (at most two per stream at the usual hops; in general the frames that overlap the last 200 samples) -- and nothing for a
+ *     stream that never received a sample, as the reference returns no column for an empty input.
+ *   center = 0: frame k exists once the stream holds k * hop + 512 samples (num_frames); finish emits nothing.
+ * After finish the stream is ended: a push or a second finish returns MELSPEC_ERR_INVALID_ARG and leaves the bank as it was, the
+ * statistics stay readable, reset starts the stream afresh.  Pre-emphasis follows the reference across chunk borders: sample 0 of a
+ * stream is never pre-emphasised, every other sample uses its true predecessor (a NaN or an infinity there reaches the rows as in the
+ * batch call); padding is zero after pre-emphasis.
+ * A push always emits UN-NORMALISED rows, whatever the context's normalize_per_feature is (the contract of
+ * melspec_blm_compute_uniform_device_split carried over time): entry i gets feature-major [n_mels][frames_i] f32.  Per stream and mel
+ * row the bank keeps a running (count, mean, M2) in f64, updated one column at a time in time order (Welford: d = x - mean;
+ * mean += d / count; M2 += d * (x - mean); every operation rounded once) -- a left fold over the stream's columns, so a function of the
+ * stream's samples alone.  melspec_blm_stream_stats_* return mean[m] (f32), inv_std[m] = 1 / (sqrt(M2 / max(count - 1, 1)) + 1e-5) --
+ * the split output's definition -- and the column count; count == 0 gives mean 0 and inv_std 1e5.  At end of stream (rows - mean) *
+ * inv_std is the normalised call's output to within the error of its f32 folds; before that, online cumulative normalisation.
+ * Per stream the device keeps the samples from the predecessor of the next frame's first tap on: fewer than 401 (center = 0: 457).
+ * Rows are f32 only; chunks are MELSPEC_PCM_F32 or MELSPEC_PCM_S16 (int16 * 2^-15, exactly, converted where the chunk is copied into the
+ * f32 state).
+ * The handle is opaque and crosses the ABI as void *.  The context must outlive the bank; one bank per host thread, like the context.
+ * Needs the fused geometry (n_fft = 512, win_length = 400, a bank the fused kernels hold): otherwise MELSPEC_ERR_UNSUPPORTED at create
+ * with melspec_last_error naming the geometry.  n_streams == 0 or max_chunk == 0, a NULL handle (no device is touched), an id out of
+ * range or twice in one call: MELSPEC_ERR_INVALID_ARG; a chunk longer than max_chunk: MELSPEC_ERR_CAPACITY.  A call that fails leaves the
+ * bank, its state and its statistics as they were.
+ * Measured (profiles/blm_stream.txt; MI355X, 1024 live streams, ms per melspec_blm_stream_push_device at 10 ms / 100 ms / 1 s chunks):
+ * f64 0.0545 / 0.0605 / 0.1484, MELSPEC_PRECISION_F32 0.0579 / 0.0592 / 0.1314.  In the same run the Kaldi bank's push took 0.0516 /
+ * 0.0593 / 0.1317 ms and melspec_blm_compute_ragged_device on the history ++ chunk batch (which leaves the history, the batch and the
+ * statistics to its caller) 0.0370 / 0.0433 / 0.0958 ms (F32: 0.0384 / 0.0406 / 0.0795): the bank is 1.40 - 1.65 x SLOWER than that call. */
+int melspec_blm_stream_create(void **out, melspec_blm *b, uint32_t n_streams, uint32_t max_chunk);
+void melspec_blm_stream_destroy(void *st);
+/* no history, no frames, not ended, zero statistics for the listed streams; ids == NULL -> all.  A bad id: nothing is reset. */
+int melspec_blm_stream_reset(void *st, const uint32_t *ids, uint32_t n);
+/* columns a push of n_new samples to stream id would emit now / a finish of it would (0 for an ended stream) */
+size_t melspec_blm_stream_frames_after(const void *st, uint32_t id, uint32_t n_new);
+size_t melspec_blm_stream_finish_frames(const void *st, uint32_t id);
+/* Host chunks: samples holds the n chunks back to back (lens[i] elements of pcm_dtype for stream ids[i]); out receives the emitted
+ * rows, [n_mels][frames_out[i]] f32 per entry, back to back in entry order.  Synchronous. */
+int melspec_blm_stream_push_host(void *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                 float *out, size_t out_capacity_floats, uint32_t *frames_out);
+/* Device producers: d_chunks != NULL: chunk i is d_chunks[h_src_offsets[i] .. + lens[i]) in elements of pcm_dtype (h_src_offsets == NULL:
+ * back to back), copied into the bank on `stream`; d_chunks == NULL: the chunks are already at melspec_blm_stream_input_ptr(st, id)
+ * (fixed per stream, 16-byte aligned, room for max_chunk samples), in f32.  Entry i's rows go to d_out + h_out_offsets[i] floats (NULL:
+ * back to back).  The launches have completed on return, as for melspec_stream_push_device. */
+float *melspec_blm_stream_input_ptr(void *st, uint32_t id);
+int melspec_blm_stream_push_device(void *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                   const uint32_t *lens, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out,
+                                   void *stream);
+/* end of the listed streams: the frames that read past the stream's end, laid out like a push's */
+int melspec_blm_stream_finish_host(void *st, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats, uint32_t *frames_out);
+int melspec_blm_stream_finish_device(void *st, const uint32_t *ids, uint32_t n, float *d_out, const uint64_t *h_out_offsets,
+                                     uint32_t *frames_out, void *stream);
+/* mean, inv_std: [n][n_mels] f32 of the listed streams, counts: [n] columns emitted so far (may be NULL) */
+int melspec_blm_stream_stats_host(void *st, const uint32_t *ids, uint32_t n, float *mean, float *inv_std, uint64_t *counts);
+int melspec_blm_stream_stats_device(void *st, const uint32_t *ids, uint32_t n, float *d_mean, float *d_inv_std, uint64_t *h_counts,
+                                    void *stream);
+
 /* ---- 8-bit quantisation + TGA container: replaces src/quant.rs ------------------------ */
 /* The reference's wire/disk format right after the mel path: a mel-major interleaved image
  * ([n_mels][width] f32, what melspec_compute_uniform_device_interleaved(.., major_column_order = 0, ..)

@@ -358,8 +358,77 @@ public:
     void release_scratch() { detail::check(melspec_blm_release_scratch(b_), false); }
 
 private:
+    friend class BlmStreamBank;
     melspec_blm *b_ = nullptr;
     std::size_t n_mels_ = 0;
+};
+
+// BatchLogMelSpectrogram::compute fed chunk by chunk (melspec_blm_stream_*): after pushes whose chunks concatenate to x and one finish a
+// stream has emitted exactly the columns of compute(x) with normalize_per_feature off, un-normalised whatever the object's setting;
+// stats() gives the running per-feature mean and 1 / (std + 1e-5) of those columns.  The frontend must outlive the bank.
+class BlmStreamBank {
+public:
+    BlmStreamBank(BatchLogMelSpectrogram &blm, std::size_t n_streams, std::size_t max_chunk) : n_mels_(blm.n_mels_) {
+        detail::check(melspec_blm_stream_create(&st_, blm.b_, static_cast<std::uint32_t>(n_streams), static_cast<std::uint32_t>(max_chunk)), true);
+    }
+    ~BlmStreamBank() { melspec_blm_stream_destroy(st_); }
+    BlmStreamBank(const BlmStreamBank &) = delete;
+    BlmStreamBank &operator=(const BlmStreamBank &) = delete;
+
+    void reset() { detail::check(melspec_blm_stream_reset(st_, nullptr, 0), false); }
+    void reset(const std::vector<std::uint32_t> &ids) { detail::check(melspec_blm_stream_reset(st_, ids.data(), static_cast<std::uint32_t>(ids.size())), false); }
+    std::size_t frames_after(std::uint32_t id, std::size_t n_new) const { return melspec_blm_stream_frames_after(st_, id, static_cast<std::uint32_t>(n_new)); }
+    std::size_t finish_frames(std::uint32_t id) const { return melspec_blm_stream_finish_frames(st_, id); }
+    // one chunk for one stream: the columns it completes, (n_mels, frames) row-major
+    Array2f push(std::uint32_t id, const std::vector<float> &chunk) { return push_typed(id, chunk.data(), MELSPEC_PCM_F32, chunk.size()); }
+    Array2f push(std::uint32_t id, const std::vector<std::int16_t> &chunk) { return push_typed(id, chunk.data(), MELSPEC_PCM_S16, chunk.size()); }
+    // end of the stream: the zero-padded columns; the stream takes no push until reset
+    Array2f finish(std::uint32_t id) {
+        Array2f a;
+        a.rows = n_mels_;
+        a.data.assign(finish_frames(id) * n_mels_, 0.0f);
+        std::uint32_t got = 0;
+        detail::check(melspec_blm_stream_finish_host(st_, &id, 1, a.data.data(), a.data.size(), &got), false);
+        a.cols = got;
+        return a;
+    }
+    float *input_ptr(std::uint32_t id) { return melspec_blm_stream_input_ptr(st_, id); }
+    void push_device(const std::vector<std::uint32_t> &ids, const void *d_chunks, int pcm_dtype, const std::uint64_t *src_offsets, const std::vector<std::uint32_t> &lens,
+                     float *d_out, const std::uint64_t *out_offsets, std::uint32_t *frames_out, void *stream = nullptr) {
+        detail::check(melspec_blm_stream_push_device(st_, ids.data(), d_chunks, pcm_dtype, src_offsets, lens.data(), static_cast<std::uint32_t>(ids.size()), d_out,
+                                                     out_offsets, frames_out, stream), false);
+    }
+    void finish_device(const std::vector<std::uint32_t> &ids, float *d_out, const std::uint64_t *out_offsets, std::uint32_t *frames_out, void *stream = nullptr) {
+        detail::check(melspec_blm_stream_finish_device(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_out, out_offsets, frames_out, stream), false);
+    }
+    struct Stats {
+        std::vector<float> mean, inv_std;  // (n_mels)
+        std::uint64_t count = 0;           // columns emitted so far
+    };
+    Stats stats(std::uint32_t id) {
+        Stats s;
+        s.mean.assign(n_mels_, 0.0f);
+        s.inv_std.assign(n_mels_, 0.0f);
+        detail::check(melspec_blm_stream_stats_host(st_, &id, 1, s.mean.data(), s.inv_std.data(), &s.count), false);
+        return s;
+    }
+    void stats_device(const std::vector<std::uint32_t> &ids, float *d_mean, float *d_inv_std, std::uint64_t *counts, void *stream = nullptr) {
+        detail::check(melspec_blm_stream_stats_device(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_mean, d_inv_std, counts, stream), false);
+    }
+
+private:
+    Array2f push_typed(std::uint32_t id, const void *samples, int pcm_dtype, std::size_t n) {
+        Array2f a;
+        const std::uint32_t len = static_cast<std::uint32_t>(n);
+        a.rows = n_mels_;
+        a.data.assign(frames_after(id, n) * n_mels_, 0.0f);
+        std::uint32_t got = 0;
+        detail::check(melspec_blm_stream_push_host(st_, &id, samples, pcm_dtype, &len, 1, a.data.data(), a.data.size(), &got), false);
+        a.cols = got;
+        return a;
+    }
+    void *st_ = nullptr;
+    std::size_t n_mels_;
 };
 
 // src/quant.rs: quantize / dequantize / tga_8bit / parse_tga_8bit, same names and return shapes

@@ -188,6 +188,18 @@ SIGNATURES = {
     "melspec_fbank_stream_push_device": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u64p, _u32p, C.c_uint32, _vp, _u64p, _u32p, _vp]),
     "melspec_fbank_stream_stats_host": (C.c_int, [_vp, _u32p, C.c_uint32, _f32p, _u64p]),
     "melspec_fbank_stream_stats_device": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, _u64p, _vp]),
+    "melspec_blm_stream_create": (C.c_int, [C.POINTER(_vp), _vp, C.c_uint32, C.c_uint32]),
+    "melspec_blm_stream_destroy": (None, [_vp]),
+    "melspec_blm_stream_reset": (C.c_int, [_vp, _u32p, C.c_uint32]),
+    "melspec_blm_stream_frames_after": (C.c_size_t, [_vp, C.c_uint32, C.c_uint32]),
+    "melspec_blm_stream_finish_frames": (C.c_size_t, [_vp, C.c_uint32]),
+    "melspec_blm_stream_push_host": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u32p, C.c_uint32, _f32p, C.c_size_t, _u32p]),
+    "melspec_blm_stream_input_ptr": (_vp, [_vp, C.c_uint32]),
+    "melspec_blm_stream_push_device": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u64p, _u32p, C.c_uint32, _vp, _u64p, _u32p, _vp]),
+    "melspec_blm_stream_finish_host": (C.c_int, [_vp, _u32p, C.c_uint32, _f32p, C.c_size_t, _u32p]),
+    "melspec_blm_stream_finish_device": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, _u64p, _u32p, _vp]),
+    "melspec_blm_stream_stats_host": (C.c_int, [_vp, _u32p, C.c_uint32, _f32p, _f32p, _u64p]),
+    "melspec_blm_stream_stats_device": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, _vp, _u64p, _vp]),
     "melspec_stream_enable_vad":(C.c_int, [_vp, C.POINTER(VadSettingsC)]),
     "melspec_stream_vad_frames": (C.c_uint64, [_vp, C.c_uint32]),
     "melspec_stream_push_host_vad": (C.c_int, [_vp, _u32p, _f32p, _u32p, C.c_uint32, _f32p, C.c_size_t, _u32p, _vp, C.c_size_t]),

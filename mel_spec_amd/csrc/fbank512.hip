@@ -6,7 +6,9 @@
 #include "fbank512_kaldi_io_kernels.hpp"
 #include "fbank512_stats_kernels.hpp"
 #include "fbank512_stream_kernels.hpp"
+#include "fbank512_nemo_stream_kernels.hpp"
 #include "blm_stats_plan.hpp"
+#include "blm_stream_plan.hpp"
 #include "fbank_stream_plan.hpp"
 #include "stream_bank.hpp"
 
@@ -29,6 +31,10 @@ MS_K512_STATS(MS_STATS_EXTERN)
 #define MS_STREAM_EXTERN(name, T, W, N, L, R) extern template __global__ void fbank512_stream_kernel<T, W, N, L, R>(const FbankStreamParams);
 MS_K512_STREAM(MS_STREAM_EXTERN)
 #undef MS_STREAM_EXTERN
+// emitted by fbank512_nemo_stream.hip: the NeMo frontend's stream bank (the batch kernels with a window origin per clip)
+#define MS_NEMO_STREAM_EXTERN(name, T, W, N, L) extern template __global__ void fbank512_nemo_stream_kernel<T, W, N, L>(const FbankNemoStreamParams);
+MS_K512_NEMO_STREAM(MS_NEMO_STREAM_EXTERN)
+#undef MS_NEMO_STREAM_EXTERN
 }  // namespace melspec
 
 namespace {
@@ -70,6 +76,8 @@ inline auto kernel512(K512 k, const FbankClipParams &) { return is_clip(k) ? kCl
 inline auto kernel512(K512 k, const FbankStatsParams &) { return is_stats(k) ? kStatsKernels[idx(k) - idx(K512::kStats128)] : nullptr; }
 inline auto kernel512(K512 k, const W512AutoParams &) { return is_auto(k) ? kAutoKernels[idx(k) - idx(K512::kAuto80Vote)] : nullptr; }
 inline auto kernel512(K512 k, const FbankStreamParams &) { return is_stream(k) ? kStreamKernels[idx(k) - idx(K512::kStream80)] : nullptr; }
+// the NeMo stream bank's kernels have a table of their own, keyed by the kernel a batch of the object runs on: same launch shape, same LDS
+inline auto kernel512(K512 k, const FbankNemoStreamParams &) { return nemo_stream_kernel(k); }
 inline const BatchDesc &batch_of(const FbankFastParams &p) { return p.b; }
 template <class P> const BatchDesc &batch_of(const P &q) { return q.f.b; }
 
@@ -97,13 +105,15 @@ const char *attr_name(K512 k) {
          : is_io(k) ? "hipFuncSetAttribute(fbank512_nemo_io_kernel)" : info_of(k).f32 ? "hipFuncSetAttribute(fbank512_wave_kernel<float>, 12 waves)"
                     : "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)";
 }
+template <class P> const char *attr_name(K512 k, const P &) { return attr_name(k); }
+const char *attr_name(K512, const FbankNemoStreamParams &) { return "hipFuncSetAttribute(fbank512_nemo_stream_kernel)"; }
 // one launch of a route with the parameters of its kernel's group; z: the object's LDS sizes
 template <class P>
 int launch512(const Launch512 &l, const P &p, const Lds512Sizes &z, int cus, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done[idx(K512::kEnd)];          // one bit per device: function attributes are per device
+    static std::atomic<uint64_t> attr_done[idx(K512::kEnd)];          // one bit per device: function attributes are per device (one array per parameter struct)
     const auto kernel = kernel512(l.kernel, p);
     if (!kernel) return fail(MELSPEC_ERR_INTERNAL, "launch512: the object has no kernel for this batch");
-    if (int rc = allow_big_lds_once(attr_done[idx(l.kernel)], attr_name(l.kernel), kernel)) return rc;
+    if (int rc = allow_big_lds_once(attr_done[idx(l.kernel)], attr_name(l.kernel, p), kernel)) return rc;
     hipLaunchKernelGGL(kernel, dim3(grid512(l, batch_of(p).n_units, cus)), dim3(l.waves * 64), lds512(l.lds, z), s, p);
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
@@ -1483,6 +1493,268 @@ int melspec_fbank_stream_stats_host(void *h, const uint32_t *ids, uint32_t n, fl
     if (int rc = st->means.ensure(bytes + 16)) return rc;
     if (int rc = melspec_fbank_stream_stats_device(h, ids, n, static_cast<float *>(st->means.p), counts, st->fb->stream)) return rc;
     HIP_TRY(hipMemcpy(means, st->means.p, bytes, hipMemcpyDeviceToHost));
+    return MELSPEC_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------
+// NeMo / Parakeet frontend: the stream bank (melspec_blm_stream_*): see include/melspec_hip.h.  Bookkeeping in blm_stream_plan.hpp, kernels in
+// fbank512_nemo_stream_kernels.hpp; everything a bank of live streams is besides its planner and its frame stage in stream_bank.hpp.
+// ------------------------------------------------------------------------------------
+namespace {
+constexpr uint32_t kBlmStreamMagic = 0x4d4c424eu;        // the handle crosses the ABI as void *: every call checks what it was given
+
+struct BlmStreamBank {
+    uint32_t magic = kBlmStreamMagic;
+    melspec_blm *b = nullptr;            // geometry, tables, kernels, precision mode; not owned
+    BlmStreamGeom geom{};
+    BlmStreamBook book;                  // total / emitted / ended per stream (host side of the state)
+    BankCore core;
+    DevBuf moments, counts;              // [n_streams][2][n_mels] f64 (mean, M2), [n_streams] u64
+    DevBuf stats;                        // the host stats call's buffer
+};
+
+BlmStreamBank *bls_of(void *h) {
+    BlmStreamBank *st = static_cast<BlmStreamBank *>(h);
+    return st && st->magic == kBlmStreamMagic ? st : nullptr;
+}
+const BlmStreamBank *bls_of(const void *h) { return bls_of(const_cast<void *>(h)); }
+
+// the contexts a bank can stand on: the fused 512-point path (every kernel of MS_K512_NEMO_STREAM)
+int bls_supported(const melspec_blm *b) {
+    if (b->fast) return MELSPEC_OK;
+    g_last_error = "the log-mel stream bank runs on the fused kernels (n_fft = 512, win_length = 400); this context is n_fft = " + std::to_string(b->cfg.n_fft) +
+                   ", win_length = " + std::to_string(b->cfg.win_length) + ", hop_length = " + std::to_string(b->cfg.hop_length) + ", n_mels = " + std::to_string(b->cfg.n_mels) +
+                   (b->cfg.n_fft == 512 && b->cfg.win_length == 400 ? " (a filterbank the fused kernels do not hold)" : "");
+    return MELSPEC_ERR_UNSUPPORTED;
+}
+
+// the frame stage behind the core's scatter: the columns, then the running statistics; the entries' tail is the clips' sample counts
+// and, behind them, their window origins
+int bls_run(BlmStreamBank *st, const BlmStreamPlan &pl, uint32_t n, const PushArgs &a) {
+    melspec_blm *b = st->b;
+    const int nm = b->cfg.n_mels;
+    const size_t len_bytes = static_cast<size_t>(n) * sizeof(uint64_t);
+    std::vector<unsigned char> tail(len_bytes + static_cast<size_t>(n) * sizeof(int32_t));
+    std::memcpy(tail.data(), pl.len.data(), len_bytes);
+    std::memcpy(tail.data() + len_bytes, pl.org0.data(), static_cast<size_t>(n) * sizeof(int32_t));
+    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data(), tail.size(), [&](const StreamEntry *d_e, const void *d_tail) {
+        BatchPlan bp;
+        RaggedSlot *pslot = nullptr;
+        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), static_cast<float *>(a.d_out), pl.off.data(), pl.frames,
+                             a.h_out_off ? a.h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
+        if (!rc) {
+            // the ragged batch of blm_ragged over the state: feature-major rows as wide as the entry's frames, every one of them valid
+            FbankNemoStreamParams q{};
+            q.f = blm_fast_params(b, bp.desc);
+            q.f.b.mel_major = 1;
+            q.f.b.sync_rounds = kNemoSync;
+            q.f.d_len = static_cast<const uint64_t *>(d_tail);
+            q.f.d_valid = bp.desc.d_frames;
+            q.d_org0 = reinterpret_cast<const int *>(static_cast<const char *>(d_tail) + len_bytes);
+            const Route512 r = route512(blm_shape(b), Batch512::kLayout);      // the kernel a batch of the context runs on now; its stream form
+            apply_route(r, q.f, b->f32);
+            rc = launch512(r.run, q, blm_lds(b), b->dev.cus, a.stream);
+        }
+        plan_ragged_done(pslot, a.stream);
+        if (rc) return rc;
+        BlmStreamStatsParams sp{};
+        sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.moments = static_cast<double *>(st->moments.p);
+        sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
+        hipLaunchKernelGGL(blm_stream_stats_kernel, dim3(n), dim3(kBlmStreamStatsThreads), 0, a.stream, sp);
+        HIP_TRY(hipGetLastError());
+        return static_cast<int>(MELSPEC_OK);
+    });
+}
+
+// a push or a finish behind its argument checks: plan, run(plan) -- its launches have completed when it returns --, then the book moves on
+template <class Run>
+int bls_push(BlmStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool finish, uint32_t *frames_out, Run run) {
+    BlmStreamPlan pl;
+    const char *err = nullptr;
+    int rc = plan_status(blm_stream_plan_push(st->geom, st->book, ids, lens, n, finish, pl, &err), err);
+    if (rc || (rc = run(pl))) return rc;
+    blm_stream_commit_push(st->geom, st->book, ids, lens, n, finish);
+    for (uint32_t i = 0; frames_out && i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
+    return MELSPEC_OK;
+}
+
+// what every push checks first: the handle, the dtype code, the context
+int bls_push_args(BlmStreamBank *st, int pcm_dtype) {
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
+    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    return bls_supported(st->b);
+}
+
+int bls_push_host(BlmStreamBank *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, bool finish, float *out,
+                  size_t out_capacity_floats, uint32_t *frames_out) {
+    return bls_push(st, ids, lens, n, finish, frames_out, [&](const BlmStreamPlan &pl) {
+        const HostPush hp{samples, out, out_capacity_floats, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), sizeof(float)};
+        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
+            return bls_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s});
+        });
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int melspec_blm_stream_create(void **out, melspec_blm *b, uint32_t n_streams, uint32_t max_chunk) {
+    if (!out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
+    *out = nullptr;
+    if (n_streams == 0 || max_chunk == 0) return fail(MELSPEC_ERR_INVALID_ARG, "n_streams and max_chunk must be > 0");
+    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
+    if (int rc = bls_supported(b)) return rc;
+    BlmStreamBank *st = new (std::nothrow) BlmStreamBank();
+    if (!st) return fail(MELSPEC_ERR_INTERNAL, "out of host memory");
+    st->b = b;
+    st->geom = blm_stream_geometry(static_cast<uint32_t>(b->cfg.hop_length), b->cfg.center != 0, static_cast<uint32_t>(b->cfg.n_mels), n_streams, max_chunk);
+    st->book.reset(n_streams);
+    auto bail = [&](int code) { melspec_blm_stream_destroy(st); return code; };
+    const size_t mom_bytes = static_cast<size_t>(n_streams) * 2 * st->geom.n_mels * sizeof(double), count_bytes = static_cast<size_t>(n_streams) * sizeof(unsigned long long);
+    int rc;
+    if ((rc = core_create(st->core, b->dev.device, b->stream, n_streams, st->geom.stride, st->geom.in_off)) || (rc = st->moments.ensure(mom_bytes)) ||
+        (rc = st->counts.ensure(count_bytes)))
+        return bail(rc);
+    if (hipMemset(st->moments.p, 0, mom_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess) return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
+    *out = st;
+    return MELSPEC_OK;
+}
+
+void melspec_blm_stream_destroy(void *h) {
+    BlmStreamBank *st = bls_of(h);
+    if (!st) return;
+    core_destroy(st->core);
+    st->moments.release(); st->counts.release(); st->stats.release();
+    st->magic = 0;
+    delete st;
+}
+
+int melspec_blm_stream_reset(void *h, const uint32_t *ids, uint32_t n) {
+    BlmStreamBank *st = bls_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
+    if (int rc = core_reset_slots(st->core, ids, n)) return rc;      // a bad id: nothing has been touched
+    const BlmStreamGeom &g = st->geom;
+    hipStream_t s = st->core.stream;
+    const size_t row = static_cast<size_t>(g.n_mels) * 2 * sizeof(double);
+    if (!ids) {
+        HIP_TRY(hipMemsetAsync(st->moments.p, 0, g.n_streams * row, s));
+        HIP_TRY(hipMemsetAsync(st->counts.p, 0, static_cast<size_t>(g.n_streams) * sizeof(unsigned long long), s));
+        st->book.reset(g.n_streams);
+    }
+    for (uint32_t i = 0; ids && i < n; ++i) {
+        HIP_TRY(hipMemsetAsync(static_cast<char *>(st->moments.p) + ids[i] * row, 0, row, s));
+        HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
+        st->book.reset_one(ids[i]);
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    return MELSPEC_OK;
+}
+
+size_t melspec_blm_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) {
+    const BlmStreamBank *st = bls_of(h);
+    if (!st || id >= st->geom.n_streams) return 0;
+    return blm_stream_frames_after(st->geom, st->book, id, n_new);
+}
+
+size_t melspec_blm_stream_finish_frames(const void *h, uint32_t id) {
+    const BlmStreamBank *st = bls_of(h);
+    if (!st || id >= st->geom.n_streams) return 0;
+    return blm_stream_finish_frames(st->geom, st->book, id);
+}
+
+float *melspec_blm_stream_input_ptr(void *h, uint32_t id) {
+    BlmStreamBank *st = bls_of(h);
+    return st ? core_input_ptr(st->core, id) : nullptr;
+}
+
+int melspec_blm_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
+                                 size_t out_capacity_floats, uint32_t *frames_out) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, pcm_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    return bls_push_host(st, ids, samples, pcm_dtype, lens, n, false, out, out_capacity_floats, frames_out);
+}
+
+int melspec_blm_stream_finish_host(void *h, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats, uint32_t *frames_out) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, MELSPEC_PCM_F32)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
+    return bls_push_host(st, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, out_capacity_floats, frames_out);
+}
+
+int melspec_blm_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                   uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, pcm_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
+        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_blm_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
+    if (io_misaligned(d_chunks, d_out, pcm_dtype))       // (the rows are f32: the out half of the code is 0)
+        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    return bls_push(st, ids, lens, n, false, frames_out, [&](const BlmStreamPlan &pl) {
+        return bls_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
+                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream});
+    });
+}
+
+int melspec_blm_stream_finish_device(void *h, const uint32_t *ids, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, MELSPEC_PCM_F32)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
+    if (io_misaligned(nullptr, d_out, MELSPEC_PCM_F32)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    return bls_push(st, ids, nullptr, n, true, frames_out, [&](const BlmStreamPlan &pl) {
+        return bls_run(st, pl, n, PushArgs{nullptr, MELSPEC_PCM_F32, nullptr, d_out, h_out_offsets, stream ? static_cast<hipStream_t>(stream) : st->core.stream});
+    });
+}
+
+int melspec_blm_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_mean, float *d_inv_std, uint64_t *h_counts, void *stream) {
+    BlmStreamBank *st = bls_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
+    if (!d_mean || !d_inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "d_mean / d_inv_std is NULL");
+    for (uint32_t i = 0; i < n; ++i)
+        if (ids[i] >= st->geom.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
+    HIP_TRY(hipSetDevice(st->b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st->b->stream;
+    const size_t bytes = round16(static_cast<size_t>(n) * sizeof(uint32_t));
+    RaggedSlot *sl = nullptr;
+    int rc = table_slot_take(st->core.ring, bytes, sl);
+    if (rc) return rc;
+    std::memcpy(sl->host, ids, static_cast<size_t>(n) * sizeof(uint32_t));
+    SlotGuard slot_guard{sl, s};
+    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
+    BlmStreamMomentsParams mp{};
+    mp.ids = static_cast<const uint32_t *>(sl->dev.p); mp.moments = static_cast<const double *>(st->moments.p);
+    mp.counts = static_cast<const unsigned long long *>(st->counts.p); mp.mean = d_mean; mp.inv_std = d_inv_std; mp.n = n; mp.n_mels = static_cast<int>(st->geom.n_mels);
+    const uint64_t total = static_cast<uint64_t>(n) * st->geom.n_mels;
+    hipLaunchKernelGGL(blm_stream_moments_kernel, dim3(grid_for((total + kBlmStreamStatsThreads - 1) / kBlmStreamStatsThreads, st->b->dev.cus, 8)),
+                       dim3(kBlmStreamStatsThreads), 0, s, mp);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    if (h_counts)
+        for (uint32_t i = 0; i < n; ++i) h_counts[i] = st->book.emitted[ids[i]];
+    return MELSPEC_OK;
+}
+
+int melspec_blm_stream_stats_host(void *h, const uint32_t *ids, uint32_t n, float *mean, float *inv_std, uint64_t *counts) {
+    BlmStreamBank *st = bls_of(h);
+    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
+    if (n == 0) return MELSPEC_OK;
+    if (!mean || !inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "mean / inv_std is NULL");
+    HIP_TRY(hipSetDevice(st->b->dev.device));
+    const size_t bytes = static_cast<size_t>(n) * st->geom.n_mels * sizeof(float);
+    if (int rc = st->stats.ensure(2 * bytes + 16)) return rc;
+    float *d_mean = static_cast<float *>(st->stats.p), *d_inv = d_mean + static_cast<size_t>(n) * st->geom.n_mels;
+    if (int rc = melspec_blm_stream_stats_device(h, ids, n, d_mean, d_inv, counts, st->b->stream)) return rc;
+    HIP_TRY(hipMemcpy(mean, d_mean, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(inv_std, d_inv, bytes, hipMemcpyDeviceToHost));
     return MELSPEC_OK;
 }
 

@@ -6,6 +6,9 @@
 // MS_FB512_CONTINUES (fbank512_stream_kernel, fbank512_stream_kernels.hpp: Kaldi flavour, parameter q around p): q.d_cont[clip] != 0 says
 // that the clip continues a stream -- the sample in front of its first frame exists and is that frame's predecessor (src/fbank.rs:177-181);
 // without the macro the text below is what it always was.
+// MS_FB512_CLIP_ORG0 (fbank512_nemo_stream_kernel, fbank512_nemo_stream_kernels.hpp: NeMo flavour, parameter q around p): the window origin
+// of a clip's first frame is the clip's own, q.d_org0[clip], instead of the batch's p.org0; without the macro the text below is what it
+// always was.
     using L = FbankLayout<T>;
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
     const int tid = threadIdx.x;
@@ -99,7 +102,11 @@
             w512_phase1<T>(fl, j, act, loc.pcm + (f0 + (uint64_t)(act ? fl : 0)) * (uint64_t)p.shift, tblob, slice);
         } else {
             const long long clip_len = p.d_len ? (long long)p.d_len[loc.clip] : p.clip_len;
+#ifdef MS_FB512_CLIP_ORG0
+            const long long org = (long long)(f0 + (uint64_t)fl) * p.shift + q.d_org0[loc.clip];
+#else
             const long long org = (long long)(f0 + (uint64_t)fl) * p.shift + p.org0;
+#endif
             const bool inside = org >= 1 && org + 400 <= clip_len;
             const bool all_inside = __builtin_amdgcn_ballot_w64(act && !inside) == 0;
             nemo_phase1<T>(fl, j, act, all_inside, loc.pcm, org, clip_len, static_cast<float>(p.preemph), tblob, slice);

@@ -8,7 +8,7 @@
 //   fused512_route.hpp  route512: which of its kernels a batch runs on, the list of its instantiations (no HIP: host-testable)
 //   pow2.hip        generic_frame_kernel / pow2_frame_kernel / generic_stft_kernel: every other geometry, f64
 //   aux.hip         batch planners, streaming bank, TGA quantiser, VAD columns, stand-alone mel helpers, synthetic PCM
-//   stream_bank.hpp BankCore: what the streaming bank (aux.hip) and the Kaldi fbank's stream bank (fbank512.hip) share; includes this header
+//   stream_bank.hpp BankCore: what the streaming bank (aux.hip) and the stream banks of the Kaldi fbank and the NeMo frontend (fbank512.hip) share; includes this header
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
 #pragma once
 #include <hip/hip_runtime.h>

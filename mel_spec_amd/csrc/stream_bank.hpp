@@ -1,6 +1,6 @@
-// stream_bank.hpp -- what the banks of live streams share on the host side: the Whisper bank (melspec_stream_*, aux.hip) and the Kaldi
-// fbank's (melspec_fbank_stream_*, fbank512.hip) are this core plus their own planner (stream_plan.hpp / fbank_stream_plan.hpp) and their
-// own frame stage.  A bank is n_streams slots of `stride` floats in HBM, [carry, ending at in_off][next chunk at in_off]; a push is
+// stream_bank.hpp -- what the banks of live streams share on the host side: the Whisper bank (melspec_stream_*, aux.hip), the Kaldi
+// fbank's (melspec_fbank_stream_*, fbank512.hip) and the NeMo / Parakeet frontend's (melspec_blm_stream_*, fbank512.hip) are this core plus
+// their own planner (stream_plan.hpp / fbank_stream_plan.hpp / blm_stream_plan.hpp) and their own frame stage.  A bank is n_streams slots of `stride` floats in HBM, [carry, ending at in_off][next chunk at in_off]; a push is
 //   entries up (unless the device still holds them) -> scatter -> the bank's frame stage -> carry -> wait
 // on one stream, and the host form of it stages samples and rows through the bank's two buffers.
 #pragma once
@@ -19,7 +19,7 @@ struct BankCore {
     float *slot(uint32_t id) const { return static_cast<float *>(state.p) + id * stride; }
 };
 
-// a planner's status (stream_plan_push, fbank_stream_plan_push) as the ABI's
+// a planner's status (stream_plan_push, fbank_stream_plan_push, blm_stream_plan_push) as the ABI's
 inline int plan_status(int rc, const char *err) {
     return rc == 1 ? fail(MELSPEC_ERR_INVALID_ARG, err) : rc == 2 ? fail(MELSPEC_ERR_CAPACITY, err) : MELSPEC_OK;
 }

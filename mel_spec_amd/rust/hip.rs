@@ -145,6 +145,28 @@ unsafe extern "C" {
     fn melspec_fbank_stream_stats_device(st: *mut c_void, ids: *const u32, n: u32, d_means: *mut f32, h_counts: *mut u64, stream: *mut c_void) -> c_int;
 }
 
+extern "C" {
+    // BatchLogMelSpectrogram::compute fed chunk by chunk: un-normalised feature-major columns + running per-feature mean and 1 / std (the
+    // handle crosses the ABI as void *)
+    fn melspec_blm_stream_create(out: *mut *mut c_void, b: *mut BlmHandle, n_streams: u32, max_chunk: u32) -> c_int;
+    fn melspec_blm_stream_destroy(st: *mut c_void);
+    fn melspec_blm_stream_reset(st: *mut c_void, ids: *const u32, n: u32) -> c_int;
+    fn melspec_blm_stream_frames_after(st: *const c_void, id: u32, n_new: u32) -> usize;
+    fn melspec_blm_stream_finish_frames(st: *const c_void, id: u32) -> usize;
+    fn melspec_blm_stream_push_host(st: *mut c_void, ids: *const u32, samples: *const c_void, pcm_dtype: c_int, lens: *const u32, n: u32,
+                                    out: *mut f32, out_capacity_floats: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_blm_stream_input_ptr(st: *mut c_void, id: u32) -> *mut f32;
+    fn melspec_blm_stream_push_device(st: *mut c_void, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
+                                      lens: *const u32, n: u32, d_out: *mut f32, h_out_offsets: *const u64, frames_out: *mut u32,
+                                      stream: *mut c_void) -> c_int;
+    fn melspec_blm_stream_finish_host(st: *mut c_void, ids: *const u32, n: u32, out: *mut f32, out_capacity_floats: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_blm_stream_finish_device(st: *mut c_void, ids: *const u32, n: u32, d_out: *mut f32, h_out_offsets: *const u64, frames_out: *mut u32,
+                                        stream: *mut c_void) -> c_int;
+    fn melspec_blm_stream_stats_host(st: *mut c_void, ids: *const u32, n: u32, mean: *mut f32, inv_std: *mut f32, counts: *mut u64) -> c_int;
+    fn melspec_blm_stream_stats_device(st: *mut c_void, ids: *const u32, n: u32, d_mean: *mut f32, d_inv_std: *mut f32, h_counts: *mut u64,
+                                       stream: *mut c_void) -> c_int;
+}
+
 #[repr(C)]
 struct Tga {
     _private: [u8; 0],
@@ -861,6 +883,92 @@ impl HipBatchLogMel {
 impl Drop for HipBatchLogMel {
     fn drop(&mut self) {
         unsafe { melspec_blm_destroy(self.b) }
+    }
+}
+
+/// One live stream of `BatchLogMelSpectrogram::compute` (src/mel.rs) over a 1-stream bank (`melspec_blm_stream_*`): `push` returns the
+/// un-normalised columns a chunk completes, `finish` the zero-padded ones at the end of the stream; concatenated they are the bits of
+/// `compute` on the whole clip with `normalize_per_feature` off.  `stats` gives the running per-feature mean and 1 / (std + 1e-5).
+pub struct HipBatchLogMelStream<'a> {
+    st: *mut c_void,
+    n_mels: usize,
+    _blm: std::marker::PhantomData<&'a mut HipBatchLogMel>,
+}
+impl<'a> HipBatchLogMelStream<'a> {
+    pub fn new(blm: &'a mut HipBatchLogMel, max_chunk: usize) -> Result<Self, HipError> {
+        let mut st = std::ptr::null_mut();
+        check(unsafe { melspec_blm_stream_create(&mut st, blm.b, 1, max_chunk as u32) })?;
+        Ok(Self { st, n_mels: blm.n_mels, _blm: std::marker::PhantomData })
+    }
+    fn columns(&self, flat: Vec<f32>, frames: u32) -> ndarray::Array2<f32> {
+        let k = frames as usize;
+        ndarray::Array2::from_shape_vec((self.n_mels, k), flat[..self.n_mels * k].to_vec()).expect("shape")
+    }
+    /// Feeds a block of any length <= max_chunk; `(n_mels, k)` columns.
+    pub fn push(&mut self, samples: &[f32]) -> Result<ndarray::Array2<f32>, HipError> {
+        let (id, len) = (0u32, samples.len() as u32);
+        let cap = unsafe { melspec_blm_stream_frames_after(self.st, 0, len) } * self.n_mels;
+        let mut flat = vec![0f32; cap];
+        let mut frames = 0u32;
+        check(unsafe {
+            melspec_blm_stream_push_host(self.st, &id, samples.as_ptr() as *const c_void, PCM_F32, &len, 1, flat.as_mut_ptr(), cap, &mut frames)
+        })?;
+        Ok(self.columns(flat, frames))
+    }
+    /// Ends the stream: the columns that read past its end.  A later `push` fails until `reset`.
+    pub fn finish(&mut self) -> Result<ndarray::Array2<f32>, HipError> {
+        let id = 0u32;
+        let cap = unsafe { melspec_blm_stream_finish_frames(self.st, 0) } * self.n_mels;
+        let mut flat = vec![0f32; cap];
+        let mut frames = 0u32;
+        check(unsafe { melspec_blm_stream_finish_host(self.st, &id, 1, flat.as_mut_ptr(), cap, &mut frames) })?;
+        Ok(self.columns(flat, frames))
+    }
+    /// `(mean, inv_std, columns emitted)`
+    pub fn stats(&mut self) -> Result<(Vec<f32>, Vec<f32>, u64), HipError> {
+        let id = 0u32;
+        let (mut mean, mut inv_std, mut count) = (vec![0f32; self.n_mels], vec![0f32; self.n_mels], 0u64);
+        check(unsafe { melspec_blm_stream_stats_host(self.st, &id, 1, mean.as_mut_ptr(), inv_std.as_mut_ptr(), &mut count) })?;
+        Ok((mean, inv_std, count))
+    }
+    pub fn reset(&mut self) -> Result<(), HipError> {
+        check(unsafe { melspec_blm_stream_reset(self.st, std::ptr::null(), 0) })
+    }
+    /// Where a device producer writes the stream's next chunk (f32, room for max_chunk samples).
+    pub fn input_ptr(&mut self) -> *mut f32 {
+        unsafe { melspec_blm_stream_input_ptr(self.st, 0) }
+    }
+    /// A chunk of `len` elements of `pcm_dtype` in device memory (null: f32 already at `input_ptr`) into `(n_mels, k)` f32 columns at
+    /// `d_out`; returns k, after the launches have completed.
+    ///
+    /// # Safety
+    /// `d_chunk` must hold `len` elements of `pcm_dtype` on the device and `d_out` room for the columns the push emits.
+    pub unsafe fn push_device(&mut self, d_chunk: *const c_void, pcm_dtype: i32, len: u32, d_out: *mut f32, stream: *mut c_void) -> Result<u32, HipError> {
+        let id = 0u32;
+        let mut frames = 0u32;
+        check(melspec_blm_stream_push_device(self.st, &id, d_chunk, pcm_dtype as c_int, std::ptr::null(), &len, 1, d_out, std::ptr::null(), &mut frames, stream))?;
+        Ok(frames)
+    }
+    /// # Safety
+    /// `d_out` must have room for the columns the finish emits (`melspec_blm_stream_finish_frames`).
+    pub unsafe fn finish_device(&mut self, d_out: *mut f32, stream: *mut c_void) -> Result<u32, HipError> {
+        let id = 0u32;
+        let mut frames = 0u32;
+        check(melspec_blm_stream_finish_device(self.st, &id, 1, d_out, std::ptr::null(), &mut frames, stream))?;
+        Ok(frames)
+    }
+    /// # Safety
+    /// `d_mean` and `d_inv_std` must each have room for n_mels f32 on the device.
+    pub unsafe fn stats_device(&mut self, d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> Result<u64, HipError> {
+        let id = 0u32;
+        let mut count = 0u64;
+        check(melspec_blm_stream_stats_device(self.st, &id, 1, d_mean, d_inv_std, &mut count, stream))?;
+        Ok(count)
+    }
+}
+impl Drop for HipBatchLogMelStream<'_> {
+    fn drop(&mut self) {
+        unsafe { melspec_blm_stream_destroy(self.st) }
     }
 }
 

@@ -271,6 +271,86 @@ class FbankStreamBank(_Bank):
         return counts
 
 
+class BlmStreamBank(_Bank):
+    """n_streams independent BatchLogMelSpectrogram::compute streams (src/mel.rs) on one BatchLogMelSpectrogram's geometry
+    (melspec_blm_stream_*): after pushes whose chunks concatenate to x and one finish, a stream has emitted exactly the columns of
+    compute(x) on a normalize_per_feature = False twin in the same precision mode (pad_to ignored) -- bit for bit, however x was cut
+    -- and stats() returns the running per-feature mean and 1 / (std + 1e-5) of those columns (Welford in f64, in time order).
+    The frontend must be on the fused kernels (n_fft = 512, win_length = 400)."""
+    _P = "melspec_blm_stream_"
+
+    def __init__(self, blm, n_streams: int, max_chunk: int):
+        self._blm = blm                      # keeps the context alive
+        self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), int(blm.config.n_mels)
+        h = C.c_void_p()
+        _check(lib().melspec_blm_stream_create(C.byref(h), blm._h, self.n_streams, self.max_chunk), construct=True)
+        self._h = h
+
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        """no history, no frames, not ended, zero statistics for the listed streams (None: all)"""
+        super().reset(ids)
+
+    def finish_frames(self, stream: int) -> int:
+        return int(lib().melspec_blm_stream_finish_frames(self._h, stream))
+
+    def _split(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
+        res, cur = [], 0
+        for f in frames:
+            n = int(f) * self.n_mels
+            res.append(out[cur:cur + n].reshape(self.n_mels, int(f)))
+            cur += n
+        return res
+
+    def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
+        """Append chunks[i] (any length <= max_chunk; np.int16 chunks are 16-bit PCM, value = sample / 32768 exactly, and all chunks of
+        one call have the same dtype) to stream ids[i]; returns the un-normalised columns each stream emitted, [n_mels, k_i]."""
+        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
+        out = np.empty(cap * self.n_mels, np.float32)
+        _check(lib().melspec_blm_stream_push_host(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
+                                                  a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
+        assert int(frames.sum()) == cap
+        return self._split(out, frames)
+
+    def finish(self, ids: Sequence[int]) -> List[np.ndarray]:
+        """End the listed streams: the columns that read past the stream's end (zero padding), [n_mels, k_i]; nothing for an empty stream."""
+        a = _u32(ids)
+        cap = sum(self.finish_frames(int(s)) for s in a)
+        out, frames = np.empty(cap * self.n_mels, np.float32), np.zeros(a.shape[0], np.uint32)
+        _check(lib().melspec_blm_stream_finish_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
+        return self._split(out, frames)
+
+    def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, d_chunks: int = 0, pcm_dtype: int = PCM_F32,
+                    src_offsets=None, stream: int = 0) -> np.ndarray:
+        """d_chunks == 0: the chunks are at input_ptr, in f32; otherwise chunk i is lens[i] elements of pcm_dtype at d_chunks +
+        src_offsets[i] elements (None: back to back).  Entry i's [n_mels, k_i] rows go to d_out + out_offsets[i] floats (None: back to back)."""
+        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
+        _check(lib().melspec_blm_stream_push_device(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
+                                                    p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
+    def finish_device(self, ids: Sequence[int], d_out: int, out_offsets=None, stream: int = 0) -> np.ndarray:
+        frames, n, (p_ids, _p_lens, p_oo), _arrs = self._dev(ids, [0] * len(ids), out_offsets)
+        _check(lib().melspec_blm_stream_finish_device(self._h, p_ids, n, C.c_void_p(d_out or None), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
+    def stats(self, ids: Sequence[int]):
+        """(mean [n, n_mels] f32, inv_std [n, n_mels] f32, counts [n] u64) of the columns the streams have emitted so far: inv_std =
+        1 / (sqrt(M2 / max(count - 1, 1)) + 1e-5); mean 0 and inv_std 1e5 for a stream without a column"""
+        a = _u32(ids)
+        mean, inv_std = np.zeros((a.shape[0], self.n_mels), np.float32), np.zeros((a.shape[0], self.n_mels), np.float32)
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(lib().melspec_blm_stream_stats_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(mean), _fp(inv_std), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return mean, inv_std, counts
+
+    def stats_device(self, ids: Sequence[int], d_mean: int, d_inv_std: int, stream: int = 0) -> np.ndarray:
+        """mean and inv_std to device memory ([n, n_mels] f32 each); returns the counts"""
+        a = _u32(ids)
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(lib().melspec_blm_stream_stats_device(self._h, a.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_mean or None), C.c_void_p(d_inv_std or None),
+                                                     counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream or None)))
+        return counts
+
+
 class RingBuffer:
     """One stream with the reference's interface (src/rb.rs:18-121): add_frame / add feed samples, maybe_mel
     returns one (n_mels, 1) column per completed hop or None.  Frames are computed on the device in batches
