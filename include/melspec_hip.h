@@ -668,8 +668,8 @@ int melspec_fbank_stream_stats_device(void *st, const uint32_t *ids, uint32_t n,
  * the split output's definition -- and the column count; count == 0 gives mean 0 and inv_std 1e5.  At end of stream (rows - mean) *
  * inv_std is the normalised call's output to within the error of its f32 folds; before that, online cumulative normalisation.
  * Per stream the device keeps the samples from the predecessor of the next frame's first tap on: fewer than 401 (center = 0: 457).
- * Rows are f32 only; chunks are MELSPEC_PCM_F32 or MELSPEC_PCM_S16 (int16 * 2^-15, exactly, converted where the chunk is copied into the
- * f32 state).
+ * Rows of these calls are f32 (f16 / bf16 rows: the _io forms below); chunks are MELSPEC_PCM_F32 or MELSPEC_PCM_S16 (int16 * 2^-15,
+ * exactly, converted where the chunk is copied into the f32 state).
  * The handle is opaque and crosses the ABI as void *.  The context must outlive the bank; one bank per host thread, like the context.
  * Needs the fused geometry (n_fft = 512, win_length = 400, a bank the fused kernels hold): otherwise MELSPEC_ERR_UNSUPPORTED at create
  * with melspec_last_error naming the geometry.  n_streams == 0 or max_chunk == 0, a NULL handle (no device is touched), an id out of
@@ -706,6 +706,57 @@ int melspec_blm_stream_finish_device(void *st, const uint32_t *ids, uint32_t n, 
 int melspec_blm_stream_stats_host(void *st, const uint32_t *ids, uint32_t n, float *mean, float *inv_std, uint64_t *counts);
 int melspec_blm_stream_stats_device(void *st, const uint32_t *ids, uint32_t n, float *d_mean, float *d_inv_std, uint64_t *h_counts,
                                     void *stream);
+
+/* ---- f16 / bf16 rows out of the two stream banks above: their pushes (and the NeMo bank's finish) with typed ends ---- */
+/* pcm_dtype is MELSPEC_PCM_F32 or MELSPEC_PCM_S16, out_dtype MELSPEC_OUT_F32, _F16 or _BF16, as for the batch calls.
+ * Rows: an element of a MELSPEC_OUT_F16 / _BF16 call is the f32 element the f32 call would emit for the same bank history, rounded to
+ * nearest even once; a NaN stays a NaN, a value beyond the f16 range becomes an infinity.  Layouts are the f32 calls': Kaldi
+ * [frame][num_mel_bins] per entry, NeMo [n_mels][frames_i] per entry, and for the NeMo bank's finish the zero-padded last columns laid
+ * out the same way.
+ * State and statistics are untouched by the row type: after any mix of f32 and typed calls the bank's carry, its frame counts and what
+ * melspec_fbank_stream_stats_* / melspec_blm_stream_stats_* return are the bits a bank driven through the f32 calls alone holds.  The
+ * statistics are folds over the f32 rows; the rounded rows never feed them.  How: the frame kernels of the f32 push, unchanged, write their
+ * f32 rows packed into a scratch of the bank (grow-only, allocated by the first typed call -- a bank that only sees f32 calls never has
+ * one --, released at destroy), and a twin of the fold kernel behind them reads each f32 element there once, folds it exactly as the f32
+ * push's fold does (same operations, same order, no contraction) and stores it, rounded, at its place in the caller's rows
+ * (csrc/stream_banks_io_kernels.hpp; the precedent is the batch _io calls with CMN / normalize_per_feature above).  No kernel reads the
+ * caller's rows and there is no conversion pass.  Because the frame kernels are the f32 push's, typed rows exist on every geometry a bank
+ * can be created on -- not only on the narrower set of the batch _io calls: melspec_*_stream_supports_io is 1 for every valid pair of
+ * codes on a live bank whose object is still on the fused path, 0 otherwise (NULL or foreign handle, unknown code).
+ * Capacities and offsets count elements of the row type; buffers need the natural alignment of their element type only.  A 16-bit entry
+ * may start at an odd element, and in the NeMo layout every mel row behind the first does whenever frames_i is odd: neighbouring entries
+ * may share a 4-byte word.  Rows are written with one 2-byte store per element, never with a read-modify-write of a word.
+ * (pcm, MELSPEC_OUT_F32) is the existing call: the same launches, no scratch.
+ * Checked in this order: NULL bank (MELSPEC_ERR_INVALID_ARG, no device is touched, melspec_last_error says "NULL"), unknown pcm_dtype /
+ * out_dtype code (MELSPEC_ERR_INVALID_ARG), support (MELSPEC_ERR_UNSUPPORTED), then everything the f32 call checks, with its codes:
+ * d_chunks == NULL needs MELSPEC_PCM_F32, a device pointer misaligned for its element type, an id out of range or listed twice,
+ * MELSPEC_ERR_CAPACITY, an ended NeMo stream.  A refused call queues nothing, writes nothing to the output and leaves the bank, its
+ * state and its statistics as they were.  "The launches have completed on return" holds as for the f32 pushes.  The host forms move the
+ * rows across the bus in their own type.
+ * Measured (profiles/stream_banks_io.txt; MI355X, 1024 live streams, ms per push at 10 ms / 100 ms / 1 s chunks; C = push_device_io
+ * (F32, F16) with the chunks at *_stream_input_ptr, B = the f32 push followed by a torch cast of the rows to f16 and a synchronise; D =
+ * push_device_io (S16, F16), Bs = B with a torch int16 -> f32 conversion of the chunks in front).  Kaldi: C 0.0537 / 0.0611 / 0.1381, B
+ * 0.0679 / 0.0755 / 0.1547, D 0.0662 / 0.0736 / 0.1629, Bs 0.0835 / 0.0908 / 0.1998.  NeMo f64: C 0.0557 / 0.0640 / 0.1437, B 0.0699 /
+ * 0.0770 / 0.1673, D 0.0695 / 0.0779 / 0.1677, Bs 0.0857 / 0.0948 / 0.2133.  NeMo MELSPEC_PRECISION_F32: C 0.0565 / 0.0605 / 0.1269, B
+ * 0.0704 / 0.0728 / 0.1521, D 0.0702 / 0.0729 / 0.1512, Bs 0.0859 / 0.0893 / 0.1912.  C and D are faster than B and Bs at every size
+ * (0.79 - 0.89 x); the typed push costs 0.97 - 1.07 x of the f32 push. */
+int melspec_fbank_stream_supports_io(const void *st, int pcm_dtype, int out_dtype);
+int melspec_fbank_stream_push_host_io(void *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                      void *out, int out_dtype, size_t out_capacity_elems, uint32_t *frames_out);
+int melspec_fbank_stream_push_device_io(void *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                        const uint32_t *lens, uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets,
+                                        uint32_t *frames_out, void *stream);
+
+int melspec_blm_stream_supports_io(const void *st, int pcm_dtype, int out_dtype);
+int melspec_blm_stream_push_host_io(void *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n,
+                                    void *out, int out_dtype, size_t out_capacity_elems, uint32_t *frames_out);
+int melspec_blm_stream_push_device_io(void *st, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets,
+                                      const uint32_t *lens, uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets,
+                                      uint32_t *frames_out, void *stream);
+int melspec_blm_stream_finish_host_io(void *st, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems,
+                                      uint32_t *frames_out);
+int melspec_blm_stream_finish_device_io(void *st, const uint32_t *ids, uint32_t n, void *d_out, int out_dtype,
+                                        const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream);
 
 /* ---- 8-bit quantisation + TGA container: replaces src/quant.rs ------------------------ */
 /* The reference's wire/disk format right after the mel path: a mel-major interleaved image

@@ -271,6 +271,24 @@ public:
         detail::check(melspec_fbank_stream_stats_device(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_means, counts, stream), false);
     }
 
+    // additive: f16 / bf16 rows out (MELSPEC_OUT_* of melspec_hip.h); offsets count elements of the row type, stats() stays that of the f32 rows
+    bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_fbank_stream_supports_io(st_, pcm_dtype, out_dtype) != 0; }
+    // push() on 16-bit PCM into out_dtype rows (MELSPEC_OUT_F16 / _BF16), returned as their bit patterns, (frames, num_mel_bins) row-major
+    std::vector<std::uint16_t> push_s16(std::uint32_t id, const std::vector<std::int16_t> &chunk, int out_dtype, std::size_t *frames = nullptr) {
+        std::vector<std::uint16_t> out(frames_after(id, chunk.size()) * n_mels_);
+        const std::uint32_t len = static_cast<std::uint32_t>(chunk.size());
+        std::uint32_t got = 0;
+        detail::check(melspec_fbank_stream_push_host_io(st_, &id, chunk.data(), MELSPEC_PCM_S16, &len, 1, out.data(), out_dtype, out.size(), &got), false);
+        if (frames) *frames = got;
+        return out;
+    }
+    void push_device_io(const std::vector<std::uint32_t> &ids, const void *d_chunks, int pcm_dtype, const std::uint64_t *src_offsets,
+                        const std::vector<std::uint32_t> &lens, void *d_out, int out_dtype, const std::uint64_t *out_offsets, std::uint32_t *frames_out,
+                        void *stream = nullptr) {
+        detail::check(melspec_fbank_stream_push_device_io(st_, ids.data(), d_chunks, pcm_dtype, src_offsets, lens.data(), static_cast<std::uint32_t>(ids.size()), d_out,
+                                                          out_dtype, out_offsets, frames_out, stream), false);
+    }
+
 private:
     Array2f push_typed(std::uint32_t id, const void *samples, int pcm_dtype, std::size_t n) {
         Array2f a;
@@ -414,6 +432,35 @@ public:
     }
     void stats_device(const std::vector<std::uint32_t> &ids, float *d_mean, float *d_inv_std, std::uint64_t *counts, void *stream = nullptr) {
         detail::check(melspec_blm_stream_stats_device(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_mean, d_inv_std, counts, stream), false);
+    }
+
+    // additive: f16 / bf16 rows out (MELSPEC_OUT_* of melspec_hip.h); offsets count elements of the row type, stats() stays that of the f32 rows
+    bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_blm_stream_supports_io(st_, pcm_dtype, out_dtype) != 0; }
+    // push() on 16-bit PCM / finish() into out_dtype columns (MELSPEC_OUT_F16 / _BF16), returned as their bit patterns, (n_mels, frames) row-major
+    std::vector<std::uint16_t> push_s16(std::uint32_t id, const std::vector<std::int16_t> &chunk, int out_dtype, std::size_t *frames = nullptr) {
+        std::vector<std::uint16_t> out(frames_after(id, chunk.size()) * n_mels_);
+        const std::uint32_t len = static_cast<std::uint32_t>(chunk.size());
+        std::uint32_t got = 0;
+        detail::check(melspec_blm_stream_push_host_io(st_, &id, chunk.data(), MELSPEC_PCM_S16, &len, 1, out.data(), out_dtype, out.size(), &got), false);
+        if (frames) *frames = got;
+        return out;
+    }
+    std::vector<std::uint16_t> finish_io(std::uint32_t id, int out_dtype, std::size_t *frames = nullptr) {
+        std::vector<std::uint16_t> out(finish_frames(id) * n_mels_);
+        std::uint32_t got = 0;
+        detail::check(melspec_blm_stream_finish_host_io(st_, &id, 1, out.data(), out_dtype, out.size(), &got), false);
+        if (frames) *frames = got;
+        return out;
+    }
+    void push_device_io(const std::vector<std::uint32_t> &ids, const void *d_chunks, int pcm_dtype, const std::uint64_t *src_offsets,
+                        const std::vector<std::uint32_t> &lens, void *d_out, int out_dtype, const std::uint64_t *out_offsets, std::uint32_t *frames_out,
+                        void *stream = nullptr) {
+        detail::check(melspec_blm_stream_push_device_io(st_, ids.data(), d_chunks, pcm_dtype, src_offsets, lens.data(), static_cast<std::uint32_t>(ids.size()), d_out,
+                                                        out_dtype, out_offsets, frames_out, stream), false);
+    }
+    void finish_device_io(const std::vector<std::uint32_t> &ids, void *d_out, int out_dtype, const std::uint64_t *out_offsets, std::uint32_t *frames_out,
+                          void *stream = nullptr) {
+        detail::check(melspec_blm_stream_finish_device_io(st_, ids.data(), static_cast<std::uint32_t>(ids.size()), d_out, out_dtype, out_offsets, frames_out, stream), false);
     }
 
 private:

@@ -200,6 +200,14 @@ SIGNATURES = {
     "melspec_blm_stream_finish_device": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, _u64p, _u32p, _vp]),
     "melspec_blm_stream_stats_host": (C.c_int, [_vp, _u32p, C.c_uint32, _f32p, _f32p, _u64p]),
     "melspec_blm_stream_stats_device": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, _vp, _u64p, _vp]),
+    "melspec_fbank_stream_supports_io": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "melspec_fbank_stream_push_host_io": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u32p, C.c_uint32, _vp, C.c_int, C.c_size_t, _u32p]),
+    "melspec_fbank_stream_push_device_io": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u64p, _u32p, C.c_uint32, _vp, C.c_int, _u64p, _u32p, _vp]),
+    "melspec_blm_stream_supports_io": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "melspec_blm_stream_push_host_io": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u32p, C.c_uint32, _vp, C.c_int, C.c_size_t, _u32p]),
+    "melspec_blm_stream_push_device_io": (C.c_int, [_vp, _u32p, _vp, C.c_int, _u64p, _u32p, C.c_uint32, _vp, C.c_int, _u64p, _u32p, _vp]),
+    "melspec_blm_stream_finish_host_io": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, C.c_int, C.c_size_t, _u32p]),
+    "melspec_blm_stream_finish_device_io": (C.c_int, [_vp, _u32p, C.c_uint32, _vp, C.c_int, _u64p, _u32p, _vp]),
     "melspec_stream_enable_vad":(C.c_int, [_vp, C.POINTER(VadSettingsC)]),
     "melspec_stream_vad_frames": (C.c_uint64, [_vp, C.c_uint32]),
     "melspec_stream_push_host_vad": (C.c_int, [_vp, _u32p, _f32p, _u32p, C.c_uint32, _f32p, C.c_size_t, _u32p, _vp, C.c_size_t]),

@@ -7,6 +7,7 @@
 #include "fbank512_stats_kernels.hpp"
 #include "fbank512_stream_kernels.hpp"
 #include "fbank512_nemo_stream_kernels.hpp"
+#include "stream_banks_io_kernels.hpp"
 #include "blm_stats_plan.hpp"
 #include "blm_stream_plan.hpp"
 #include "fbank_stream_plan.hpp"
@@ -1291,6 +1292,25 @@ struct FbankStreamBank {
     BankCore core;
     DevBuf sums, counts;                 // [n_streams][bins] f64, [n_streams] u64
     DevBuf means;                        // the host stats call's buffer
+    DevBuf rows32;                       // the f32 rows of a push with 16-bit rows, packed in entry order: allocated by the first such push
+};
+
+// The table that travels behind a push's entries (core_run's tail).  An f32 push: the bank's own table as it is.  A push with 16-bit rows
+// (stream_banks_io_kernels.hpp): the fold behind the frame stage needs each entry's place in the bank's f32 scratch beside its place in the
+// caller's rows (the entries' out_off), so the plan's packed offsets follow the bank's table, 8-byte aligned.
+struct TypedTail {
+    std::vector<unsigned char> joined;
+    const void *data;
+    size_t bytes, packed_at = 0;
+    TypedTail(const void *own, size_t own_bytes, const uint64_t *packed_off, uint32_t n) : data(own), bytes(own_bytes) {
+        if (!packed_off) return;
+        packed_at = (own_bytes + 7) & ~static_cast<size_t>(7);
+        joined.resize(packed_at + static_cast<size_t>(n) * sizeof(uint64_t));
+        std::memcpy(joined.data(), own, own_bytes);
+        std::memcpy(joined.data() + packed_at, packed_off, static_cast<size_t>(n) * sizeof(uint64_t));
+        data = joined.data(); bytes = joined.size();
+    }
+    const uint64_t *packed_on_device(const void *d_tail) const { return reinterpret_cast<const uint64_t *>(static_cast<const char *>(d_tail) + packed_at); }
 };
 
 FbankStreamBank *fbs_of(void *h) {
@@ -1310,24 +1330,41 @@ int fbs_supported(const melspec_fbank *fb) {
     return MELSPEC_ERR_UNSUPPORTED;
 }
 
-// the frame stage behind the core's scatter: the rows, then their column sums; the entries' tail is the clips' continues flags
-int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const PushArgs &a) {
+// the frame stage behind the core's scatter: the rows, then their column sums; the entries' tail is the clips' continues flags.
+// out_dtype: the row type at a.d_out.  16-bit rows: the same frame stage, planned onto the bank's f32 scratch with the plan's packed
+// offsets, and the typed twin of the sum kernel, which reads the rows there and writes the caller's (the scratch grows before anything
+// is queued)
+int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const PushArgs &a, int out_dtype = MELSPEC_OUT_F32) {
     melspec_fbank *fb = st->fb;
     const int nm = fb->cfg.num_mel_bins;
-    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t),
-                    [&](const StreamEntry *d_e, const void *d_cont) {
+    const bool typed = out_dtype != MELSPEC_OUT_F32;
+    TypedTail tail(pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t), typed ? pl.out_off.data() : nullptr, n);
+    if (typed && pl.total_frames) {
+        if (!a.d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");
+        HIP_TRY(hipSetDevice(st->core.device));
+        if (int rc = st->rows32.ensure(static_cast<size_t>(pl.total_frames) * nm * sizeof(float) + 16)) return rc;
+    }
+    float *rows = static_cast<float *>(typed ? st->rows32.p : a.d_out);
+    const uint64_t *rows_off = a.h_out_off && !typed ? a.h_out_off : pl.out_off.data();
+    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data, tail.bytes, [&](const StreamEntry *d_e, const void *d_tail) {
         BatchPlan bp;
         RaggedSlot *pslot = nullptr;
-        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), static_cast<float *>(a.d_out), pl.off.data(), pl.frames,
-                             a.h_out_off ? a.h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
+        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), rows, pl.off.data(), pl.frames, rows_off, n, nm, kFbFPW, bp, pslot);
         if (!rc) {
             FbankStreamParams q{};
             q.f = fbank_fast_params(fb, bp.desc);
-            q.d_cont = static_cast<const uint32_t *>(d_cont);
+            q.d_cont = static_cast<const uint32_t *>(d_tail);
             rc = launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, nm}, fb->dev.cus, a.stream);
         }
         plan_ragged_done(pslot, a.stream);
         if (rc) return rc;
+        if (typed) {
+            FbankStreamSumIoParams sp{};
+            sp.entries = d_e; sp.src_off = tail.packed_on_device(d_tail); sp.rows = rows; sp.dst = a.d_out; sp.sums = static_cast<double *>(st->sums.p);
+            sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
+            HIP_TRY(fbank_stream_sum_io_launch(sp, out_dtype, n, a.stream));
+            return static_cast<int>(MELSPEC_OK);
+        }
         FbankStreamSumParams sp{};
         sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.sums = static_cast<double *>(st->sums.p);
         sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
@@ -1349,11 +1386,43 @@ int fbs_push(FbankStreamBank *st, const uint32_t *ids, const uint32_t *lens, uin
     return MELSPEC_OK;
 }
 
-// what every push checks first: the handle, the dtype code, the object
-int fbs_push_args(FbankStreamBank *st, int pcm_dtype) {
+// what every push checks first: the handle, the dtype codes, the object
+int fbs_push_args(FbankStreamBank *st, int pcm_dtype, int out_dtype) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
-    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    int io;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     return fbs_supported(st->fb);
+}
+
+// melspec_fbank_stream_push_host / _push_host_io: the rows cross the bus in their own type
+int fbs_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out, int out_dtype,
+                  size_t out_capacity_elems, uint32_t *frames_out) {
+    FbankStreamBank *st = fbs_of(h);
+    if (int rc = fbs_push_args(st, pcm_dtype, out_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
+        const HostPush hp{samples, out, out_capacity_elems, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), io_out_bytes(out_dtype)};
+        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
+            return fbs_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s}, out_dtype);
+        });
+    });
+}
+
+// melspec_fbank_stream_push_device / _push_device_io
+int fbs_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens, uint32_t n,
+                    void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    FbankStreamBank *st = fbs_of(h);
+    if (int rc = fbs_push_args(st, pcm_dtype, out_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
+        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
+    if (io_misaligned(d_chunks, d_out, pcm_dtype | out_dtype << 4)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
+        return fbs_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
+                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream}, out_dtype);
+    });
 }
 }  // namespace
 
@@ -1386,7 +1455,7 @@ void melspec_fbank_stream_destroy(void *h) {
     FbankStreamBank *st = fbs_of(h);
     if (!st) return;
     core_destroy(st->core);
-    st->sums.release(); st->counts.release(); st->means.release();
+    st->sums.release(); st->counts.release(); st->means.release(); st->rows32.release();
     st->magic = 0;
     delete st;
 }
@@ -1425,32 +1494,28 @@ float *melspec_fbank_stream_input_ptr(void *h, uint32_t id) {
 
 int melspec_fbank_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
                                    size_t out_capacity_floats, uint32_t *frames_out) {
-    FbankStreamBank *st = fbs_of(h);
-    if (int rc = fbs_push_args(st, pcm_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
-        const HostPush hp{samples, out, out_capacity_floats, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), sizeof(float)};
-        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
-            return fbs_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s});
-        });
-    });
+    return fbs_push_host(h, ids, samples, pcm_dtype, lens, n, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
 }
 
 int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
                                      uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    FbankStreamBank *st = fbs_of(h);
-    if (int rc = fbs_push_args(st, pcm_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
-        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
-    if (io_misaligned(d_chunks, d_out, pcm_dtype))       // (the rows are f32: the out half of the code is 0)
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
-        return fbs_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
-                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream});
-    });
+    return fbs_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
+}
+
+int melspec_fbank_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) {
+    const FbankStreamBank *st = fbs_of(h);
+    if (!st || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
+    return melspec_fbank_uses_fast_path(st->fb) && st->fb->frame_shift <= st->fb->frame_len ? 1 : 0;      // fbs_supported, without its message
+}
+
+int melspec_fbank_stream_push_host_io(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out,
+                                      int out_dtype, size_t out_capacity_elems, uint32_t *frames_out) {
+    return fbs_push_host(h, ids, samples, pcm_dtype, lens, n, out, out_dtype, out_capacity_elems, frames_out);
+}
+
+int melspec_fbank_stream_push_device_io(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                        uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    return fbs_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, d_out, out_dtype, h_out_offsets, frames_out, stream);
 }
 
 int melspec_fbank_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream) {
@@ -1513,6 +1578,7 @@ struct BlmStreamBank {
     BankCore core;
     DevBuf moments, counts;              // [n_streams][2][n_mels] f64 (mean, M2), [n_streams] u64
     DevBuf stats;                        // the host stats call's buffer
+    DevBuf rows32;                       // the f32 rows of a push with 16-bit rows, packed in entry order: allocated by the first such push
 };
 
 BlmStreamBank *bls_of(void *h) {
@@ -1532,18 +1598,29 @@ int bls_supported(const melspec_blm *b) {
 
 // the frame stage behind the core's scatter: the columns, then the running statistics; the entries' tail is the clips' sample counts
 // and, behind them, their window origins
-int bls_run(BlmStreamBank *st, const BlmStreamPlan &pl, uint32_t n, const PushArgs &a) {
+// out_dtype: the row type at a.d_out.  16-bit rows: the same frame stage, planned onto the bank's f32 scratch with the plan's packed
+// offsets, and the typed twin of the statistics kernel, which reads the rows there and writes the caller's (the scratch grows before
+// anything is queued)
+int bls_run(BlmStreamBank *st, const BlmStreamPlan &pl, uint32_t n, const PushArgs &a, int out_dtype = MELSPEC_OUT_F32) {
     melspec_blm *b = st->b;
     const int nm = b->cfg.n_mels;
+    const bool typed = out_dtype != MELSPEC_OUT_F32;
     const size_t len_bytes = static_cast<size_t>(n) * sizeof(uint64_t);
-    std::vector<unsigned char> tail(len_bytes + static_cast<size_t>(n) * sizeof(int32_t));
-    std::memcpy(tail.data(), pl.len.data(), len_bytes);
-    std::memcpy(tail.data() + len_bytes, pl.org0.data(), static_cast<size_t>(n) * sizeof(int32_t));
-    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data(), tail.size(), [&](const StreamEntry *d_e, const void *d_tail) {
+    std::vector<unsigned char> own(len_bytes + static_cast<size_t>(n) * sizeof(int32_t));
+    std::memcpy(own.data(), pl.len.data(), len_bytes);
+    std::memcpy(own.data() + len_bytes, pl.org0.data(), static_cast<size_t>(n) * sizeof(int32_t));
+    TypedTail tail(own.data(), own.size(), typed ? pl.out_off.data() : nullptr, n);
+    if (typed && pl.total_frames) {
+        if (!a.d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");
+        HIP_TRY(hipSetDevice(st->core.device));
+        if (int rc = st->rows32.ensure(static_cast<size_t>(pl.total_frames) * nm * sizeof(float) + 16)) return rc;
+    }
+    float *rows = static_cast<float *>(typed ? st->rows32.p : a.d_out);
+    const uint64_t *rows_off = a.h_out_off && !typed ? a.h_out_off : pl.out_off.data();
+    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data, tail.bytes, [&](const StreamEntry *d_e, const void *d_tail) {
         BatchPlan bp;
         RaggedSlot *pslot = nullptr;
-        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), static_cast<float *>(a.d_out), pl.off.data(), pl.frames,
-                             a.h_out_off ? a.h_out_off : pl.out_off.data(), n, nm, kFbFPW, bp, pslot);
+        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), rows, pl.off.data(), pl.frames, rows_off, n, nm, kFbFPW, bp, pslot);
         if (!rc) {
             // the ragged batch of blm_ragged over the state: feature-major rows as wide as the entry's frames, every one of them valid
             FbankNemoStreamParams q{};
@@ -1559,6 +1636,13 @@ int bls_run(BlmStreamBank *st, const BlmStreamPlan &pl, uint32_t n, const PushAr
         }
         plan_ragged_done(pslot, a.stream);
         if (rc) return rc;
+        if (typed) {
+            BlmStreamStatsIoParams sp{};
+            sp.entries = d_e; sp.src_off = tail.packed_on_device(d_tail); sp.rows = rows; sp.dst = a.d_out; sp.moments = static_cast<double *>(st->moments.p);
+            sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
+            HIP_TRY(blm_stream_stats_io_launch(sp, out_dtype, n, a.stream));
+            return static_cast<int>(MELSPEC_OK);
+        }
         BlmStreamStatsParams sp{};
         sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.moments = static_cast<double *>(st->moments.p);
         sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
@@ -1580,20 +1664,44 @@ int bls_push(BlmStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint3
     return MELSPEC_OK;
 }
 
-// what every push checks first: the handle, the dtype code, the context
-int bls_push_args(BlmStreamBank *st, int pcm_dtype) {
+// what every push checks first: the handle, the dtype codes, the context
+int bls_push_args(BlmStreamBank *st, int pcm_dtype, int out_dtype) {
     if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
-    if (!io_pcm_known(pcm_dtype)) return fail(MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16");
+    int io;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     return bls_supported(st->b);
 }
 
-int bls_push_host(BlmStreamBank *st, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, bool finish, float *out,
-                  size_t out_capacity_floats, uint32_t *frames_out) {
+// melspec_blm_stream_push_host / _finish_host and their _io forms (finish: no samples, lens is not read): the rows cross the bus in their own type
+int bls_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, bool finish, void *out, int out_dtype,
+                  size_t out_capacity_elems, uint32_t *frames_out) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, pcm_dtype, out_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, finish ? "ids is NULL" : "ids/lens is NULL");
+    if (!finish && !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
     return bls_push(st, ids, lens, n, finish, frames_out, [&](const BlmStreamPlan &pl) {
-        const HostPush hp{samples, out, out_capacity_floats, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), sizeof(float)};
+        const HostPush hp{samples, out, out_capacity_elems, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), io_out_bytes(out_dtype)};
         return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
-            return bls_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s});
+            return bls_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s}, out_dtype);
         });
+    });
+}
+
+// melspec_blm_stream_push_device / _finish_device and their _io forms (finish: d_chunks NULL, MELSPEC_PCM_F32, lens is not read)
+int bls_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens, uint32_t n, bool finish,
+                    void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    BlmStreamBank *st = bls_of(h);
+    if (int rc = bls_push_args(st, pcm_dtype, out_dtype)) return rc;
+    if (n == 0) return MELSPEC_OK;
+    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, finish ? "ids is NULL" : "ids/lens is NULL");
+    if (!finish && !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
+    if (!finish && !d_chunks && pcm_dtype != MELSPEC_PCM_F32)
+        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_blm_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
+    if (io_misaligned(d_chunks, d_out, pcm_dtype | out_dtype << 4)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
+    return bls_push(st, ids, lens, n, finish, frames_out, [&](const BlmStreamPlan &pl) {
+        return bls_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
+                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream}, out_dtype);
     });
 }
 }  // namespace
@@ -1626,7 +1734,7 @@ void melspec_blm_stream_destroy(void *h) {
     BlmStreamBank *st = bls_of(h);
     if (!st) return;
     core_destroy(st->core);
-    st->moments.release(); st->counts.release(); st->stats.release();
+    st->moments.release(); st->counts.release(); st->stats.release(); st->rows32.release();
     st->magic = 0;
     delete st;
 }
@@ -1671,46 +1779,44 @@ float *melspec_blm_stream_input_ptr(void *h, uint32_t id) {
 
 int melspec_blm_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
                                  size_t out_capacity_floats, uint32_t *frames_out) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, pcm_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    return bls_push_host(st, ids, samples, pcm_dtype, lens, n, false, out, out_capacity_floats, frames_out);
+    return bls_push_host(h, ids, samples, pcm_dtype, lens, n, false, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
 }
 
 int melspec_blm_stream_finish_host(void *h, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats, uint32_t *frames_out) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, MELSPEC_PCM_F32)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
-    return bls_push_host(st, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, out_capacity_floats, frames_out);
+    return bls_push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
 }
 
 int melspec_blm_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
                                    uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, pcm_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
-        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_blm_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
-    if (io_misaligned(d_chunks, d_out, pcm_dtype))       // (the rows are f32: the out half of the code is 0)
-        return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    return bls_push(st, ids, lens, n, false, frames_out, [&](const BlmStreamPlan &pl) {
-        return bls_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
-                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream});
-    });
+    return bls_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
 }
 
 int melspec_blm_stream_finish_device(void *h, const uint32_t *ids, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, MELSPEC_PCM_F32)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
-    if (io_misaligned(nullptr, d_out, MELSPEC_PCM_F32)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    return bls_push(st, ids, nullptr, n, true, frames_out, [&](const BlmStreamPlan &pl) {
-        return bls_run(st, pl, n, PushArgs{nullptr, MELSPEC_PCM_F32, nullptr, d_out, h_out_offsets, stream ? static_cast<hipStream_t>(stream) : st->core.stream});
-    });
+    return bls_push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
+}
+
+int melspec_blm_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) {
+    const BlmStreamBank *st = bls_of(h);
+    return st && io_pcm_known(pcm_dtype) && io_out_known(out_dtype) && st->b->fast ? 1 : 0;      // bls_supported, without its message
+}
+
+int melspec_blm_stream_push_host_io(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out, int out_dtype,
+                                    size_t out_capacity_elems, uint32_t *frames_out) {
+    return bls_push_host(h, ids, samples, pcm_dtype, lens, n, false, out, out_dtype, out_capacity_elems, frames_out);
+}
+
+int melspec_blm_stream_push_device_io(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                      uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    return bls_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, out_dtype, h_out_offsets, frames_out, stream);
+}
+
+int melspec_blm_stream_finish_host_io(void *h, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems, uint32_t *frames_out) {
+    return bls_push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, out_dtype, out_capacity_elems, frames_out);
+}
+
+int melspec_blm_stream_finish_device_io(void *h, const uint32_t *ids, uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out,
+                                        void *stream) {
+    return bls_push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, out_dtype, h_out_offsets, frames_out, stream);
 }
 
 int melspec_blm_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_mean, float *d_inv_std, uint64_t *h_counts, void *stream) {

@@ -143,6 +143,13 @@ unsafe extern "C" {
                                         stream: *mut c_void) -> c_int;
     fn melspec_fbank_stream_stats_host(st: *mut c_void, ids: *const u32, n: u32, means: *mut f32, counts: *mut u64) -> c_int;
     fn melspec_fbank_stream_stats_device(st: *mut c_void, ids: *const u32, n: u32, d_means: *mut f32, h_counts: *mut u64, stream: *mut c_void) -> c_int;
+    // ... with f16 / bf16 rows out; the means stay those of the f32 rows
+    fn melspec_fbank_stream_supports_io(st: *const c_void, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_fbank_stream_push_host_io(st: *mut c_void, ids: *const u32, samples: *const c_void, pcm_dtype: c_int, lens: *const u32, n: u32,
+                                         out: *mut c_void, out_dtype: c_int, out_capacity_elems: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_fbank_stream_push_device_io(st: *mut c_void, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
+                                           lens: *const u32, n: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64,
+                                           frames_out: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 extern "C" {
@@ -165,6 +172,17 @@ extern "C" {
     fn melspec_blm_stream_stats_host(st: *mut c_void, ids: *const u32, n: u32, mean: *mut f32, inv_std: *mut f32, counts: *mut u64) -> c_int;
     fn melspec_blm_stream_stats_device(st: *mut c_void, ids: *const u32, n: u32, d_mean: *mut f32, d_inv_std: *mut f32, h_counts: *mut u64,
                                        stream: *mut c_void) -> c_int;
+    // ... with f16 / bf16 columns out; the statistics stay those of the f32 columns
+    fn melspec_blm_stream_supports_io(st: *const c_void, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_blm_stream_push_host_io(st: *mut c_void, ids: *const u32, samples: *const c_void, pcm_dtype: c_int, lens: *const u32, n: u32,
+                                       out: *mut c_void, out_dtype: c_int, out_capacity_elems: usize, frames_out: *mut u32) -> c_int;
+    fn melspec_blm_stream_push_device_io(st: *mut c_void, ids: *const u32, d_chunks: *const c_void, pcm_dtype: c_int, h_src_offsets: *const u64,
+                                         lens: *const u32, n: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64,
+                                         frames_out: *mut u32, stream: *mut c_void) -> c_int;
+    fn melspec_blm_stream_finish_host_io(st: *mut c_void, ids: *const u32, n: u32, out: *mut c_void, out_dtype: c_int, out_capacity_elems: usize,
+                                         frames_out: *mut u32) -> c_int;
+    fn melspec_blm_stream_finish_device_io(st: *mut c_void, ids: *const u32, n: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64,
+                                           frames_out: *mut u32, stream: *mut c_void) -> c_int;
 }
 
 #[repr(C)]
@@ -955,6 +973,54 @@ impl<'a> HipBatchLogMelStream<'a> {
         let id = 0u32;
         let mut frames = 0u32;
         check(melspec_blm_stream_finish_device(self.st, &id, 1, d_out, std::ptr::null(), &mut frames, stream))?;
+        Ok(frames)
+    }
+    /// Additive: f16 / bf16 columns out (`OUT_F16` / `OUT_BF16`).  `stats` stays that of the f32 columns.
+    pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_blm_stream_supports_io(self.st, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+    /// `push` on 16-bit PCM (value = sample / 32768, exactly) into columns of `out_dtype`, returned as their bit patterns, `(n_mels, k)`
+    /// row-major, with k.
+    pub fn push_s16(&mut self, samples: &[i16], out_dtype: i32) -> Result<(Vec<u16>, usize), HipError> {
+        let (id, len) = (0u32, samples.len() as u32);
+        let cap = unsafe { melspec_blm_stream_frames_after(self.st, 0, len) } * self.n_mels;
+        let mut flat = vec![0u16; cap];
+        let mut frames = 0u32;
+        check(unsafe {
+            melspec_blm_stream_push_host_io(self.st, &id, samples.as_ptr() as *const c_void, PCM_S16, &len, 1, flat.as_mut_ptr() as *mut c_void,
+                                            out_dtype as c_int, cap, &mut frames)
+        })?;
+        flat.truncate(self.n_mels * frames as usize);
+        Ok((flat, frames as usize))
+    }
+    /// `finish` into columns of `out_dtype`, as `push_s16` returns them.
+    pub fn finish_io(&mut self, out_dtype: i32) -> Result<(Vec<u16>, usize), HipError> {
+        let id = 0u32;
+        let cap = unsafe { melspec_blm_stream_finish_frames(self.st, 0) } * self.n_mels;
+        let mut flat = vec![0u16; cap];
+        let mut frames = 0u32;
+        check(unsafe { melspec_blm_stream_finish_host_io(self.st, &id, 1, flat.as_mut_ptr() as *mut c_void, out_dtype as c_int, cap, &mut frames) })?;
+        flat.truncate(self.n_mels * frames as usize);
+        Ok((flat, frames as usize))
+    }
+    /// `push_device` into `(n_mels, k)` columns of `out_dtype` at `d_out`.
+    ///
+    /// # Safety
+    /// `d_chunk` must hold `len` elements of `pcm_dtype` on the device and `d_out` room for the columns the push emits, in `out_dtype`.
+    pub unsafe fn push_device_io(&mut self, d_chunk: *const c_void, pcm_dtype: i32, len: u32, d_out: *mut c_void, out_dtype: i32,
+                                 stream: *mut c_void) -> Result<u32, HipError> {
+        let id = 0u32;
+        let mut frames = 0u32;
+        check(melspec_blm_stream_push_device_io(self.st, &id, d_chunk, pcm_dtype as c_int, std::ptr::null(), &len, 1, d_out, out_dtype as c_int,
+                                                std::ptr::null(), &mut frames, stream))?;
+        Ok(frames)
+    }
+    /// # Safety
+    /// `d_out` must have room for the columns the finish emits (`melspec_blm_stream_finish_frames`), in `out_dtype`.
+    pub unsafe fn finish_device_io(&mut self, d_out: *mut c_void, out_dtype: i32, stream: *mut c_void) -> Result<u32, HipError> {
+        let id = 0u32;
+        let mut frames = 0u32;
+        check(melspec_blm_stream_finish_device_io(self.st, &id, 1, d_out, out_dtype as c_int, std::ptr::null(), &mut frames, stream))?;
         Ok(frames)
     }
     /// # Safety

@@ -64,6 +64,16 @@ class _Bank:
         ptrs = [None if x is None else x.ctypes.data_as(C.POINTER(C.c_uint64) if x.dtype == np.uint64 else _u32p) for x in arrs]
         return np.zeros(arrs[0].shape[0], np.uint32), arrs[0].shape[0], ptrs, arrs
 
+    def _supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(self._fn("supports_io")(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def _push_device_io(self, ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream) -> np.ndarray:
+        """the typed device push of the Kaldi and the NeMo bank (FbankStreamBank / BlmStreamBank.push_device_io)"""
+        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
+        _check(self._fn("push_device_io")(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
+                                          int(out_dtype), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
     def _gather(self, ids: Sequence[int], chunks: Sequence, allow_s16: bool):
         """a push's arguments: (ids, PCM code, the chunks back to back, their lengths, rows the push will emit, a frames array to fill)"""
         a = _u32(ids)
@@ -253,6 +263,27 @@ class FbankStreamBank(_Bank):
                                                       p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
         return frames
 
+    # ---- f16 / bf16 rows out (melspec_fbank_stream_*_io): the statistics stay those of the f32 rows ----
+    def push_io(self, ids: Sequence[int], chunks: Sequence, out_dtype=None) -> List[np.ndarray]:
+        """push() whose rows have the type out_dtype names: None np.float32, "f16" (or np.float16) np.float16, "bf16" the bfloat16 bit
+        patterns as np.uint16 -- the f32 rows of push() rounded to nearest even.  stats() is what it is after the same push()es."""
+        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
+        out_code = _out_code(out_dtype)
+        out = np.empty((cap, self.n_mels), _OUT_NUMPY[out_code])
+        _check(lib().melspec_fbank_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
+                                                       a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size, frames.ctypes.data_as(_u32p)))
+        return self._collect(out, frames, cap)
+
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        """every valid pair of codes, on every Fbank a bank can be created on"""
+        return self._supports_io(pcm_dtype, out_dtype)
+
+    def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
+                       src_offsets=None, out_offsets=None, stream: int = 0) -> np.ndarray:
+        """push_device with typed rows: d_chunks / pcm_dtype / src_offsets as there; rows of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to
+        d_out + out_offsets[i] elements (None: back to back; a 16-bit entry may start at an odd element)."""
+        return self._push_device_io(ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream)
+
     def stats(self, ids: Sequence[int]):
         """(means [n, num_mel_bins] f32, counts [n] u64): mean[bin] = f32(f64 sum of the stream's emitted rows / their count), zeros for
         a stream without a row"""
@@ -331,6 +362,45 @@ class BlmStreamBank(_Bank):
     def finish_device(self, ids: Sequence[int], d_out: int, out_offsets=None, stream: int = 0) -> np.ndarray:
         frames, n, (p_ids, _p_lens, p_oo), _arrs = self._dev(ids, [0] * len(ids), out_offsets)
         _check(lib().melspec_blm_stream_finish_device(self._h, p_ids, n, C.c_void_p(d_out or None), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
+    # ---- f16 / bf16 rows out (melspec_blm_stream_*_io): the statistics stay those of the f32 rows ----
+    def push_io(self, ids: Sequence[int], chunks: Sequence, out_dtype=None) -> List[np.ndarray]:
+        """push() whose columns have the type out_dtype names: None np.float32, "f16" (or np.float16) np.float16, "bf16" the bfloat16 bit
+        patterns as np.uint16 -- the f32 columns of push() rounded to nearest even.  stats() is what it is after the same push()es."""
+        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
+        out_code = _out_code(out_dtype)
+        out = np.empty(cap * self.n_mels, _OUT_NUMPY[out_code])
+        _check(lib().melspec_blm_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
+                                                     a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size, frames.ctypes.data_as(_u32p)))
+        assert int(frames.sum()) == cap
+        return self._split(out, frames)
+
+    def finish_io(self, ids: Sequence[int], out_dtype=None) -> List[np.ndarray]:
+        """finish() whose columns have the type of push_io's out_dtype"""
+        a = _u32(ids)
+        out_code = _out_code(out_dtype)
+        cap = sum(self.finish_frames(int(s)) for s in a)
+        out, frames = np.empty(cap * self.n_mels, _OUT_NUMPY[out_code]), np.zeros(a.shape[0], np.uint32)
+        _check(lib().melspec_blm_stream_finish_host_io(self._h, a.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size,
+                                                       frames.ctypes.data_as(_u32p)))
+        return self._split(out, frames)
+
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        """every valid pair of codes, on every frontend a bank can be created on"""
+        return self._supports_io(pcm_dtype, out_dtype)
+
+    def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
+                       src_offsets=None, out_offsets=None, stream: int = 0) -> np.ndarray:
+        """push_device with typed rows: d_chunks / pcm_dtype / src_offsets as there; entry i's [n_mels, k_i] rows of out_dtype (OUT_F32 /
+        OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back; a 16-bit entry may start at an odd element)."""
+        return self._push_device_io(ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream)
+
+    def finish_device_io(self, ids: Sequence[int], d_out: int, out_dtype: int, out_offsets=None, stream: int = 0) -> np.ndarray:
+        """finish_device whose columns of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back)"""
+        frames, n, (p_ids, _p_lens, p_oo), _arrs = self._dev(ids, [0] * len(ids), out_offsets)
+        _check(lib().melspec_blm_stream_finish_device_io(self._h, p_ids, n, C.c_void_p(d_out or None), int(out_dtype), p_oo, frames.ctypes.data_as(_u32p),
+                                                         C.c_void_p(stream or None)))
         return frames
 
     def stats(self, ids: Sequence[int]):
