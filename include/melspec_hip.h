@@ -524,11 +524,33 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
  * own pass over the rows, not time inside this library.  Set the F32 mode where the call is used for speed.
  * A clip_len without a valid frame returns MELSPEC_OK and writes nothing.  Supported: the fused geometry (n_fft 512 / win_length 400)
  * with the 80- or 128-mel Slaney bank, both precision modes (melspec_blm_supports_split == 1; the condition of the 16-bit ends); every
- * other context returns MELSPEC_ERR_UNSUPPORTED, names its geometry in melspec_last_error and touches no buffer.  Uniform batches and
- * the single host clip only: no ragged form, no 16-bit ends. */
+ * other context returns MELSPEC_ERR_UNSUPPORTED, names its geometry in melspec_last_error and touches no buffer.  Uniform batches,
+ * ragged batches (below) and the single host clip; f32 samples in and f32 rows out only: no 16-bit ends. */
 int melspec_blm_supports_split(const melspec_blm *b);
 int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
                                              uint32_t n_clips, float *d_rows, float *d_mean, float *d_inv_std, void *stream);
+/* The ragged form -- clips of any length in one launch, what an ASR server has: clip c = d_pcm[h_offsets[c] .. + h_lengths[c]) ->
+ *   d_rows    [n_mels][cols_c] f32 at d_rows + h_rows_offsets[c] (floats; NULL: packed in clip order), cols_c = melspec_blm_padded_frames(len_c);
+ *   d_mean, d_inv_std  [n_clips][n_mels] f32, always packed.
+ * A clip's rows, mean and inv_std are THE BITS melspec_blm_compute_uniform_device_split gives for that clip alone in the same precision
+ * mode, whatever the clip's place in the batch, the other clips, the batch's size, the output offsets or what ran before: every clip's
+ * work is rounded up to whole rounds of the kernel's workgroup, so its blocks of 32 / 48 frames are counted from its own first frame.
+ * A clip without a valid frame (length 0, or center = 0 and fewer than n_fft samples) has no rows, and its mean / inv_std slots are left
+ * untouched; a batch without any valid frame returns MELSPEC_OK and writes nothing.  Checked in the order of
+ * melspec_blm_compute_ragged_device: NULL context, an unsupported context (as above: MELSPEC_ERR_UNSUPPORTED, the same message, no buffer
+ * touched), n_clips == 0 (OK), NULL tables, nothing to do (OK), NULL device pointers.  A batch with 2^32 blocks or more, or whose scratch
+ * (blocks * n_mels * 8 bytes) does not fit size_t, returns MELSPEC_ERR_UNSUPPORTED ("too large for the split output's plan").  Stream-
+ * ordered and asynchronous like the ragged call; the tables are read before the call returns.
+ * What it costs (1024 clips of 2-20 s, profiles/blm_split_ragged.txt; A: this call, B: melspec_blm_compute_ragged_device without
+ * normalize_per_feature, C: with it -- the call A replaces): in
+ * MELSPEC_PRECISION_F32 A takes 0.74 x (80 mels) / 0.65 x (128 mels) the time of C and 1.16 x / 1.19 x of B; in the default (f64) mode
+ * 0.96 x / 0.86 x of C and 1.37 x / 1.41 x of B.  A beats C in both modes there -- at 80 mels in f64 by 4 % only, a margin inside the
+ * spread of the timed calls -- because the ragged normaliser is dearer than the uniform one, not because the f64 kernel got faster.
+ * Not offered: int16 PCM in or 16-bit rows out for the split, a device-table (_desc) form, a ragged form of the Kaldi split
+ * (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
+int melspec_blm_compute_ragged_device_split(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                            uint32_t n_clips, float *d_rows, const uint64_t *h_rows_offsets, float *d_mean,
+                                            float *d_inv_std, void *stream);
 /* One clip from host memory: rows = [n_mels][cols] (capacity in floats), mean / inv_std = [n_mels]; *n_rows = n_mels, *n_cols = cols. */
 int melspec_blm_compute_host_split(melspec_blm *b, const float *samples, size_t n_samples, float *rows, size_t rows_capacity_floats,
                                    float *mean, float *inv_std, size_t *n_rows, size_t *n_cols);

@@ -335,6 +335,12 @@ public:
                                       float *d_mean, float *d_inv_std, void *stream = nullptr) {
         detail::check(melspec_blm_compute_uniform_device_split(b_, d_pcm, clip_stride, clip_len, n_clips, d_rows, d_mean, d_inv_std, stream), false);
     }
+    // the ragged form: clip c = d_pcm[offsets[c] .. + lengths[c]) -> rows [n_mels][cols_c] at d_rows + rows_offsets[c] (nullptr: packed in
+    // clip order), mean / inv_std [n_clips][n_mels] -- per clip the bits of the uniform call on that clip alone
+    void compute_ragged_device_split(const float *d_pcm, const std::uint64_t *offsets, const std::uint64_t *lengths, std::uint32_t n_clips, float *d_rows,
+                                     const std::uint64_t *rows_offsets, float *d_mean, float *d_inv_std, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_ragged_device_split(b_, d_pcm, offsets, lengths, n_clips, d_rows, rows_offsets, d_mean, d_inv_std, stream), false);
+    }
     struct Split {
         Array2f rows;                      // (n_mels, cols), un-normalised
         std::vector<float> mean, inv_std;  // (n_mels)

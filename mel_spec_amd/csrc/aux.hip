@@ -2,6 +2,7 @@
 // (src/stft.rs:48-86, src/rb.rs:86-121), the TGA quantiser (src/quant.rs), the VAD column stencil (src/vad.rs:373-415), synthetic PCM.
 #include "host_common.hpp"
 #include "aux_kernels.hpp"
+#include "blm_stats_plan.hpp"
 #include "stream_bank.hpp"
 #include "mel_bank.hpp"
 #include "tga_quant.hpp"
@@ -110,9 +111,12 @@ __global__ void plan_upload_kernel(const uint4 *src, uint4 *dst, size_t n16) {
 // hand out whole clips.
 int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *h_off,
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
-                int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order) {
+                int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order, uint32_t round_units) {
+    // round_units (1: as they are): every clip's units rounded up to a multiple of it -- the split output's kernels want whole rounds of
+    // their workgroup per clip (blm_stats_plan.hpp); the units past a clip's frames compute and store nothing
+    const auto units_of = [&](uint64_t fr) { return ragged_clip_units(fr, static_cast<uint32_t>(frames_per_unit), round_units); };
     uint64_t units = 0;
-    for (uint32_t c = 0; c < n_clips; ++c) units += (frames[c] + frames_per_unit - 1) / frames_per_unit;
+    for (uint32_t c = 0; c < n_clips; ++c) units += units_of(frames[c]);
     const uint64_t n_blocks = (units + kUnitBlock - 1) / kUnitBlock;
     const size_t words64 = static_cast<size_t>(n_clips) * 4 + 1;
     const size_t blk_words = static_cast<size_t>(n_blocks ? n_blocks : 1);
@@ -128,7 +132,7 @@ int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float
         oo[c] = h_out_off ? h_out_off[c] : out_cursor;
         out_cursor += frames[c] * static_cast<uint64_t>(n_mels);
         pre[c] = cursor;
-        cursor += (frames[c] + frames_per_unit - 1) / frames_per_unit;
+        cursor += units_of(frames[c]);
         total += frames[c];
     }
     pre[n_clips] = units;

@@ -5,6 +5,7 @@
 #include "fbank512_io_kernels.hpp"
 #include "fbank512_kaldi_io_kernels.hpp"
 #include "fbank512_stats_kernels.hpp"
+#include "fbank512_stats_ragged_kernels.hpp"
 #include "fbank512_stream_kernels.hpp"
 #include "fbank512_nemo_stream_kernels.hpp"
 #include "stream_banks_io_kernels.hpp"
@@ -28,6 +29,10 @@ extern template __global__ void cmn_io_kernel<io_bf16>(const CmnIoParams);
 #define MS_STATS_EXTERN(name, T, W, N, L) extern template __global__ void fbank512_nemo_stats_kernel<T, W, N, L>(const FbankStatsParams);
 MS_K512_STATS(MS_STATS_EXTERN)
 #undef MS_STATS_EXTERN
+// emitted by fbank512_stats_ragged.hip: the ragged form of the split output, one kernel per kernel of the list above
+#define MS_STATS_RAGGED_EXTERN(name, T, W, N, L) extern template __global__ void fbank512_nemo_stats_ragged_kernel<T, W, N, L>(const FbankStatsRaggedParams);
+MS_K512_STATS(MS_STATS_RAGGED_EXTERN)
+#undef MS_STATS_RAGGED_EXTERN
 // emitted by fbank512_stream.hip: the Kaldi fbank's stream bank (the plain kernels with a "continues" flag per clip)
 #define MS_STREAM_EXTERN(name, T, W, N, L, R) extern template __global__ void fbank512_stream_kernel<T, W, N, L, R>(const FbankStreamParams);
 MS_K512_STREAM(MS_STREAM_EXTERN)
@@ -51,17 +56,20 @@ MS_K512_WAVE(MS_WAVE)
 #define MS_IO(name, In, Out, fam, T, W, N, L) &fbank512_##fam##_io_kernel<T, W, N, L, In, Out>,
 #define MS_CLIP(name, N, L, R) &fbank512_clip_kernel<N, L, R>,
 #define MS_STATS(name, T, W, N, L) &fbank512_nemo_stats_kernel<T, W, N, L>,
+#define MS_STATS_RAGGED(name, T, W, N, L) &fbank512_nemo_stats_ragged_kernel<T, W, N, L>,
 #define MS_AUTO(name, T, W, N, L) &w512_auto_kernel<T, W, N, L>,
 #define MS_STREAM(name, T, W, N, L, R) &fbank512_stream_kernel<T, W, N, L, R>,
 void (*const kFastKernels[])(const FbankFastParams) = {MS_K512_WAVE(MS_WAVE) MS_K512_IO(MS_IO)};
 void (*const kClipKernels[])(const FbankClipParams) = {MS_K512_CLIP(MS_CLIP)};
 void (*const kStatsKernels[])(const FbankStatsParams) = {MS_K512_STATS(MS_STATS)};
+void (*const kStatsRaggedKernels[])(const FbankStatsRaggedParams) = {MS_K512_STATS(MS_STATS_RAGGED)};       // keyed by the uniform call's kernel: same launch shape, same LDS
 void (*const kAutoKernels[])(const W512AutoParams) = {MS_K512_AUTO(MS_AUTO)};
 void (*const kStreamKernels[])(const FbankStreamParams) = {MS_K512_STREAM(MS_STREAM)};
 #undef MS_WAVE
 #undef MS_IO
 #undef MS_CLIP
 #undef MS_STATS
+#undef MS_STATS_RAGGED
 #undef MS_AUTO
 #undef MS_STREAM
 constexpr int idx(K512 k) { return static_cast<int>(k); }
@@ -75,6 +83,7 @@ static_assert(kFused512F32Waves == 12, "fused512_route.hpp spells the f32 kernel
 inline auto kernel512(K512 k, const FbankFastParams &) { return is_fast(k) ? kFastKernels[idx(k)] : nullptr; }
 inline auto kernel512(K512 k, const FbankClipParams &) { return is_clip(k) ? kClipKernels[idx(k) - idx(K512::kClip80)] : nullptr; }
 inline auto kernel512(K512 k, const FbankStatsParams &) { return is_stats(k) ? kStatsKernels[idx(k) - idx(K512::kStats128)] : nullptr; }
+inline auto kernel512(K512 k, const FbankStatsRaggedParams &) { return is_stats(k) ? kStatsRaggedKernels[idx(k) - idx(K512::kStats128)] : nullptr; }
 inline auto kernel512(K512 k, const W512AutoParams &) { return is_auto(k) ? kAutoKernels[idx(k) - idx(K512::kAuto80Vote)] : nullptr; }
 inline auto kernel512(K512 k, const FbankStreamParams &) { return is_stream(k) ? kStreamKernels[idx(k) - idx(K512::kStream80)] : nullptr; }
 // the NeMo stream bank's kernels have a table of their own, keyed by the kernel a batch of the object runs on: same launch shape, same LDS
@@ -107,6 +116,7 @@ const char *attr_name(K512 k) {
                     : "hipFuncSetAttribute(fbank512_wave_kernel, 8 / 4 waves)";
 }
 template <class P> const char *attr_name(K512 k, const P &) { return attr_name(k); }
+const char *attr_name(K512, const FbankStatsRaggedParams &) { return "hipFuncSetAttribute(fbank512_nemo_stats_ragged_kernel)"; }
 const char *attr_name(K512, const FbankNemoStreamParams &) { return "hipFuncSetAttribute(fbank512_nemo_stream_kernel)"; }
 // one launch of a route with the parameters of its kernel's group; z: the object's LDS sizes
 template <class P>
@@ -1079,6 +1089,13 @@ static bool blm_stats_ok(const melspec_blm *b) {
     return stats_ok(shape) && lds512(route512(shape, Batch512::kStats).run.lds, blm_lds(b)) <= kLdsLimit;
 }
 
+// the unsupported context's message, which names its geometry
+static std::string blm_stats_unsupported(const melspec_blm *b) {
+    return "the split output (rows + per-feature mean and 1 / std) is computed by the n_fft = 512 / win_length = 400 frontend with the 80- or 128-mel Slaney bank only; "
+           "this context is n_fft = " + std::to_string(b->cfg.n_fft) + ", win_length = " + std::to_string(b->cfg.win_length) + ", n_mels = " +
+           std::to_string(b->cfg.n_mels) + (b->fast ? " (another filterbank)" : "");
+}
+
 int melspec_blm_supports_split(const melspec_blm *b) { return b && blm_stats_ok(b) ? 1 : 0; }
 
 int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
@@ -1088,9 +1105,7 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
     if (a.verdict == kBlmStatsDone) return MELSPEC_OK;
     if (a.verdict == kBlmStatsFail) {
         if (a.msg) return fail(a.status, a.msg);
-        g_last_error = "the split output (rows + per-feature mean and 1 / std) is computed by the n_fft = 512 / win_length = 400 frontend with the 80- or 128-mel Slaney bank only; "
-                       "this context is n_fft = " + std::to_string(b->cfg.n_fft) + ", win_length = " + std::to_string(b->cfg.win_length) + ", n_mels = " +
-                       std::to_string(b->cfg.n_mels) + (b->fast ? " (another filterbank)" : "");
+        g_last_error = blm_stats_unsupported(b);
         return a.status;
     }
     const int nm = b->cfg.n_mels;
@@ -1120,6 +1135,72 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
     hipLaunchKernelGGL(blm_stats_finish_kernel, dim3(grid_for((rows + kBlmStatsFinishThreads - 1) / kBlmStatsFinishThreads, b->dev.cus, 8)), dim3(kBlmStatsFinishThreads), 0, s, fq);
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
+}
+
+// The ragged form: clip c = d_pcm[h_offsets[c] .. + h_lengths[c]) -> rows [n_mels][cols_c] at d_rows + h_rows_offsets[c] (NULL: packed in
+// clip order) and mean / inv_std at [c][n_mels] -- the bits of the call above for that clip alone.  The batch is blm_ragged's raw batch
+// with every clip's units rounded up to whole rounds of the workgroup (blm_stats_plan_ragged says what rests on that).
+int melspec_blm_compute_ragged_device_split(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
+                                            float *d_rows, const uint64_t *h_rows_offsets, float *d_mean, float *d_inv_std, void *stream) {
+    const bool ok = b && blm_stats_ok(b);
+    // lengths, valid frames (the kernels' d_len / d_valid); the clips' columns
+    std::vector<uint64_t> cols, aux;
+    uint64_t most = 0;
+    if (ok && n_clips && h_offsets && h_lengths) {
+        cols.resize(n_clips);
+        aux.resize(2 * static_cast<size_t>(n_clips));
+        for (uint32_t i = 0; i < n_clips; ++i) {
+            const uint64_t valid = blm_valid_frames(b, h_lengths[i]);
+            cols[i] = blm_padded(b, valid);
+            aux[i] = h_lengths[i];
+            aux[n_clips + i] = valid;
+            most = std::max(most, cols[i]);
+        }
+    }
+    const BlmStatsArgs a = blm_stats_ragged_args(b != nullptr, ok, n_clips, h_offsets, h_lengths, most, d_pcm, d_rows, d_mean, d_inv_std);
+    if (a.verdict == kBlmStatsDone) return MELSPEC_OK;
+    if (a.verdict == kBlmStatsFail) {
+        if (a.msg) return fail(a.status, a.msg);
+        g_last_error = blm_stats_unsupported(b);
+        return a.status;
+    }
+    const int nm = b->cfg.n_mels;
+    const Route512 r = route512(blm_shape(b), Batch512::kStats);
+    BlmStatsRaggedPlan sp;
+    if (!blm_stats_plan_ragged(cols.data(), n_clips, nm, info_of(r.run.kernel).f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
+    int rc;
+    if ((rc = b->stats.ensure(static_cast<size_t>(sp.part_bytes) + 16, s))) return rc;
+    if ((rc = b->aux.ensure(aux.size() * sizeof(uint64_t), s))) return rc;
+    const uint64_t *d_aux = static_cast<const uint64_t *>(b->aux.p());
+    HIP_TRY(hipMemcpyAsync(b->aux.p(), aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    rc = plan_ragged(b->ragged, s, d_pcm, d_rows, h_offsets, cols, h_rows_offsets, n_clips, nm, kFbFPW, pl, slot, false, sp.waves);
+    // the kernels' waits count on whole rounds: a plan that disagrees with blm_stats_plan_ragged is not launched
+    if (!rc && pl.desc.n_units != sp.n_units) rc = fail(MELSPEC_ERR_INTERNAL, "the split output's ragged plan and its batch plan disagree");
+    if (!rc) {
+        FbankStatsRaggedParams q{};
+        q.f = blm_fast_params(b, pl.desc);
+        q.f.b.mel_major = 1;
+        q.f.b.sync_rounds = kNemoSync;          // as the raw call (f32: the route's StagedRows)
+        apply_route(r, q.f, b->f32);
+        q.f.d_len = d_aux;
+        q.f.d_valid = d_aux + n_clips;
+        q.d_part = static_cast<float2 *>(b->stats.p());
+        rc = launch512(r.run, q, blm_lds(b), b->dev.cus, s);
+        if (!rc) {
+            BlmStatsFinishRaggedParams fq{};
+            fq.part = q.d_part; fq.mean = d_mean; fq.inv_std = d_inv_std; fq.d_valid = q.f.d_valid; fq.d_unit_prefix = pl.desc.d_unit_prefix;
+            fq.n_clips = n_clips; fq.waves = sp.waves; fq.block_frames = sp.block_frames; fq.n_mels = nm;
+            const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+            hipLaunchKernelGGL(blm_stats_finish_ragged_kernel, dim3(grid_for((rows + kBlmStatsFinishThreads - 1) / kBlmStatsFinishThreads, b->dev.cus, 8)), dim3(kBlmStatsFinishThreads), 0, s, fq);
+            if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_stats_finish_ragged_kernel launch failed");
+        }
+    }
+    plan_ragged_done(slot, s);
+    return rc;
 }
 
 // One clip from host memory; the rows and the two statistics share the context's device-to-host buffer.

@@ -3,6 +3,9 @@
 // flavour) and fbank512_kaldi_io_kernel (fbank512_kaldi_io_kernels.hpp: the same ends, Kaldi flavour).  The including kernel provides T, WAVES, FLAVOR, NSLOTS, Lens, RUNS and the parameter p.
 // MS_FB512_STATS (fbank512_nemo_stats_kernel, fbank512_stats_kernels.hpp: NeMo flavour, parameter q around p): the per-block partials of the
 // split output next to the rows; without the macro the text below is what it always was.
+// MS_FB512_STATS_RAGGED (on top of MS_FB512_STATS: fbank512_nemo_stats_ragged_kernel, fbank512_stats_ragged_kernels.hpp): the batch is a ragged
+// one whose clips' unit counts are each a multiple of WAVES, the partials lie at [round of the batch][mel] and a block's valid frames come
+// from the clip's own count; without the macro the text below is what it always was.
 // MS_FB512_CONTINUES (fbank512_stream_kernel, fbank512_stream_kernels.hpp: Kaldi flavour, parameter q around p): q.d_cont[clip] != 0 says
 // that the clip continues a stream -- the sample in front of its first frame exists and is that frame's predecessor (src/fbank.rs:177-181);
 // without the macro the text below is what it always was.
@@ -54,6 +57,14 @@
     using SStats = StagedStats<STAGE ? WAVES : 4>;
     // the round's block of the batch, clip * blocks_per_clip + block = first / WAVES (the plan keeps it in 32 bits): counted, not divided
     uint32_t sblock = xcd_logical_block();
+#ifdef MS_FB512_STATS_RAGGED
+    // the partials of the round before this one: that round's block is its index among the batch's rounds, and its valid frames are what
+    // the wave noted when it was in that round (another clip's, as often as not) -- one scalar, the kernel has no VGPR left
+    int sn_prev = 0;
+    auto sreduce = [&](unsigned r, int t) __attribute__((always_inline)) {
+        SStats::reduce(staged, r, t, q.d_part + (uint64_t)(sblock - gridDim.x) * (uint64_t)p.n_mels, sn_prev);
+    };
+#else
     // the partials of the round before this one (its image has just been drained)
     auto sreduce = [&](unsigned r, int t) __attribute__((always_inline)) {
         const uint32_t sprev = sblock - gridDim.x, blk = sprev % q.blocks_per_clip;
@@ -61,6 +72,7 @@
         const int n = vf > bf0 ? (vf - bf0 < (uint64_t)(WAVES * kFbFPW) ? (int)(vf - bf0) : WAVES * kFbFPW) : 0;
         SStats::reduce(staged, r, t, q.d_part + (uint64_t)sprev * (uint64_t)p.n_mels, n);
     };
+#endif
     RoundStats<WAVES> rstats(arrive + 16, arrive + 8, p.n_mels);
 #endif
     // batches planned on the device (plan_ragged_device_kernel) keep the real unit count in d_n_units; n_units is the host's bound
@@ -155,10 +167,16 @@
             const uint64_t wleft = (have && f0 < row_w) ? row_w - f0 : 0;      // the clip's units are rounded up to whole rounds: some lie past the row
             // the round's block (computed where it is used, by the one wave that uses it): WAVES units from unit blk * WAVES of the clip on,
             // nb valid frames, its partials at pdst
+#ifdef MS_FB512_STATS_RAGGED
+            // (every clip in front of this one has whole rounds: unit_prefix[clip] / WAVES + blk = first / WAVES, which sblock counts)
+#define MS_FB512_STATS_BLOCK_INDEX (uint64_t)sblock
+#else
+#define MS_FB512_STATS_BLOCK_INDEX ((uint64_t)loc.clip * q.blocks_per_clip + blk)
+#endif
 #define MS_FB512_STATS_BLOCK                                                                                                             \
             const uint64_t blk = loc.unit / WAVES, bf0 = blk * (WAVES * kFbFPW);                                                         \
             const int nb = vframes > bf0 ? (vframes - bf0 < (uint64_t)(WAVES * kFbFPW) ? (int)(vframes - bf0) : WAVES * kFbFPW) : 0;     \
-            float2 *const pdst = q.d_part + ((uint64_t)loc.clip * q.blocks_per_clip + blk) * (uint64_t)p.n_mels;
+            float2 *const pdst = q.d_part + MS_FB512_STATS_BLOCK_INDEX * (uint64_t)p.n_mels;
 #else
             const uint64_t wleft = have ? row_w - f0 : 0;
 #endif
@@ -179,6 +197,13 @@
                     staged.drain(staged.round - 1, dtid);
                     sreduce(staged.round - 1, dtid);
                 }
+#ifdef MS_FB512_STATS_RAGGED
+                {
+                    // this round's block for the next iteration: the round's first unit is this wave's less its slot
+                    const uint64_t bf0 = (loc.unit - (uint64_t)rs.slot) * kFbFPW;
+                    sn_prev = __builtin_amdgcn_readfirstlane(vframes > bf0 ? (vframes - bf0 < (uint64_t)(WAVES * kFbFPW) ? (int)(vframes - bf0) : WAVES * kFbFPW) : 0);
+                }
+#endif
                 staged.publish(lane);
 #else
                 if (staged.round > 0) {
@@ -225,6 +250,7 @@
         }
 #ifdef MS_FB512_STATS
 #undef MS_FB512_STATS_BLOCK
+#undef MS_FB512_STATS_BLOCK_INDEX
 #endif
         __builtin_amdgcn_wave_barrier();
         if (ROUNDS) rs.after_round();

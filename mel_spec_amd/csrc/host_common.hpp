@@ -311,7 +311,7 @@ inline bool is_layout(const BatchDesc &b) { return b.mel_major || b.out_width !=
 // Fills the next slot and queues its upload on `stream`.  The caller launches on `stream` and then calls plan_ragged_done.  (aux.hip)
 int plan_ragged(RaggedScratch &rs, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *h_off,
                 const std::vector<uint64_t> &frames, const uint64_t *h_out_off, uint32_t n_clips, int n_mels,
-                int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order = false);
+                int frames_per_unit, BatchPlan &pl, RaggedSlot *&used, bool want_order = false, uint32_t round_units = 1);
 void plan_ragged_done(RaggedSlot *sl, hipStream_t stream);
 // a table on its way to the device through a ring slot (plan_ragged, the stream banks' entries), and the launches of the banks' scatter /
 // carry kernels (aux_kernels.hpp): the one launch site of each, behind stream_bank.hpp's core_run  (aux.hip)

@@ -734,6 +734,37 @@ class BatchLogMelSpectrogram(_Frontend):
         return self._compute_many(clips)
 
 
+# -- the split output's ragged form (melspec_blm_compute_ragged_device_split): module-level, the frontend's attributes being a pinned set ----
+def blm_compute_ragged_device_split(fe: BatchLogMelSpectrogram, d_pcm: int, offsets, lengths, d_rows: int, d_mean: int, d_inv_std: int,
+                                    rows_offsets=None, stream: int = 0) -> None:
+    """clip i = d_pcm[offsets[i] : + lengths[i]] -> its un-normalised rows [n_mels][padded_frames(lengths[i])] at d_rows + rows_offsets[i]
+    floats (None = packed in clip order), d_mean / d_inv_std = [n_clips][n_mels]: per clip the bits of compute_uniform_device_split on
+    that clip alone.  A clip without a valid frame has no rows and its two statistics slots stay as they were.  Asynchronous on `stream`."""
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_blm_compute_ragged_device_split(fe._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0], C.c_void_p(d_rows), p_out,
+                                                         C.c_void_p(d_mean), C.c_void_p(d_inv_std), C.c_void_p(stream)))
+
+
+def blm_compute_ragged_split(fe: BatchLogMelSpectrogram, clips) -> list:
+    """list of 1-D host arrays of any lengths -> list of (rows (n_mels, cols), mean (n_mels,), inv_std (n_mels,)), one launch; a clip
+    without a valid frame gives (zeros((n_mels, 0)), None, None)"""
+    flat, offs, lens = _flatten(clips)
+    shapes, total = fe._packed(lens)
+    nm, n = fe.config.n_mels, len(shapes)
+    if n == 0:
+        return []
+    din, drows, dstat = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * 4, 16)), DeviceBuffer(2 * n * nm * 4)
+    try:
+        din.upload(flat)
+        blm_compute_ragged_device_split(fe, din.ptr, offs, lens, drows.ptr, dstat.ptr, dstat.ptr + n * nm * 4)
+        fe.synchronize()
+        rows = _split(drows.download((max(total, 1),))[:total], shapes)
+        stat = dstat.download((2, n, nm))
+    finally:
+        din.free(); drows.free(); dstat.free()
+    return [(r, stat[0, i].copy(), stat[1, i].copy()) if r.shape[1] else (r, None, None) for i, r in enumerate(rows)]
+
+
 class SparseMelFilterbank:
     """SparseMelFilterbank (src/mel.rs:40-168) + log_mel_spectrogram / norm_mel / norm_mel_vec (:436-469) on the GPU (melspec_bank_*)."""
 

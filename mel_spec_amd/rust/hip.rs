@@ -89,6 +89,9 @@ unsafe extern "C" {
     fn melspec_blm_supports_split(b: *const BlmHandle) -> c_int;
     fn melspec_blm_compute_uniform_device_split(b: *mut BlmHandle, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, d_rows: *mut f32,
                                                 d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_ragged_device_split(b: *mut BlmHandle, d_pcm: *const f32, h_offsets: *const u64, h_lengths: *const u64, n_clips: u32,
+                                               d_rows: *mut f32, h_rows_offsets: *const u64, d_mean: *mut f32, d_inv_std: *mut f32,
+                                               stream: *mut c_void) -> c_int;
     fn melspec_blm_compute_host_split(b: *mut BlmHandle, samples: *const f32, n_samples: usize, rows: *mut f32, rows_capacity_floats: usize,
                                       mean: *mut f32, inv_std: *mut f32, n_rows: *mut usize, n_cols: *mut usize) -> c_int;
     fn melspec_blm_supports_io(b: *const BlmHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
@@ -815,6 +818,24 @@ impl HipBatchLogMel {
     pub unsafe fn compute_uniform_device_split(&mut self, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, d_rows: *mut f32,
                                                d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
         check(melspec_blm_compute_uniform_device_split(self.b, d_pcm, clip_stride, clip_len, n_clips, d_rows, d_mean, d_inv_std, stream))
+    }
+    /// Additive: clips of any length resident in device memory, clip `c` = `d_pcm[offsets[c] .. + lengths[c])` -> un-normalised rows
+    /// `[n_mels][cols_c]` at `d_rows + rows_offsets[c]` (`None`: packed in clip order) plus `[n_clips][n_mels]` means and inverse standard
+    /// deviations -- per clip the bits `compute_uniform_device_split` gives for that clip alone.  A clip without a valid frame has no rows
+    /// and its two statistics slots are left untouched.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`; `d_rows` must hold every clip's `n_mels * cols_c` floats where the offsets put
+    /// them, `d_mean` and `d_inv_std` `offsets.len() * n_mels` floats each.
+    pub unsafe fn compute_ragged_device_split(&mut self, d_pcm: *const f32, offsets: &[u64], lengths: &[u64], d_rows: *mut f32,
+                                              rows_offsets: Option<&[u64]>, d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void)
+                                              -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        if let Some(o) = rows_offsets {
+            assert_eq!(o.len(), offsets.len());
+        }
+        check(melspec_blm_compute_ragged_device_split(self.b, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_rows,
+                                                      rows_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), d_mean, d_inv_std, stream))
     }
     /// Additive: `compute` without the normaliser's pass: `(rows (n_mels, cols), mean, inv_std)` of one host clip.
     pub fn compute_split(&mut self, samples: &[f32]) -> Result<(ndarray::Array2<f32>, Vec<f32>, Vec<f32>), HipError> {
