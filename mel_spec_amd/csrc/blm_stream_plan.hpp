@@ -1,6 +1,8 @@
 // blm_stream_plan.hpp -- host bookkeeping of the NeMo / Parakeet frontend's stream bank (plain C++, no HIP): which columns of
 // BatchLogMelSpectrogram::compute (compute_flat_with_scratch, num_frames, prepare_padded_waveform, apply_preemphasis in src/mel.rs) a push
-// completes and where their samples start in the bank's state.  Shared by fbank512.hip and tests/cpp/blm_stream_host.cpp.
+// completes and where their samples start in the bank's state.  Shared by fbank512.hip (the NeMo traits of stat_bank.hpp's StatBank, which
+// is the bank around this planner) and tests/cpp/blm_stream_host.cpp.  The plan's `len` and `org0` go to the device as the bank's own tail
+// (stat_bank_tail.hpp).
 //
 // Frame k of a clip reads the 400 window taps from sample k * hop + org0 on (org0 = -200 centred: the window sits in the middle of the
 // 512-point frame whose centre is sample k * hop; +56 otherwise) and, for the pre-emphasis of its first tap, the sample in front of them.

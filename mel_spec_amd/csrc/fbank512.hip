@@ -12,7 +12,7 @@
 #include "blm_stats_plan.hpp"
 #include "blm_stream_plan.hpp"
 #include "fbank_stream_plan.hpp"
-#include "stream_bank.hpp"
+#include "stat_bank.hpp"
 
 namespace melspec {
 // emitted by fbank512_io.hip / fbank512_kaldi_io.hip: the NeMo frontend and the Kaldi fbank with int16 PCM in and / or f16, bf16 rows out
@@ -1359,590 +1359,220 @@ int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pc
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------
-// Kaldi fbank: the stream bank (melspec_fbank_stream_*): see include/melspec_hip.h.  Bookkeeping in fbank_stream_plan.hpp, kernels in
-// fbank512_stream_kernels.hpp; everything a bank of live streams is besides its planner and its frame stage in stream_bank.hpp.
+// The stream banks of the two objects (melspec_fbank_stream_*, melspec_blm_stream_*): see include/melspec_hip.h.  The bank itself is
+// written once, in stat_bank.hpp (StatBank<B> over stream_bank.hpp's core).  Here: the two sets of traits -- what a bank reads of its
+// object, its planner (fbank_stream_plan.hpp / blm_stream_plan.hpp), its own tail (stat_bank_tail.hpp), its frame stage and the kernels
+// behind it (fbank512_stream_kernels.hpp / fbank512_nemo_stream_kernels.hpp, stream_banks_io_kernels.hpp) -- and the ABI's forwards.
 // ------------------------------------------------------------------------------------
 namespace {
-constexpr uint32_t kFbankStreamMagic = 0x4b53424du;      // the handle crosses the ABI as void *: every call checks what it was given
+struct KaldiStream;
+struct NemoStream;
+using FbankStreamBank = StatBank<KaldiStream>;
+using BlmStreamBank = StatBank<NemoStream>;
 
-struct FbankStreamBank {
-    uint32_t magic = kFbankStreamMagic;
-    melspec_fbank *fb = nullptr;         // geometry, tables, kernels; not owned
-    FbankStreamGeom geom{};
-    FbankStreamBook book;                // total / emitted / pending per stream (host side of the state)
-    BankCore core;
-    DevBuf sums, counts;                 // [n_streams][bins] f64, [n_streams] u64
-    DevBuf means;                        // the host stats call's buffer
-    DevBuf rows32;                       // the f32 rows of a push with 16-bit rows, packed in entry order: allocated by the first such push
+// Kaldi fbank: rows before CMN and their f64 column sums; the entries' tail is the clips' continues flags
+struct KaldiStream {
+    using Owner = melspec_fbank;
+    using Geom = FbankStreamGeom;
+    using Book = FbankStreamBook;            // total / emitted / pending per stream
+    using Plan = FbankStreamPlan;
+    static constexpr uint32_t kMagic = 0x4b53424du;
+    static constexpr int kAccWords = 1, kStats = 1;          // sum; means
+    static constexpr const char *kBankNull = "fbank stream bank is NULL", *kOwnerNull = "fbank is NULL", *kStatsDeviceNull = "d_means is NULL", *kStatsHostNull = "means is NULL",
+                                *kChunksNull = "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)";
+
+    // the objects a bank can stand on: the fused 512-point path (every kernel of MS_K512_STREAM), frames that overlap or abut
+    static bool ok(const Owner *fb) { return melspec_fbank_uses_fast_path(fb) && fb->frame_shift <= fb->frame_len; }
+    static int supported(const Owner *fb) {
+        if (ok(fb)) return MELSPEC_OK;
+        char geo[256];
+        std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d", fb->cfg.sample_rate,
+                      fb->frame_len, fb->frame_shift, fb->cfg.num_mel_bins);
+        g_last_error = std::string("the fbank stream bank runs on the fused fbank path (400-sample frames) with frame_shift <= frame_length; this object is ") + geo +
+                       (fb->use_generic ? " on the generic path (melspec_fbank_use_generic)" : (fb->fast ? "" : " (generic path)"));
+        return MELSPEC_ERR_UNSUPPORTED;
+    }
+    static Geom geometry(const Owner *fb, uint32_t n_streams, uint32_t max_chunk) {
+        return fbank_stream_geometry(static_cast<uint32_t>(fb->frame_len), static_cast<uint32_t>(fb->frame_shift), static_cast<uint32_t>(fb->cfg.num_mel_bins), n_streams, max_chunk);
+    }
+    // the reference drops a stream's tail: nothing to finish, and no entry point says so
+    static int plan(const Geom &g, Book &bk, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool, Plan &pl, const char **err) {
+        return fbank_stream_plan_push(g, bk, ids, lens, n, pl, err);
+    }
+    static void commit(const Geom &g, Book &bk, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool) { fbank_stream_commit_push(g, bk, ids, lens, n); }
+    static size_t frames_after(const Geom &g, const Book &bk, uint32_t id, uint32_t n_new) { return fbank_stream_frames_after(g, bk, id, n_new); }
+    static std::vector<unsigned char> own_tail(const Plan &pl, uint32_t n) { return fbank_stream_own_tail(pl.continues.data(), n); }
+
+    static int frames(const FbankStreamBank &st, const BatchPlan &bp, const void *d_tail, uint32_t, hipStream_t s) {
+        melspec_fbank *fb = st.owner;
+        FbankStreamParams q{};
+        q.f = fbank_fast_params(fb, bp.desc);
+        q.d_cont = static_cast<const uint32_t *>(d_tail);
+        return launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, fb->cfg.num_mel_bins}, fb->dev.cus, s);
+    }
+    static hipError_t fold(const FbankStreamBank &st, const StreamEntry *d_e, const uint64_t *src_off, const float *rows, void *dst, int out_dtype, uint32_t n, hipStream_t s) {
+        double *sums = static_cast<double *>(st.acc.p);
+        unsigned long long *counts = static_cast<unsigned long long *>(st.counts.p);
+        const int nm = static_cast<int>(st.geom.n_mels);
+        if (src_off) return fbank_stream_sum_io_launch(FbankStreamSumIoParams{d_e, src_off, rows, dst, sums, counts, nm}, out_dtype, n, s);
+        const FbankStreamSumParams sp{d_e, rows, sums, counts, nm};
+        hipLaunchKernelGGL(fbank_stream_sum_kernel, dim3(n), dim3(kFbankStreamSumThreads), 0, s, sp);
+        return hipGetLastError();
+    }
+    static void read_out(const FbankStreamBank &st, const uint32_t *d_ids, uint32_t n, float *const *out, hipStream_t s) {
+        const FbankStreamMeanParams mp{d_ids, static_cast<const double *>(st.acc.p), static_cast<const unsigned long long *>(st.counts.p), out[0], n, static_cast<int>(st.geom.n_mels)};
+        hipLaunchKernelGGL(fbank_stream_mean_kernel, st.stats_grid(n, kFbankStreamSumThreads), dim3(kFbankStreamSumThreads), 0, s, mp);
+    }
 };
 
-// The table that travels behind a push's entries (core_run's tail).  An f32 push: the bank's own table as it is.  A push with 16-bit rows
-// (stream_banks_io_kernels.hpp): the fold behind the frame stage needs each entry's place in the bank's f32 scratch beside its place in the
-// caller's rows (the entries' out_off), so the plan's packed offsets follow the bank's table, 8-byte aligned.
-struct TypedTail {
-    std::vector<unsigned char> joined;
-    const void *data;
-    size_t bytes, packed_at = 0;
-    TypedTail(const void *own, size_t own_bytes, const uint64_t *packed_off, uint32_t n) : data(own), bytes(own_bytes) {
-        if (!packed_off) return;
-        packed_at = (own_bytes + 7) & ~static_cast<size_t>(7);
-        joined.resize(packed_at + static_cast<size_t>(n) * sizeof(uint64_t));
-        std::memcpy(joined.data(), own, own_bytes);
-        std::memcpy(joined.data() + packed_at, packed_off, static_cast<size_t>(n) * sizeof(uint64_t));
-        data = joined.data(); bytes = joined.size();
+// NeMo / Parakeet frontend: feature-major columns and their f64 Welford moments; the entries' tail is the clips' sample counts and,
+// behind them, their window origins
+struct NemoStream {
+    using Owner = melspec_blm;               // with its precision mode
+    using Geom = BlmStreamGeom;
+    using Book = BlmStreamBook;              // total / emitted / ended per stream
+    using Plan = BlmStreamPlan;
+    static constexpr uint32_t kMagic = 0x4d4c424eu;
+    static constexpr int kAccWords = 2, kStats = 2;          // mean, M2; mean, 1 / std
+    static constexpr const char *kBankNull = "blm stream bank is NULL", *kOwnerNull = "blm is NULL", *kStatsDeviceNull = "d_mean / d_inv_std is NULL",
+                                *kStatsHostNull = "mean / inv_std is NULL",
+                                *kChunksNull = "d_chunks is NULL: the chunks are at melspec_blm_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)";
+
+    // the contexts a bank can stand on: the fused 512-point path (every kernel of MS_K512_NEMO_STREAM)
+    static bool ok(const Owner *b) { return b->fast; }
+    static int supported(const Owner *b) {
+        if (ok(b)) return MELSPEC_OK;
+        g_last_error = "the log-mel stream bank runs on the fused kernels (n_fft = 512, win_length = 400); this context is n_fft = " + std::to_string(b->cfg.n_fft) +
+                       ", win_length = " + std::to_string(b->cfg.win_length) + ", hop_length = " + std::to_string(b->cfg.hop_length) + ", n_mels = " + std::to_string(b->cfg.n_mels) +
+                       (b->cfg.n_fft == 512 && b->cfg.win_length == 400 ? " (a filterbank the fused kernels do not hold)" : "");
+        return MELSPEC_ERR_UNSUPPORTED;
     }
-    const uint64_t *packed_on_device(const void *d_tail) const { return reinterpret_cast<const uint64_t *>(static_cast<const char *>(d_tail) + packed_at); }
+    static Geom geometry(const Owner *b, uint32_t n_streams, uint32_t max_chunk) {
+        return blm_stream_geometry(static_cast<uint32_t>(b->cfg.hop_length), b->cfg.center != 0, static_cast<uint32_t>(b->cfg.n_mels), n_streams, max_chunk);
+    }
+    static int plan(const Geom &g, Book &bk, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool finish, Plan &pl, const char **err) {
+        return blm_stream_plan_push(g, bk, ids, lens, n, finish, pl, err);
+    }
+    static void commit(const Geom &g, Book &bk, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool finish) { blm_stream_commit_push(g, bk, ids, lens, n, finish); }
+    static size_t frames_after(const Geom &g, const Book &bk, uint32_t id, uint32_t n_new) { return blm_stream_frames_after(g, bk, id, n_new); }
+    static std::vector<unsigned char> own_tail(const Plan &pl, uint32_t n) { return blm_stream_own_tail(pl.len.data(), pl.org0.data(), n); }
+
+    // the ragged batch of blm_ragged over the state: feature-major rows as wide as the entry's frames, every one of them valid
+    static int frames(const BlmStreamBank &st, const BatchPlan &bp, const void *d_tail, uint32_t n, hipStream_t s) {
+        melspec_blm *b = st.owner;
+        FbankNemoStreamParams q{};
+        q.f = blm_fast_params(b, bp.desc);
+        q.f.b.mel_major = 1;
+        q.f.b.sync_rounds = kNemoSync;
+        q.f.d_len = static_cast<const uint64_t *>(d_tail);
+        q.f.d_valid = bp.desc.d_frames;
+        q.d_org0 = reinterpret_cast<const int *>(static_cast<const char *>(d_tail) + blm_stream_org0_at(n));
+        const Route512 r = route512(blm_shape(b), Batch512::kLayout);      // the kernel a batch of the context runs on now; its stream form
+        apply_route(r, q.f, b->f32);
+        return launch512(r.run, q, blm_lds(b), b->dev.cus, s);
+    }
+    static hipError_t fold(const BlmStreamBank &st, const StreamEntry *d_e, const uint64_t *src_off, const float *rows, void *dst, int out_dtype, uint32_t n, hipStream_t s) {
+        double *moments = static_cast<double *>(st.acc.p);
+        unsigned long long *counts = static_cast<unsigned long long *>(st.counts.p);
+        const int nm = static_cast<int>(st.geom.n_mels);
+        if (src_off) return blm_stream_stats_io_launch(BlmStreamStatsIoParams{d_e, src_off, rows, dst, moments, counts, nm, 0}, out_dtype, n, s);
+        const BlmStreamStatsParams sp{d_e, rows, moments, counts, nm};
+        hipLaunchKernelGGL(blm_stream_stats_kernel, dim3(n), dim3(kBlmStreamStatsThreads), 0, s, sp);
+        return hipGetLastError();
+    }
+    static void read_out(const BlmStreamBank &st, const uint32_t *d_ids, uint32_t n, float *const *out, hipStream_t s) {
+        const BlmStreamMomentsParams mp{d_ids, static_cast<const double *>(st.acc.p), static_cast<const unsigned long long *>(st.counts.p), out[0], out[1], n, static_cast<int>(st.geom.n_mels)};
+        hipLaunchKernelGGL(blm_stream_moments_kernel, st.stats_grid(n, kBlmStreamStatsThreads), dim3(kBlmStreamStatsThreads), 0, s, mp);
+    }
 };
-
-FbankStreamBank *fbs_of(void *h) {
-    FbankStreamBank *st = static_cast<FbankStreamBank *>(h);
-    return st && st->magic == kFbankStreamMagic ? st : nullptr;
-}
-const FbankStreamBank *fbs_of(const void *h) { return fbs_of(const_cast<void *>(h)); }
-
-// the objects a bank can stand on: the fused 512-point path (every kernel of MS_K512_STREAM), frames that overlap or abut
-int fbs_supported(const melspec_fbank *fb) {
-    if (melspec_fbank_uses_fast_path(fb) && fb->frame_shift <= fb->frame_len) return MELSPEC_OK;
-    char geo[256];
-    std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d", fb->cfg.sample_rate,
-                  fb->frame_len, fb->frame_shift, fb->cfg.num_mel_bins);
-    g_last_error = std::string("the fbank stream bank runs on the fused fbank path (400-sample frames) with frame_shift <= frame_length; this object is ") + geo +
-                   (fb->use_generic ? " on the generic path (melspec_fbank_use_generic)" : (fb->fast ? "" : " (generic path)"));
-    return MELSPEC_ERR_UNSUPPORTED;
-}
-
-// the frame stage behind the core's scatter: the rows, then their column sums; the entries' tail is the clips' continues flags.
-// out_dtype: the row type at a.d_out.  16-bit rows: the same frame stage, planned onto the bank's f32 scratch with the plan's packed
-// offsets, and the typed twin of the sum kernel, which reads the rows there and writes the caller's (the scratch grows before anything
-// is queued)
-int fbs_run(FbankStreamBank *st, const FbankStreamPlan &pl, uint32_t n, const PushArgs &a, int out_dtype = MELSPEC_OUT_F32) {
-    melspec_fbank *fb = st->fb;
-    const int nm = fb->cfg.num_mel_bins;
-    const bool typed = out_dtype != MELSPEC_OUT_F32;
-    TypedTail tail(pl.continues.data(), static_cast<size_t>(n) * sizeof(uint32_t), typed ? pl.out_off.data() : nullptr, n);
-    if (typed && pl.total_frames) {
-        if (!a.d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");
-        HIP_TRY(hipSetDevice(st->core.device));
-        if (int rc = st->rows32.ensure(static_cast<size_t>(pl.total_frames) * nm * sizeof(float) + 16)) return rc;
-    }
-    float *rows = static_cast<float *>(typed ? st->rows32.p : a.d_out);
-    const uint64_t *rows_off = a.h_out_off && !typed ? a.h_out_off : pl.out_off.data();
-    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data, tail.bytes, [&](const StreamEntry *d_e, const void *d_tail) {
-        BatchPlan bp;
-        RaggedSlot *pslot = nullptr;
-        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), rows, pl.off.data(), pl.frames, rows_off, n, nm, kFbFPW, bp, pslot);
-        if (!rc) {
-            FbankStreamParams q{};
-            q.f = fbank_fast_params(fb, bp.desc);
-            q.d_cont = static_cast<const uint32_t *>(d_tail);
-            rc = launch512(route512(fbank_shape(fb), Batch512::kStream).run, q, Lds512Sizes{fb->fast_lds, 0, nm}, fb->dev.cus, a.stream);
-        }
-        plan_ragged_done(pslot, a.stream);
-        if (rc) return rc;
-        if (typed) {
-            FbankStreamSumIoParams sp{};
-            sp.entries = d_e; sp.src_off = tail.packed_on_device(d_tail); sp.rows = rows; sp.dst = a.d_out; sp.sums = static_cast<double *>(st->sums.p);
-            sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
-            HIP_TRY(fbank_stream_sum_io_launch(sp, out_dtype, n, a.stream));
-            return static_cast<int>(MELSPEC_OK);
-        }
-        FbankStreamSumParams sp{};
-        sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.sums = static_cast<double *>(st->sums.p);
-        sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
-        hipLaunchKernelGGL(fbank_stream_sum_kernel, dim3(n), dim3(kFbankStreamSumThreads), 0, a.stream, sp);
-        HIP_TRY(hipGetLastError());
-        return static_cast<int>(MELSPEC_OK);
-    });
-}
-
-// a push behind its argument checks: plan, run(plan) -- its launches have completed when it returns --, then the book moves on
-template <class Run>
-int fbs_push(FbankStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, uint32_t *frames_out, Run run) {
-    FbankStreamPlan pl;
-    const char *err = nullptr;
-    int rc = plan_status(fbank_stream_plan_push(st->geom, st->book, ids, lens, n, pl, &err), err);
-    if (rc || (rc = run(pl))) return rc;
-    fbank_stream_commit_push(st->geom, st->book, ids, lens, n);
-    for (uint32_t i = 0; frames_out && i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
-    return MELSPEC_OK;
-}
-
-// what every push checks first: the handle, the dtype codes, the object
-int fbs_push_args(FbankStreamBank *st, int pcm_dtype, int out_dtype) {
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
-    int io;
-    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
-    return fbs_supported(st->fb);
-}
-
-// melspec_fbank_stream_push_host / _push_host_io: the rows cross the bus in their own type
-int fbs_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out, int out_dtype,
-                  size_t out_capacity_elems, uint32_t *frames_out) {
-    FbankStreamBank *st = fbs_of(h);
-    if (int rc = fbs_push_args(st, pcm_dtype, out_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
-        const HostPush hp{samples, out, out_capacity_elems, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), io_out_bytes(out_dtype)};
-        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
-            return fbs_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s}, out_dtype);
-        });
-    });
-}
-
-// melspec_fbank_stream_push_device / _push_device_io
-int fbs_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens, uint32_t n,
-                    void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    FbankStreamBank *st = fbs_of(h);
-    if (int rc = fbs_push_args(st, pcm_dtype, out_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids || !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    if (!d_chunks && pcm_dtype != MELSPEC_PCM_F32)
-        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_fbank_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
-    if (io_misaligned(d_chunks, d_out, pcm_dtype | out_dtype << 4)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    return fbs_push(st, ids, lens, n, frames_out, [&](const FbankStreamPlan &pl) {
-        return fbs_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
-                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream}, out_dtype);
-    });
-}
 }  // namespace
 
 extern "C" {
 
-int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_streams, uint32_t max_chunk) {
-    if (!out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
-    *out = nullptr;
-    if (n_streams == 0 || max_chunk == 0) return fail(MELSPEC_ERR_INVALID_ARG, "n_streams and max_chunk must be > 0");
-    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
-    if (int rc = fbs_supported(fb)) return rc;
-    FbankStreamBank *st = new (std::nothrow) FbankStreamBank();
-    if (!st) return fail(MELSPEC_ERR_INTERNAL, "out of host memory");
-    st->fb = fb;
-    st->geom = fbank_stream_geometry(static_cast<uint32_t>(fb->frame_len), static_cast<uint32_t>(fb->frame_shift), static_cast<uint32_t>(fb->cfg.num_mel_bins),
-                                     n_streams, max_chunk);
-    st->book.reset(n_streams);
-    auto bail = [&](int code) { melspec_fbank_stream_destroy(st); return code; };
-    const size_t sum_bytes = static_cast<size_t>(n_streams) * st->geom.n_mels * sizeof(double), count_bytes = static_cast<size_t>(n_streams) * sizeof(unsigned long long);
-    int rc;
-    if ((rc = core_create(st->core, fb->dev.device, fb->stream, n_streams, st->geom.stride, st->geom.in_off)) || (rc = st->sums.ensure(sum_bytes)) ||
-        (rc = st->counts.ensure(count_bytes)))
-        return bail(rc);
-    if (hipMemset(st->sums.p, 0, sum_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess) return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
-    *out = st;
-    return MELSPEC_OK;
-}
-
-void melspec_fbank_stream_destroy(void *h) {
-    FbankStreamBank *st = fbs_of(h);
-    if (!st) return;
-    core_destroy(st->core);
-    st->sums.release(); st->counts.release(); st->means.release(); st->rows32.release();
-    st->magic = 0;
-    delete st;
-}
-
-int melspec_fbank_stream_reset(void *h, const uint32_t *ids, uint32_t n) {
-    FbankStreamBank *st = fbs_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
-    if (int rc = core_reset_slots(st->core, ids, n)) return rc;      // a bad id: nothing has been touched
-    const FbankStreamGeom &g = st->geom;
-    hipStream_t s = st->core.stream;
-    const size_t row = static_cast<size_t>(g.n_mels) * sizeof(double);
-    if (!ids) {
-        HIP_TRY(hipMemsetAsync(st->sums.p, 0, g.n_streams * row, s));
-        HIP_TRY(hipMemsetAsync(st->counts.p, 0, static_cast<size_t>(g.n_streams) * sizeof(unsigned long long), s));
-        st->book.reset(g.n_streams);
-    }
-    for (uint32_t i = 0; ids && i < n; ++i) {
-        HIP_TRY(hipMemsetAsync(static_cast<char *>(st->sums.p) + ids[i] * row, 0, row, s));
-        HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
-        st->book.reset_one(ids[i]);
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return MELSPEC_OK;
-}
-
-size_t melspec_fbank_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) {
-    const FbankStreamBank *st = fbs_of(h);
-    if (!st || id >= st->geom.n_streams) return 0;
-    return fbank_stream_frames_after(st->geom, st->book, id, n_new);
-}
-
-float *melspec_fbank_stream_input_ptr(void *h, uint32_t id) {
-    FbankStreamBank *st = fbs_of(h);
-    return st ? core_input_ptr(st->core, id) : nullptr;
-}
+int melspec_fbank_stream_create(void **out, melspec_fbank *fb, uint32_t n_streams, uint32_t max_chunk) { return FbankStreamBank::create(out, fb, n_streams, max_chunk); }
+void melspec_fbank_stream_destroy(void *h) { FbankStreamBank::destroy(h); }
+int melspec_fbank_stream_reset(void *h, const uint32_t *ids, uint32_t n) { return FbankStreamBank::reset(h, ids, n); }
+size_t melspec_fbank_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) { return FbankStreamBank::frames_after(h, id, n_new); }
+float *melspec_fbank_stream_input_ptr(void *h, uint32_t id) { return FbankStreamBank::input_ptr(h, id); }
+int melspec_fbank_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) { return FbankStreamBank::supports_io(h, pcm_dtype, out_dtype); }
 
 int melspec_fbank_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
                                    size_t out_capacity_floats, uint32_t *frames_out) {
-    return fbs_push_host(h, ids, samples, pcm_dtype, lens, n, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
+    return FbankStreamBank::push_host(h, ids, samples, pcm_dtype, lens, n, false, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
 }
-
-int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
-                                     uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    return fbs_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
-}
-
-int melspec_fbank_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) {
-    const FbankStreamBank *st = fbs_of(h);
-    if (!st || !io_pcm_known(pcm_dtype) || !io_out_known(out_dtype)) return 0;
-    return melspec_fbank_uses_fast_path(st->fb) && st->fb->frame_shift <= st->fb->frame_len ? 1 : 0;      // fbs_supported, without its message
-}
-
 int melspec_fbank_stream_push_host_io(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out,
                                       int out_dtype, size_t out_capacity_elems, uint32_t *frames_out) {
-    return fbs_push_host(h, ids, samples, pcm_dtype, lens, n, out, out_dtype, out_capacity_elems, frames_out);
+    return FbankStreamBank::push_host(h, ids, samples, pcm_dtype, lens, n, false, out, out_dtype, out_capacity_elems, frames_out);
 }
-
+int melspec_fbank_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                     uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    return FbankStreamBank::push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
+}
 int melspec_fbank_stream_push_device_io(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
                                         uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    return fbs_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, d_out, out_dtype, h_out_offsets, frames_out, stream);
+    return FbankStreamBank::push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, out_dtype, h_out_offsets, frames_out, stream);
 }
 
 int melspec_fbank_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_means, uint64_t *h_counts, void *stream) {
-    FbankStreamBank *st = fbs_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
-    if (!d_means) return fail(MELSPEC_ERR_INVALID_ARG, "d_means is NULL");
-    for (uint32_t i = 0; i < n; ++i)
-        if (ids[i] >= st->geom.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
-    HIP_TRY(hipSetDevice(st->fb->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st->fb->stream;
-    const size_t bytes = round16(static_cast<size_t>(n) * sizeof(uint32_t));
-    RaggedSlot *sl = nullptr;
-    int rc = table_slot_take(st->core.ring, bytes, sl);
-    if (rc) return rc;
-    std::memcpy(sl->host, ids, static_cast<size_t>(n) * sizeof(uint32_t));
-    SlotGuard slot_guard{sl, s};
-    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
-    FbankStreamMeanParams mp{};
-    mp.ids = static_cast<const uint32_t *>(sl->dev.p); mp.sums = static_cast<const double *>(st->sums.p);
-    mp.counts = static_cast<const unsigned long long *>(st->counts.p); mp.means = d_means; mp.n = n; mp.n_mels = static_cast<int>(st->geom.n_mels);
-    const uint64_t total = static_cast<uint64_t>(n) * st->geom.n_mels;
-    hipLaunchKernelGGL(fbank_stream_mean_kernel, dim3(grid_for((total + kFbankStreamSumThreads - 1) / kFbankStreamSumThreads, st->fb->dev.cus, 8)),
-                       dim3(kFbankStreamSumThreads), 0, s, mp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h_counts)
-        for (uint32_t i = 0; i < n; ++i) h_counts[i] = st->book.emitted[ids[i]];
-    return MELSPEC_OK;
+    float *const out[] = {d_means};
+    return FbankStreamBank::stats_device(h, ids, n, out, h_counts, stream);
 }
-
 int melspec_fbank_stream_stats_host(void *h, const uint32_t *ids, uint32_t n, float *means, uint64_t *counts) {
-    FbankStreamBank *st = fbs_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "fbank stream bank is NULL");
-    if (n == 0) return MELSPEC_OK;
-    if (!means) return fail(MELSPEC_ERR_INVALID_ARG, "means is NULL");
-    HIP_TRY(hipSetDevice(st->fb->dev.device));
-    const size_t bytes = static_cast<size_t>(n) * st->geom.n_mels * sizeof(float);
-    if (int rc = st->means.ensure(bytes + 16)) return rc;
-    if (int rc = melspec_fbank_stream_stats_device(h, ids, n, static_cast<float *>(st->means.p), counts, st->fb->stream)) return rc;
-    HIP_TRY(hipMemcpy(means, st->means.p, bytes, hipMemcpyDeviceToHost));
-    return MELSPEC_OK;
+    float *const out[] = {means};
+    return FbankStreamBank::stats_host(h, ids, n, out, counts);
 }
 
-}  // extern "C"
-
-// ------------------------------------------------------------------------------------
-// NeMo / Parakeet frontend: the stream bank (melspec_blm_stream_*): see include/melspec_hip.h.  Bookkeeping in blm_stream_plan.hpp, kernels in
-// fbank512_nemo_stream_kernels.hpp; everything a bank of live streams is besides its planner and its frame stage in stream_bank.hpp.
-// ------------------------------------------------------------------------------------
-namespace {
-constexpr uint32_t kBlmStreamMagic = 0x4d4c424eu;        // the handle crosses the ABI as void *: every call checks what it was given
-
-struct BlmStreamBank {
-    uint32_t magic = kBlmStreamMagic;
-    melspec_blm *b = nullptr;            // geometry, tables, kernels, precision mode; not owned
-    BlmStreamGeom geom{};
-    BlmStreamBook book;                  // total / emitted / ended per stream (host side of the state)
-    BankCore core;
-    DevBuf moments, counts;              // [n_streams][2][n_mels] f64 (mean, M2), [n_streams] u64
-    DevBuf stats;                        // the host stats call's buffer
-    DevBuf rows32;                       // the f32 rows of a push with 16-bit rows, packed in entry order: allocated by the first such push
-};
-
-BlmStreamBank *bls_of(void *h) {
-    BlmStreamBank *st = static_cast<BlmStreamBank *>(h);
-    return st && st->magic == kBlmStreamMagic ? st : nullptr;
-}
-const BlmStreamBank *bls_of(const void *h) { return bls_of(const_cast<void *>(h)); }
-
-// the contexts a bank can stand on: the fused 512-point path (every kernel of MS_K512_NEMO_STREAM)
-int bls_supported(const melspec_blm *b) {
-    if (b->fast) return MELSPEC_OK;
-    g_last_error = "the log-mel stream bank runs on the fused kernels (n_fft = 512, win_length = 400); this context is n_fft = " + std::to_string(b->cfg.n_fft) +
-                   ", win_length = " + std::to_string(b->cfg.win_length) + ", hop_length = " + std::to_string(b->cfg.hop_length) + ", n_mels = " + std::to_string(b->cfg.n_mels) +
-                   (b->cfg.n_fft == 512 && b->cfg.win_length == 400 ? " (a filterbank the fused kernels do not hold)" : "");
-    return MELSPEC_ERR_UNSUPPORTED;
-}
-
-// the frame stage behind the core's scatter: the columns, then the running statistics; the entries' tail is the clips' sample counts
-// and, behind them, their window origins
-// out_dtype: the row type at a.d_out.  16-bit rows: the same frame stage, planned onto the bank's f32 scratch with the plan's packed
-// offsets, and the typed twin of the statistics kernel, which reads the rows there and writes the caller's (the scratch grows before
-// anything is queued)
-int bls_run(BlmStreamBank *st, const BlmStreamPlan &pl, uint32_t n, const PushArgs &a, int out_dtype = MELSPEC_OUT_F32) {
-    melspec_blm *b = st->b;
-    const int nm = b->cfg.n_mels;
-    const bool typed = out_dtype != MELSPEC_OUT_F32;
-    const size_t len_bytes = static_cast<size_t>(n) * sizeof(uint64_t);
-    std::vector<unsigned char> own(len_bytes + static_cast<size_t>(n) * sizeof(int32_t));
-    std::memcpy(own.data(), pl.len.data(), len_bytes);
-    std::memcpy(own.data() + len_bytes, pl.org0.data(), static_cast<size_t>(n) * sizeof(int32_t));
-    TypedTail tail(own.data(), own.size(), typed ? pl.out_off.data() : nullptr, n);
-    if (typed && pl.total_frames) {
-        if (!a.d_out) return fail(MELSPEC_ERR_INVALID_ARG, "d_out is NULL");
-        HIP_TRY(hipSetDevice(st->core.device));
-        if (int rc = st->rows32.ensure(static_cast<size_t>(pl.total_frames) * nm * sizeof(float) + 16)) return rc;
-    }
-    float *rows = static_cast<float *>(typed ? st->rows32.p : a.d_out);
-    const uint64_t *rows_off = a.h_out_off && !typed ? a.h_out_off : pl.out_off.data();
-    return core_run(st->core, pl.entries.data(), n, pl.total_frames, a, nullptr, tail.data, tail.bytes, [&](const StreamEntry *d_e, const void *d_tail) {
-        BatchPlan bp;
-        RaggedSlot *pslot = nullptr;
-        int rc = plan_ragged(st->core.plan_ring, a.stream, static_cast<float *>(st->core.state.p), rows, pl.off.data(), pl.frames, rows_off, n, nm, kFbFPW, bp, pslot);
-        if (!rc) {
-            // the ragged batch of blm_ragged over the state: feature-major rows as wide as the entry's frames, every one of them valid
-            FbankNemoStreamParams q{};
-            q.f = blm_fast_params(b, bp.desc);
-            q.f.b.mel_major = 1;
-            q.f.b.sync_rounds = kNemoSync;
-            q.f.d_len = static_cast<const uint64_t *>(d_tail);
-            q.f.d_valid = bp.desc.d_frames;
-            q.d_org0 = reinterpret_cast<const int *>(static_cast<const char *>(d_tail) + len_bytes);
-            const Route512 r = route512(blm_shape(b), Batch512::kLayout);      // the kernel a batch of the context runs on now; its stream form
-            apply_route(r, q.f, b->f32);
-            rc = launch512(r.run, q, blm_lds(b), b->dev.cus, a.stream);
-        }
-        plan_ragged_done(pslot, a.stream);
-        if (rc) return rc;
-        if (typed) {
-            BlmStreamStatsIoParams sp{};
-            sp.entries = d_e; sp.src_off = tail.packed_on_device(d_tail); sp.rows = rows; sp.dst = a.d_out; sp.moments = static_cast<double *>(st->moments.p);
-            sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
-            HIP_TRY(blm_stream_stats_io_launch(sp, out_dtype, n, a.stream));
-            return static_cast<int>(MELSPEC_OK);
-        }
-        BlmStreamStatsParams sp{};
-        sp.entries = d_e; sp.rows = static_cast<const float *>(a.d_out); sp.moments = static_cast<double *>(st->moments.p);
-        sp.counts = static_cast<unsigned long long *>(st->counts.p); sp.n_mels = nm;
-        hipLaunchKernelGGL(blm_stream_stats_kernel, dim3(n), dim3(kBlmStreamStatsThreads), 0, a.stream, sp);
-        HIP_TRY(hipGetLastError());
-        return static_cast<int>(MELSPEC_OK);
-    });
-}
-
-// a push or a finish behind its argument checks: plan, run(plan) -- its launches have completed when it returns --, then the book moves on
-template <class Run>
-int bls_push(BlmStreamBank *st, const uint32_t *ids, const uint32_t *lens, uint32_t n, bool finish, uint32_t *frames_out, Run run) {
-    BlmStreamPlan pl;
-    const char *err = nullptr;
-    int rc = plan_status(blm_stream_plan_push(st->geom, st->book, ids, lens, n, finish, pl, &err), err);
-    if (rc || (rc = run(pl))) return rc;
-    blm_stream_commit_push(st->geom, st->book, ids, lens, n, finish);
-    for (uint32_t i = 0; frames_out && i < n; ++i) frames_out[i] = static_cast<uint32_t>(pl.frames[i]);
-    return MELSPEC_OK;
-}
-
-// what every push checks first: the handle, the dtype codes, the context
-int bls_push_args(BlmStreamBank *st, int pcm_dtype, int out_dtype) {
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
-    int io;
-    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
-    return bls_supported(st->b);
-}
-
-// melspec_blm_stream_push_host / _finish_host and their _io forms (finish: no samples, lens is not read): the rows cross the bus in their own type
-int bls_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, bool finish, void *out, int out_dtype,
-                  size_t out_capacity_elems, uint32_t *frames_out) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, pcm_dtype, out_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, finish ? "ids is NULL" : "ids/lens is NULL");
-    if (!finish && !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    return bls_push(st, ids, lens, n, finish, frames_out, [&](const BlmStreamPlan &pl) {
-        const HostPush hp{samples, out, out_capacity_elems, pl.total_frames * static_cast<uint64_t>(st->geom.n_mels), io_pcm_bytes(pcm_dtype), io_out_bytes(out_dtype)};
-        return core_push_host(st->core, pl.entries.data(), n, hp, [&](const void *d_src, void *d_out, hipStream_t s) {
-            return bls_run(st, pl, n, PushArgs{d_src, pcm_dtype, nullptr, d_out, nullptr, s}, out_dtype);
-        });
-    });
-}
-
-// melspec_blm_stream_push_device / _finish_device and their _io forms (finish: d_chunks NULL, MELSPEC_PCM_F32, lens is not read)
-int bls_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens, uint32_t n, bool finish,
-                    void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    BlmStreamBank *st = bls_of(h);
-    if (int rc = bls_push_args(st, pcm_dtype, out_dtype)) return rc;
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, finish ? "ids is NULL" : "ids/lens is NULL");
-    if (!finish && !lens) return fail(MELSPEC_ERR_INVALID_ARG, "ids/lens is NULL");
-    if (!finish && !d_chunks && pcm_dtype != MELSPEC_PCM_F32)
-        return fail(MELSPEC_ERR_INVALID_ARG, "d_chunks is NULL: the chunks are at melspec_blm_stream_input_ptr, which holds f32 (pcm_dtype must be MELSPEC_PCM_F32)");
-    if (io_misaligned(d_chunks, d_out, pcm_dtype | out_dtype << 4)) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type");
-    return bls_push(st, ids, lens, n, finish, frames_out, [&](const BlmStreamPlan &pl) {
-        return bls_run(st, pl, n, PushArgs{d_chunks, pcm_dtype, d_chunks ? h_src_offsets : nullptr, d_out, h_out_offsets,
-                                           stream ? static_cast<hipStream_t>(stream) : st->core.stream}, out_dtype);
-    });
-}
-}  // namespace
-
-extern "C" {
-
-int melspec_blm_stream_create(void **out, melspec_blm *b, uint32_t n_streams, uint32_t max_chunk) {
-    if (!out) return fail(MELSPEC_ERR_INVALID_ARG, "out is NULL");
-    *out = nullptr;
-    if (n_streams == 0 || max_chunk == 0) return fail(MELSPEC_ERR_INVALID_ARG, "n_streams and max_chunk must be > 0");
-    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
-    if (int rc = bls_supported(b)) return rc;
-    BlmStreamBank *st = new (std::nothrow) BlmStreamBank();
-    if (!st) return fail(MELSPEC_ERR_INTERNAL, "out of host memory");
-    st->b = b;
-    st->geom = blm_stream_geometry(static_cast<uint32_t>(b->cfg.hop_length), b->cfg.center != 0, static_cast<uint32_t>(b->cfg.n_mels), n_streams, max_chunk);
-    st->book.reset(n_streams);
-    auto bail = [&](int code) { melspec_blm_stream_destroy(st); return code; };
-    const size_t mom_bytes = static_cast<size_t>(n_streams) * 2 * st->geom.n_mels * sizeof(double), count_bytes = static_cast<size_t>(n_streams) * sizeof(unsigned long long);
-    int rc;
-    if ((rc = core_create(st->core, b->dev.device, b->stream, n_streams, st->geom.stride, st->geom.in_off)) || (rc = st->moments.ensure(mom_bytes)) ||
-        (rc = st->counts.ensure(count_bytes)))
-        return bail(rc);
-    if (hipMemset(st->moments.p, 0, mom_bytes) != hipSuccess || hipMemset(st->counts.p, 0, count_bytes) != hipSuccess) return bail(fail(MELSPEC_ERR_INTERNAL, "hipMemset failed"));
-    *out = st;
-    return MELSPEC_OK;
-}
-
-void melspec_blm_stream_destroy(void *h) {
-    BlmStreamBank *st = bls_of(h);
-    if (!st) return;
-    core_destroy(st->core);
-    st->moments.release(); st->counts.release(); st->stats.release(); st->rows32.release();
-    st->magic = 0;
-    delete st;
-}
-
-int melspec_blm_stream_reset(void *h, const uint32_t *ids, uint32_t n) {
-    BlmStreamBank *st = bls_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
-    if (int rc = core_reset_slots(st->core, ids, n)) return rc;      // a bad id: nothing has been touched
-    const BlmStreamGeom &g = st->geom;
-    hipStream_t s = st->core.stream;
-    const size_t row = static_cast<size_t>(g.n_mels) * 2 * sizeof(double);
-    if (!ids) {
-        HIP_TRY(hipMemsetAsync(st->moments.p, 0, g.n_streams * row, s));
-        HIP_TRY(hipMemsetAsync(st->counts.p, 0, static_cast<size_t>(g.n_streams) * sizeof(unsigned long long), s));
-        st->book.reset(g.n_streams);
-    }
-    for (uint32_t i = 0; ids && i < n; ++i) {
-        HIP_TRY(hipMemsetAsync(static_cast<char *>(st->moments.p) + ids[i] * row, 0, row, s));
-        HIP_TRY(hipMemsetAsync(static_cast<unsigned long long *>(st->counts.p) + ids[i], 0, sizeof(unsigned long long), s));
-        st->book.reset_one(ids[i]);
-    }
-    HIP_TRY(hipStreamSynchronize(s));
-    return MELSPEC_OK;
-}
-
-size_t melspec_blm_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) {
-    const BlmStreamBank *st = bls_of(h);
-    if (!st || id >= st->geom.n_streams) return 0;
-    return blm_stream_frames_after(st->geom, st->book, id, n_new);
-}
-
+int melspec_blm_stream_create(void **out, melspec_blm *b, uint32_t n_streams, uint32_t max_chunk) { return BlmStreamBank::create(out, b, n_streams, max_chunk); }
+void melspec_blm_stream_destroy(void *h) { BlmStreamBank::destroy(h); }
+int melspec_blm_stream_reset(void *h, const uint32_t *ids, uint32_t n) { return BlmStreamBank::reset(h, ids, n); }
+size_t melspec_blm_stream_frames_after(const void *h, uint32_t id, uint32_t n_new) { return BlmStreamBank::frames_after(h, id, n_new); }
 size_t melspec_blm_stream_finish_frames(const void *h, uint32_t id) {
-    const BlmStreamBank *st = bls_of(h);
-    if (!st || id >= st->geom.n_streams) return 0;
-    return blm_stream_finish_frames(st->geom, st->book, id);
+    const BlmStreamBank *st = BlmStreamBank::of(h);
+    return st && id < st->geom.n_streams ? blm_stream_finish_frames(st->geom, st->book, id) : 0;
 }
-
-float *melspec_blm_stream_input_ptr(void *h, uint32_t id) {
-    BlmStreamBank *st = bls_of(h);
-    return st ? core_input_ptr(st->core, id) : nullptr;
-}
+float *melspec_blm_stream_input_ptr(void *h, uint32_t id) { return BlmStreamBank::input_ptr(h, id); }
+int melspec_blm_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) { return BlmStreamBank::supports_io(h, pcm_dtype, out_dtype); }
 
 int melspec_blm_stream_push_host(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, float *out,
                                  size_t out_capacity_floats, uint32_t *frames_out) {
-    return bls_push_host(h, ids, samples, pcm_dtype, lens, n, false, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
+    return BlmStreamBank::push_host(h, ids, samples, pcm_dtype, lens, n, false, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
 }
-
-int melspec_blm_stream_finish_host(void *h, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats, uint32_t *frames_out) {
-    return bls_push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
-}
-
-int melspec_blm_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
-                                   uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    return bls_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
-}
-
-int melspec_blm_stream_finish_device(void *h, const uint32_t *ids, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    return bls_push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
-}
-
-int melspec_blm_stream_supports_io(const void *h, int pcm_dtype, int out_dtype) {
-    const BlmStreamBank *st = bls_of(h);
-    return st && io_pcm_known(pcm_dtype) && io_out_known(out_dtype) && st->b->fast ? 1 : 0;      // bls_supported, without its message
-}
-
 int melspec_blm_stream_push_host_io(void *h, const uint32_t *ids, const void *samples, int pcm_dtype, const uint32_t *lens, uint32_t n, void *out, int out_dtype,
                                     size_t out_capacity_elems, uint32_t *frames_out) {
-    return bls_push_host(h, ids, samples, pcm_dtype, lens, n, false, out, out_dtype, out_capacity_elems, frames_out);
+    return BlmStreamBank::push_host(h, ids, samples, pcm_dtype, lens, n, false, out, out_dtype, out_capacity_elems, frames_out);
 }
-
+int melspec_blm_stream_push_device(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
+                                   uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    return BlmStreamBank::push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
+}
 int melspec_blm_stream_push_device_io(void *h, const uint32_t *ids, const void *d_chunks, int pcm_dtype, const uint64_t *h_src_offsets, const uint32_t *lens,
                                       uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
-    return bls_push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, out_dtype, h_out_offsets, frames_out, stream);
+    return BlmStreamBank::push_device(h, ids, d_chunks, pcm_dtype, h_src_offsets, lens, n, false, d_out, out_dtype, h_out_offsets, frames_out, stream);
 }
 
+// a finish is a push of no samples with the planner's finish flag
+int melspec_blm_stream_finish_host(void *h, const uint32_t *ids, uint32_t n, float *out, size_t out_capacity_floats, uint32_t *frames_out) {
+    return BlmStreamBank::push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, MELSPEC_OUT_F32, out_capacity_floats, frames_out);
+}
 int melspec_blm_stream_finish_host_io(void *h, const uint32_t *ids, uint32_t n, void *out, int out_dtype, size_t out_capacity_elems, uint32_t *frames_out) {
-    return bls_push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, out_dtype, out_capacity_elems, frames_out);
+    return BlmStreamBank::push_host(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, n, true, out, out_dtype, out_capacity_elems, frames_out);
 }
-
+int melspec_blm_stream_finish_device(void *h, const uint32_t *ids, uint32_t n, float *d_out, const uint64_t *h_out_offsets, uint32_t *frames_out, void *stream) {
+    return BlmStreamBank::push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, MELSPEC_OUT_F32, h_out_offsets, frames_out, stream);
+}
 int melspec_blm_stream_finish_device_io(void *h, const uint32_t *ids, uint32_t n, void *d_out, int out_dtype, const uint64_t *h_out_offsets, uint32_t *frames_out,
                                         void *stream) {
-    return bls_push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, out_dtype, h_out_offsets, frames_out, stream);
+    return BlmStreamBank::push_device(h, ids, nullptr, MELSPEC_PCM_F32, nullptr, nullptr, n, true, d_out, out_dtype, h_out_offsets, frames_out, stream);
 }
 
 int melspec_blm_stream_stats_device(void *h, const uint32_t *ids, uint32_t n, float *d_mean, float *d_inv_std, uint64_t *h_counts, void *stream) {
-    BlmStreamBank *st = bls_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
-    if (n == 0) return MELSPEC_OK;
-    if (!ids) return fail(MELSPEC_ERR_INVALID_ARG, "ids is NULL");
-    if (!d_mean || !d_inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "d_mean / d_inv_std is NULL");
-    for (uint32_t i = 0; i < n; ++i)
-        if (ids[i] >= st->geom.n_streams) return fail(MELSPEC_ERR_INVALID_ARG, "stream id out of range");
-    HIP_TRY(hipSetDevice(st->b->dev.device));
-    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : st->b->stream;
-    const size_t bytes = round16(static_cast<size_t>(n) * sizeof(uint32_t));
-    RaggedSlot *sl = nullptr;
-    int rc = table_slot_take(st->core.ring, bytes, sl);
-    if (rc) return rc;
-    std::memcpy(sl->host, ids, static_cast<size_t>(n) * sizeof(uint32_t));
-    SlotGuard slot_guard{sl, s};
-    if ((rc = table_slot_upload(*sl, bytes, s))) return rc;
-    BlmStreamMomentsParams mp{};
-    mp.ids = static_cast<const uint32_t *>(sl->dev.p); mp.moments = static_cast<const double *>(st->moments.p);
-    mp.counts = static_cast<const unsigned long long *>(st->counts.p); mp.mean = d_mean; mp.inv_std = d_inv_std; mp.n = n; mp.n_mels = static_cast<int>(st->geom.n_mels);
-    const uint64_t total = static_cast<uint64_t>(n) * st->geom.n_mels;
-    hipLaunchKernelGGL(blm_stream_moments_kernel, dim3(grid_for((total + kBlmStreamStatsThreads - 1) / kBlmStreamStatsThreads, st->b->dev.cus, 8)),
-                       dim3(kBlmStreamStatsThreads), 0, s, mp);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s));
-    if (h_counts)
-        for (uint32_t i = 0; i < n; ++i) h_counts[i] = st->book.emitted[ids[i]];
-    return MELSPEC_OK;
+    float *const out[] = {d_mean, d_inv_std};
+    return BlmStreamBank::stats_device(h, ids, n, out, h_counts, stream);
 }
-
 int melspec_blm_stream_stats_host(void *h, const uint32_t *ids, uint32_t n, float *mean, float *inv_std, uint64_t *counts) {
-    BlmStreamBank *st = bls_of(h);
-    if (!st) return fail(MELSPEC_ERR_INVALID_ARG, "blm stream bank is NULL");
-    if (n == 0) return MELSPEC_OK;
-    if (!mean || !inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "mean / inv_std is NULL");
-    HIP_TRY(hipSetDevice(st->b->dev.device));
-    const size_t bytes = static_cast<size_t>(n) * st->geom.n_mels * sizeof(float);
-    if (int rc = st->stats.ensure(2 * bytes + 16)) return rc;
-    float *d_mean = static_cast<float *>(st->stats.p), *d_inv = d_mean + static_cast<size_t>(n) * st->geom.n_mels;
-    if (int rc = melspec_blm_stream_stats_device(h, ids, n, d_mean, d_inv, counts, st->b->stream)) return rc;
-    HIP_TRY(hipMemcpy(mean, d_mean, bytes, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(inv_std, d_inv, bytes, hipMemcpyDeviceToHost));
-    return MELSPEC_OK;
+    float *const out[] = {mean, inv_std};
+    return BlmStreamBank::stats_host(h, ids, n, out, counts);
 }
 
 }  // extern "C"
+

@@ -1,6 +1,7 @@
 // fbank_stream_plan.hpp -- host bookkeeping of the Kaldi fbank's stream bank (plain C++, no HIP): which frames of Fbank::compute
-// (src/fbank.rs:141-236) a push completes and where their samples start in the bank's state.  Shared by fbank512.hip and
-// tests/cpp/fbank_stream_host.cpp.
+// (src/fbank.rs:141-236) a push completes and where their samples start in the bank's state.  Shared by fbank512.hip (the Kaldi traits of
+// stat_bank.hpp's StatBank, which is the bank around this planner) and tests/cpp/fbank_stream_host.cpp.  The plan's `continues` goes to
+// the device as the bank's own tail (stat_bank_tail.hpp).
 //
 // A stream that has received `total` samples has emitted E = frames(total) rows (src/fbank.rs:147-151: 0 below frame_len, then one per
 // shift) -- the first rows of Fbank::compute on whatever the stream goes on to receive, since a row depends on its own frame_len samples and

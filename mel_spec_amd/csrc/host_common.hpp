@@ -9,6 +9,8 @@
 //   pow2.hip        generic_frame_kernel / pow2_frame_kernel / generic_stft_kernel: every other geometry, f64
 //   aux.hip         batch planners, streaming bank, TGA quantiser, VAD columns, stand-alone mel helpers, synthetic PCM
 //   stream_bank.hpp BankCore: what the streaming bank (aux.hip) and the stream banks of the Kaldi fbank and the NeMo frontend (fbank512.hip) share; includes this header
+//   stat_bank.hpp   StatBank<B>: the Kaldi fbank's and the NeMo frontend's stream bank, written once over BankCore; their traits and the ABI's forwards are in fbank512.hip
+//   stat_bank_tail.hpp  the table those banks send behind a push's entries (no HIP: host-testable)
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,6 +1,7 @@
 // stream_bank.hpp -- what the banks of live streams share on the host side: the Whisper bank (melspec_stream_*, aux.hip), the Kaldi
 // fbank's (melspec_fbank_stream_*, fbank512.hip) and the NeMo / Parakeet frontend's (melspec_blm_stream_*, fbank512.hip) are this core plus
-// their own planner (stream_plan.hpp / fbank_stream_plan.hpp / blm_stream_plan.hpp) and their own frame stage.  A bank is n_streams slots of `stride` floats in HBM, [carry, ending at in_off][next chunk at in_off]; a push is
+// their own planner (stream_plan.hpp / fbank_stream_plan.hpp / blm_stream_plan.hpp) and their own frame stage; the latter two, which also
+// keep running statistics of their rows, are one bank written once on top of this core (stat_bank.hpp).  A bank is n_streams slots of `stride` floats in HBM, [carry, ending at in_off][next chunk at in_off]; a push is
 //   entries up (unless the device still holds them) -> scatter -> the bank's frame stage -> carry -> wait
 // on one stream, and the host form of it stages samples and rows through the bank's two buffers.
 #pragma once

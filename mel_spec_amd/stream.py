@@ -64,16 +64,6 @@ class _Bank:
         ptrs = [None if x is None else x.ctypes.data_as(C.POINTER(C.c_uint64) if x.dtype == np.uint64 else _u32p) for x in arrs]
         return np.zeros(arrs[0].shape[0], np.uint32), arrs[0].shape[0], ptrs, arrs
 
-    def _supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
-        return bool(self._fn("supports_io")(self._h, int(pcm_dtype), int(out_dtype)))
-
-    def _push_device_io(self, ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream) -> np.ndarray:
-        """the typed device push of the Kaldi and the NeMo bank (FbankStreamBank / BlmStreamBank.push_device_io)"""
-        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
-        _check(self._fn("push_device_io")(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
-                                          int(out_dtype), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
-        return frames
-
     def _gather(self, ids: Sequence[int], chunks: Sequence, allow_s16: bool):
         """a push's arguments: (ids, PCM code, the chunks back to back, their lengths, rows the push will emit, a frames array to fill)"""
         a = _u32(ids)
@@ -227,7 +217,66 @@ class StreamBank(_Bank):
         return frames
 
 
-class FbankStreamBank(_Bank):
+class _StatBank(_Bank):
+    """What the Kaldi and the NeMo / Parakeet bank share (csrc/stat_bank.hpp's StatBank): the calls behind their pushes and stats.  A
+    subclass states its prefix (_P), keeps its owner alive, and says how the flat output of a host call splits per stream (_cut)."""
+
+    def _open(self, owner_handle, n_streams: int, max_chunk: int, n_mels: int) -> None:
+        self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), int(n_mels)
+        h = C.c_void_p()
+        _check(self._fn("create")(C.byref(h), owner_handle, self.n_streams, self.max_chunk), construct=True)
+        self._h = h
+
+    def _cut(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
+        raise NotImplementedError
+
+    def _host(self, name: str, a: np.ndarray, cap: int, out_code: Optional[int], *src) -> tuple:
+        """the host call `name` (out_code None) or its _io form; src: its arguments between ids and n.  Returns (the output cut per
+        stream, the frames each emitted)"""
+        out = np.empty(cap * self.n_mels, np.float32 if out_code is None else _OUT_NUMPY[out_code])
+        frames = np.zeros(a.shape[0], np.uint32)
+        dst = (_fp(out),) if out_code is None else (out.ctypes.data_as(C.c_void_p), out_code)
+        _check(self._fn(name if out_code is None else name + "_io")(self._h, a.ctypes.data_as(_u32p), *src, a.shape[0], *dst, out.size, frames.ctypes.data_as(_u32p)))
+        return self._cut(out, frames), frames
+
+    def _push(self, ids: Sequence[int], chunks: Sequence, out_code: Optional[int] = None) -> List[np.ndarray]:
+        a, pcm, flat, lens, cap, _ = self._gather(ids, chunks, True)
+        res, frames = self._host("push_host", a, cap, out_code, flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p))
+        assert int(frames.sum()) == cap
+        return res
+
+    def _device(self, name: str, ids, lens, d_out, out_offsets, stream, out_dtype: Optional[int], src=None) -> np.ndarray:
+        """the device call `name` (out_dtype None) or its _io form; src: a push's (d_chunks, pcm_dtype, src_offsets), None where the call
+        takes no chunks.  Returns the frames each stream emitted"""
+        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src and src[2])
+        chunks = () if src is None else (C.c_void_p(src[0] or None), int(src[1]), p_so, p_lens)
+        dst = (C.c_void_p(d_out or None),) if out_dtype is None else (C.c_void_p(d_out or None), int(out_dtype))
+        _check(self._fn(name if out_dtype is None else name + "_io")(self._h, p_ids, *chunks, n, *dst, p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
+        return frames
+
+    def _push_device(self, ids, lens, d_out, out_offsets, d_chunks, pcm_dtype, src_offsets, stream, out_dtype: Optional[int] = None) -> np.ndarray:
+        return self._device("push_device", ids, lens, d_out, out_offsets, stream, out_dtype, (d_chunks, pcm_dtype, src_offsets))
+
+    def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
+        return bool(self._fn("supports_io")(self._h, int(pcm_dtype), int(out_dtype)))
+
+    def _stats(self, ids: Sequence[int], k: int) -> tuple:
+        """stats_host: (k arrays [n, n_mels] f32, counts [n] u64)"""
+        a = _u32(ids)
+        arrs = [np.zeros((a.shape[0], self.n_mels), np.float32) for _ in range(k)]
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(self._fn("stats_host")(self._h, a.ctypes.data_as(_u32p), a.shape[0], *[_fp(x) for x in arrs], counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return (*arrs, counts)
+
+    def _stats_device(self, ids: Sequence[int], stream: int, *d_arrs: int) -> np.ndarray:
+        a = _u32(ids)
+        counts = np.zeros(a.shape[0], np.uint64)
+        _check(self._fn("stats_device")(self._h, a.ctypes.data_as(_u32p), a.shape[0], *[C.c_void_p(d or None) for d in d_arrs],
+                                        counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream or None)))
+        return counts
+
+
+class FbankStreamBank(_StatBank):
     """n_streams independent Fbank::compute streams (src/fbank.rs:141-236) on one Fbank's geometry (melspec_fbank_stream_*): after pushes
     whose chunks concatenate to x a stream has emitted exactly the rows of Fbank::compute(x) with apply_cmn off -- the bits of
     Fbank.compute on an apply_cmn = False twin, however x was cut -- and stats() returns the running column means of those rows.
@@ -236,10 +285,10 @@ class FbankStreamBank(_Bank):
 
     def __init__(self, fbank, n_streams: int, max_chunk: int):
         self._fbank = fbank                  # keeps the object alive
-        self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), fbank.num_mel_bins
-        h = C.c_void_p()
-        _check(lib().melspec_fbank_stream_create(C.byref(h), fbank._h, self.n_streams, self.max_chunk), construct=True)
-        self._h = h
+        self._open(fbank._h, n_streams, max_chunk, fbank.num_mel_bins)
+
+    def _cut(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
+        return self._collect(out.reshape(-1, self.n_mels), frames)
 
     def reset(self, ids: Optional[Sequence[int]] = None) -> None:
         """no history, no frames, zero sums for the listed streams (None: all)"""
@@ -248,61 +297,41 @@ class FbankStreamBank(_Bank):
     def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
         """Append chunks[i] (any length <= max_chunk; np.int16 chunks are 16-bit PCM, value = sample / 32768 exactly, and all chunks of
         one call have the same dtype) to stream ids[i]; returns the rows each stream emitted, [k_i, num_mel_bins], before CMN."""
-        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
-        out = np.empty((cap, self.n_mels), np.float32)
-        _check(lib().melspec_fbank_stream_push_host(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
-                                                    a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
-        return self._collect(out, frames, cap)
+        return self._push(ids, chunks)
 
     def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, d_chunks: int = 0, pcm_dtype: int = PCM_F32,
                     src_offsets=None, stream: int = 0) -> np.ndarray:
         """d_chunks == 0: the chunks are at input_ptr, in f32; otherwise chunk i is lens[i] elements of pcm_dtype at d_chunks +
         src_offsets[i] elements (None: back to back).  Rows go to d_out + out_offsets[i] floats (None: back to back)."""
-        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
-        _check(lib().melspec_fbank_stream_push_device(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
-                                                      p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
-        return frames
+        return self._push_device(ids, lens, d_out, out_offsets, d_chunks, pcm_dtype, src_offsets, stream)
 
     # ---- f16 / bf16 rows out (melspec_fbank_stream_*_io): the statistics stay those of the f32 rows ----
     def push_io(self, ids: Sequence[int], chunks: Sequence, out_dtype=None) -> List[np.ndarray]:
         """push() whose rows have the type out_dtype names: None np.float32, "f16" (or np.float16) np.float16, "bf16" the bfloat16 bit
         patterns as np.uint16 -- the f32 rows of push() rounded to nearest even.  stats() is what it is after the same push()es."""
-        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
-        out_code = _out_code(out_dtype)
-        out = np.empty((cap, self.n_mels), _OUT_NUMPY[out_code])
-        _check(lib().melspec_fbank_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
-                                                       a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size, frames.ctypes.data_as(_u32p)))
-        return self._collect(out, frames, cap)
+        return self._push(ids, chunks, _out_code(out_dtype))
 
     def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
         """every valid pair of codes, on every Fbank a bank can be created on"""
-        return self._supports_io(pcm_dtype, out_dtype)
+        return super().supports_io(pcm_dtype, out_dtype)
 
     def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
                        src_offsets=None, out_offsets=None, stream: int = 0) -> np.ndarray:
         """push_device with typed rows: d_chunks / pcm_dtype / src_offsets as there; rows of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to
         d_out + out_offsets[i] elements (None: back to back; a 16-bit entry may start at an odd element)."""
-        return self._push_device_io(ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream)
+        return self._push_device(ids, lens, d_out, out_offsets, d_chunks, pcm_dtype, src_offsets, stream, out_dtype)
 
     def stats(self, ids: Sequence[int]):
         """(means [n, num_mel_bins] f32, counts [n] u64): mean[bin] = f32(f64 sum of the stream's emitted rows / their count), zeros for
         a stream without a row"""
-        a = _u32(ids)
-        means = np.zeros((a.shape[0], self.n_mels), np.float32)
-        counts = np.zeros(a.shape[0], np.uint64)
-        _check(lib().melspec_fbank_stream_stats_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(means), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return means, counts
+        return self._stats(ids, 1)
 
     def stats_device(self, ids: Sequence[int], d_means: int, stream: int = 0) -> np.ndarray:
         """the means to device memory at d_means ([n, num_mel_bins] f32); returns the counts"""
-        a = _u32(ids)
-        counts = np.zeros(a.shape[0], np.uint64)
-        _check(lib().melspec_fbank_stream_stats_device(self._h, a.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_means or None),
-                                                       counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream or None)))
-        return counts
+        return self._stats_device(ids, stream, d_means)
 
 
-class BlmStreamBank(_Bank):
+class BlmStreamBank(_StatBank):
     """n_streams independent BatchLogMelSpectrogram::compute streams (src/mel.rs) on one BatchLogMelSpectrogram's geometry
     (melspec_blm_stream_*): after pushes whose chunks concatenate to x and one finish, a stream has emitted exactly the columns of
     compute(x) on a normalize_per_feature = False twin in the same precision mode (pad_to ignored) -- bit for bit, however x was cut
@@ -312,19 +341,9 @@ class BlmStreamBank(_Bank):
 
     def __init__(self, blm, n_streams: int, max_chunk: int):
         self._blm = blm                      # keeps the context alive
-        self.n_streams, self.max_chunk, self.n_mels = int(n_streams), int(max_chunk), int(blm.config.n_mels)
-        h = C.c_void_p()
-        _check(lib().melspec_blm_stream_create(C.byref(h), blm._h, self.n_streams, self.max_chunk), construct=True)
-        self._h = h
+        self._open(blm._h, n_streams, max_chunk, blm.config.n_mels)
 
-    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
-        """no history, no frames, not ended, zero statistics for the listed streams (None: all)"""
-        super().reset(ids)
-
-    def finish_frames(self, stream: int) -> int:
-        return int(lib().melspec_blm_stream_finish_frames(self._h, stream))
-
-    def _split(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
+    def _cut(self, out: np.ndarray, frames: np.ndarray) -> List[np.ndarray]:
         res, cur = [], 0
         for f in frames:
             n = int(f) * self.n_mels
@@ -332,93 +351,70 @@ class BlmStreamBank(_Bank):
             cur += n
         return res
 
+    def reset(self, ids: Optional[Sequence[int]] = None) -> None:
+        """no history, no frames, not ended, zero statistics for the listed streams (None: all)"""
+        super().reset(ids)
+
+    def finish_frames(self, stream: int) -> int:
+        return int(self._fn("finish_frames")(self._h, stream))
+
+    def _finish(self, ids: Sequence[int], out_code: Optional[int] = None) -> List[np.ndarray]:
+        a = _u32(ids)
+        return self._host("finish_host", a, sum(self.finish_frames(int(s)) for s in a), out_code)[0]
+
+    def _finish_device(self, ids, d_out, out_offsets, stream, out_dtype: Optional[int] = None) -> np.ndarray:
+        return self._device("finish_device", ids, [0] * len(ids), d_out, out_offsets, stream, out_dtype)
+
     def push(self, ids: Sequence[int], chunks: Sequence) -> List[np.ndarray]:
         """Append chunks[i] (any length <= max_chunk; np.int16 chunks are 16-bit PCM, value = sample / 32768 exactly, and all chunks of
         one call have the same dtype) to stream ids[i]; returns the un-normalised columns each stream emitted, [n_mels, k_i]."""
-        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
-        out = np.empty(cap * self.n_mels, np.float32)
-        _check(lib().melspec_blm_stream_push_host(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
-                                                  a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
-        assert int(frames.sum()) == cap
-        return self._split(out, frames)
+        return self._push(ids, chunks)
 
     def finish(self, ids: Sequence[int]) -> List[np.ndarray]:
         """End the listed streams: the columns that read past the stream's end (zero padding), [n_mels, k_i]; nothing for an empty stream."""
-        a = _u32(ids)
-        cap = sum(self.finish_frames(int(s)) for s in a)
-        out, frames = np.empty(cap * self.n_mels, np.float32), np.zeros(a.shape[0], np.uint32)
-        _check(lib().melspec_blm_stream_finish_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(out), out.size, frames.ctypes.data_as(_u32p)))
-        return self._split(out, frames)
+        return self._finish(ids)
 
     def push_device(self, ids: Sequence[int], lens: Sequence[int], d_out: int, out_offsets=None, d_chunks: int = 0, pcm_dtype: int = PCM_F32,
                     src_offsets=None, stream: int = 0) -> np.ndarray:
         """d_chunks == 0: the chunks are at input_ptr, in f32; otherwise chunk i is lens[i] elements of pcm_dtype at d_chunks +
         src_offsets[i] elements (None: back to back).  Entry i's [n_mels, k_i] rows go to d_out + out_offsets[i] floats (None: back to back)."""
-        frames, n, (p_ids, p_lens, p_oo, p_so), _arrs = self._dev(ids, lens, out_offsets, src_offsets)
-        _check(lib().melspec_blm_stream_push_device(self._h, p_ids, C.c_void_p(d_chunks or None), int(pcm_dtype), p_so, p_lens, n, C.c_void_p(d_out or None),
-                                                    p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
-        return frames
+        return self._push_device(ids, lens, d_out, out_offsets, d_chunks, pcm_dtype, src_offsets, stream)
 
     def finish_device(self, ids: Sequence[int], d_out: int, out_offsets=None, stream: int = 0) -> np.ndarray:
-        frames, n, (p_ids, _p_lens, p_oo), _arrs = self._dev(ids, [0] * len(ids), out_offsets)
-        _check(lib().melspec_blm_stream_finish_device(self._h, p_ids, n, C.c_void_p(d_out or None), p_oo, frames.ctypes.data_as(_u32p), C.c_void_p(stream or None)))
-        return frames
+        return self._finish_device(ids, d_out, out_offsets, stream)
 
     # ---- f16 / bf16 rows out (melspec_blm_stream_*_io): the statistics stay those of the f32 rows ----
     def push_io(self, ids: Sequence[int], chunks: Sequence, out_dtype=None) -> List[np.ndarray]:
         """push() whose columns have the type out_dtype names: None np.float32, "f16" (or np.float16) np.float16, "bf16" the bfloat16 bit
         patterns as np.uint16 -- the f32 columns of push() rounded to nearest even.  stats() is what it is after the same push()es."""
-        a, pcm, flat, lens, cap, frames = self._gather(ids, chunks, True)
-        out_code = _out_code(out_dtype)
-        out = np.empty(cap * self.n_mels, _OUT_NUMPY[out_code])
-        _check(lib().melspec_blm_stream_push_host_io(self._h, a.ctypes.data_as(_u32p), flat.ctypes.data_as(C.c_void_p), pcm, lens.ctypes.data_as(_u32p),
-                                                     a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size, frames.ctypes.data_as(_u32p)))
-        assert int(frames.sum()) == cap
-        return self._split(out, frames)
+        return self._push(ids, chunks, _out_code(out_dtype))
 
     def finish_io(self, ids: Sequence[int], out_dtype=None) -> List[np.ndarray]:
         """finish() whose columns have the type of push_io's out_dtype"""
-        a = _u32(ids)
-        out_code = _out_code(out_dtype)
-        cap = sum(self.finish_frames(int(s)) for s in a)
-        out, frames = np.empty(cap * self.n_mels, _OUT_NUMPY[out_code]), np.zeros(a.shape[0], np.uint32)
-        _check(lib().melspec_blm_stream_finish_host_io(self._h, a.ctypes.data_as(_u32p), a.shape[0], out.ctypes.data_as(C.c_void_p), out_code, out.size,
-                                                       frames.ctypes.data_as(_u32p)))
-        return self._split(out, frames)
+        return self._finish(ids, _out_code(out_dtype))
 
     def supports_io(self, pcm_dtype: int, out_dtype: int) -> bool:
         """every valid pair of codes, on every frontend a bank can be created on"""
-        return self._supports_io(pcm_dtype, out_dtype)
+        return super().supports_io(pcm_dtype, out_dtype)
 
     def push_device_io(self, ids: Sequence[int], d_chunks: int, pcm_dtype: int, lens: Sequence[int], d_out: int, out_dtype: int,
                        src_offsets=None, out_offsets=None, stream: int = 0) -> np.ndarray:
         """push_device with typed rows: d_chunks / pcm_dtype / src_offsets as there; entry i's [n_mels, k_i] rows of out_dtype (OUT_F32 /
         OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back; a 16-bit entry may start at an odd element)."""
-        return self._push_device_io(ids, d_chunks, pcm_dtype, lens, d_out, out_dtype, src_offsets, out_offsets, stream)
+        return self._push_device(ids, lens, d_out, out_offsets, d_chunks, pcm_dtype, src_offsets, stream, out_dtype)
 
     def finish_device_io(self, ids: Sequence[int], d_out: int, out_dtype: int, out_offsets=None, stream: int = 0) -> np.ndarray:
         """finish_device whose columns of out_dtype (OUT_F32 / OUT_F16 / OUT_BF16) go to d_out + out_offsets[i] elements (None: back to back)"""
-        frames, n, (p_ids, _p_lens, p_oo), _arrs = self._dev(ids, [0] * len(ids), out_offsets)
-        _check(lib().melspec_blm_stream_finish_device_io(self._h, p_ids, n, C.c_void_p(d_out or None), int(out_dtype), p_oo, frames.ctypes.data_as(_u32p),
-                                                         C.c_void_p(stream or None)))
-        return frames
+        return self._finish_device(ids, d_out, out_offsets, stream, out_dtype)
 
     def stats(self, ids: Sequence[int]):
         """(mean [n, n_mels] f32, inv_std [n, n_mels] f32, counts [n] u64) of the columns the streams have emitted so far: inv_std =
         1 / (sqrt(M2 / max(count - 1, 1)) + 1e-5); mean 0 and inv_std 1e5 for a stream without a column"""
-        a = _u32(ids)
-        mean, inv_std = np.zeros((a.shape[0], self.n_mels), np.float32), np.zeros((a.shape[0], self.n_mels), np.float32)
-        counts = np.zeros(a.shape[0], np.uint64)
-        _check(lib().melspec_blm_stream_stats_host(self._h, a.ctypes.data_as(_u32p), a.shape[0], _fp(mean), _fp(inv_std), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
-        return mean, inv_std, counts
+        return self._stats(ids, 2)
 
     def stats_device(self, ids: Sequence[int], d_mean: int, d_inv_std: int, stream: int = 0) -> np.ndarray:
         """mean and inv_std to device memory ([n, n_mels] f32 each); returns the counts"""
-        a = _u32(ids)
-        counts = np.zeros(a.shape[0], np.uint64)
-        _check(lib().melspec_blm_stream_stats_device(self._h, a.ctypes.data_as(_u32p), a.shape[0], C.c_void_p(d_mean or None), C.c_void_p(d_inv_std or None),
-                                                     counts.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(stream or None)))
-        return counts
+        return self._stats_device(ids, stream, d_mean, d_inv_std)
 
 
 class RingBuffer:

@@ -75,12 +75,32 @@ def test_errors_without_a_device():
         lambda: L.melspec_fbank_stream_stats_host(None, u32, 1, f32, u64),
         lambda: L.melspec_fbank_stream_stats_device(None, u32, 1, None, u64, None),
     ]
-    for call in calls:
-        assert call() == _lib.ERR_INVALID_ARG
-        assert "NULL" in _lib.last_error()
-    assert L.melspec_fbank_stream_frames_after(None, 0, 400) == 0
-    assert not L.melspec_fbank_stream_input_ptr(None, 0)
-    L.melspec_fbank_stream_destroy(None)
+    # the handle is looked at first: before n == 0, before NULL ids / lens / samples / means, before the dtype codes
+    assert L.melspec_fbank_stream_create(None, None, 0, 0) == _lib.ERR_INVALID_ARG and "out is NULL" in _lib.last_error()
+    calls += [
+        lambda: L.melspec_fbank_stream_push_host(None, None, None, 0, None, 0, None, 0, None),
+        lambda: L.melspec_fbank_stream_push_host(None, None, None, 7, None, 1, None, 0, None),
+        lambda: L.melspec_fbank_stream_push_device(None, None, None, 1, None, None, 1, None, None, None, None),
+        lambda: L.melspec_fbank_stream_stats_host(None, None, 0, None, None),
+        lambda: L.melspec_fbank_stream_stats_host(None, None, 1, None, None),
+        lambda: L.melspec_fbank_stream_stats_device(None, None, 1, None, None, None),
+    ]
+    # a handle of another bank (the NeMo bank's tag in its first word) reads as NULL
+    other = (C.c_uint32 * 16)(0x4D4C424E)
+    calls += [
+        lambda: L.melspec_fbank_stream_reset(other, None, 0),
+        lambda: L.melspec_fbank_stream_push_host(other, u32, f32, 0, u32, 1, f32, 8, u32),
+        lambda: L.melspec_fbank_stream_stats_host(other, u32, 1, f32, u64),
+    ]
+    for k, call in enumerate(calls):
+        assert call() == _lib.ERR_INVALID_ARG, k
+        assert "fbank stream bank is NULL" in _lib.last_error(), (k, _lib.last_error())
+    for h_bad in (None, other):
+        assert L.melspec_fbank_stream_frames_after(h_bad, 0, 400) == 0
+        assert not L.melspec_fbank_stream_input_ptr(h_bad, 0)
+        assert L.melspec_fbank_stream_supports_io(h_bad, 0, 0) == 0
+        L.melspec_fbank_stream_destroy(h_bad)
+    assert other[0] == 0x4D4C424E and not any(other[i] for i in range(1, 16))
 
 
 def test_symbols_are_exported_and_bound():
