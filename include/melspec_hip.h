@@ -471,6 +471,44 @@ int melspec_blm_compute_uniform_device(melspec_blm *b, const float *d_pcm, uint6
  * floats (NULL: packed in clip order), cols_c = melspec_blm_padded_frames(b, h_lengths[c]).  Fused kernel (n_fft 512 / win_length 400). */
 int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                       uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream);
+/* The same batch with its clip table in DEVICE memory (a segmenter or VAD on the GPU produces it; nothing is copied back), as
+ * melspec_compute_ragged_device_desc and melspec_fbank_compute_ragged_device_desc: d_offsets / d_lengths in samples, d_out_offsets in
+ * floats (NULL: the clips' rows packed back to back in clip order).  Clip c = d_pcm[d_offsets[c] .. + d_lengths[c]) -> [n_mels][cols_c]
+ * f32 at d_out + d_out_offsets[c], cols_c = melspec_blm_padded_frames(len_c), normalised or not as the context's normalize_per_feature
+ * says.  The plan the host would build -- centred or plain frame counts, the pad_to rounding, the clips' lengths and valid frames, the
+ * normaliser's counter -- is built by one kernel on `stream`; the call reads no host table, queues no copy between host and device, and
+ * synchronises only when its plan buffer has to grow or was last used on another stream.  Everything else is stream-ordered and
+ * asynchronous.  Supported where the ragged call is: the fused geometry, n_fft 512 / win_length 400 (melspec_blm_supports_desc == 1).
+ * For every accepted clip the output is THE BITS melspec_blm_compute_ragged_device writes for the same tables on the host, in the same
+ * precision mode, whatever the two bounds, the clip's place in the batch, the other clips or what ran before.  (The normaliser's launch
+ * is sized from max_clip_samples; the order of a row's sum of squares, which depends on the batch's longest clip in the host-table call,
+ * is noted by the planner kernel from the true lengths and followed whatever the launch's size.)
+ * The two bounds exist so that nothing the launch sizes from the host can be overrun by what the device table says:
+ *   max_clip_samples   sizes the normaliser (its LDS rows hold the valid frames of a clip that long; a bound that does not fit LDS runs
+ *                      the one-thread-per-row pass);
+ *   max_total_columns  sizes the grid and the block table: an upper bound of the sum of cols_c -- with packed outputs, the capacity of
+ *                      d_out in columns.
+ * Rejection is decided by the planner kernel: (A) a clip with len > max_clip_samples is rejected and planned as a clip of length 0 -- no
+ * rows, no space in a packed output, none of its samples read; (B) if the columns of the clips that survive (A) sum to more than
+ * max_total_columns, every clip is rejected and nothing is written to d_out.  d_rejected (device, may be NULL) receives the number of
+ * rejected clips, 0 .. n_clips; every call that launches writes it.
+ * Checked in this order: NULL context (INVALID_ARG, "blm is NULL"); a context off the fused kernel (UNSUPPORTED, the ragged call's
+ * message); n_clips == 0 or a bound of 0 (OK, nothing queued, d_rejected untouched); NULL d_pcm / d_out / d_offsets / d_lengths
+ * (INVALID_ARG); max_total_columns >= 2^40 or a max_clip_samples whose row has 2^31 columns or more (UNSUPPORTED: the plan's integer
+ * widths).
+ * What it costs (1024 clips of 2-20 s, ms per call + synchronise, profiles/blm_desc.txt; A: this call with the tables resident on the
+ * device, B: what it replaces -- the two tables copied to the host with a synchronise, then melspec_blm_compute_ragged_device --,
+ * C: melspec_blm_compute_ragged_device with the tables already on the host), 80 / 128 mels, both precision modes, normalisation off and
+ * on: A takes 0.92-0.97 x the time of B (about 0.04 ms less per call: the two copies and their synchronise) and 0.97-1.00 x of C -- the
+ * planner kernel costs what C's host-side plan and its two small uploads cost.  What the call saves a pipeline is the synchronise
+ * itself, which this figure counts only as time.
+ * Not offered: a _desc form of the split output (its rounds wait for every wave of the workgroup -- "a round with a wave missing would
+ * never end", blm_stats_plan.hpp -- so a unit count that only the device knows needs a design of its own); _desc with int16 PCM in or
+ * 16-bit rows out; a ragged Kaldi split. */
+int melspec_blm_supports_desc(const melspec_blm *b);     /* 1: the fused geometry (n_fft 512 / win_length 400), as the ragged call */
+int melspec_blm_compute_ragged_device_desc(melspec_blm *b, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths,
+                                           uint32_t n_clips, float *d_out, const uint64_t *d_out_offsets, uint64_t max_total_columns,
+                                           uint64_t max_clip_samples, uint32_t *d_rejected, void *stream);
 /* The same from host memory, many clips per call (BatchLogMelSpectrogram::compute is per clip, src/mel.rs:299): clip i ->
  * [n_mels][cols_i] at out + out_offsets[i] floats (NULL: packed); *total_columns = sum of cols_i.  Host pipeline as above. */
 int melspec_blm_compute_batch_host(melspec_blm *b, const float *samples, const uint64_t *offsets, const uint64_t *lengths, uint32_t n_clips,
@@ -546,8 +584,8 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
  * MELSPEC_PRECISION_F32 A takes 0.74 x (80 mels) / 0.65 x (128 mels) the time of C and 1.16 x / 1.19 x of B; in the default (f64) mode
  * 0.96 x / 0.86 x of C and 1.37 x / 1.41 x of B.  A beats C in both modes there -- at 80 mels in f64 by 4 % only, a margin inside the
  * spread of the timed calls -- because the ragged normaliser is dearer than the uniform one, not because the f64 kernel got faster.
- * Not offered: int16 PCM in or 16-bit rows out for the split, a device-table (_desc) form, a ragged form of the Kaldi split
- * (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
+ * Not offered: int16 PCM in or 16-bit rows out for the split, a device-table (_desc) form of the split (the frontend's plain ragged call has
+ * one: melspec_blm_compute_ragged_device_desc), a ragged form of the Kaldi split (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
 int melspec_blm_compute_ragged_device_split(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                             uint32_t n_clips, float *d_rows, const uint64_t *h_rows_offsets, float *d_mean,
                                             float *d_inv_std, void *stream);

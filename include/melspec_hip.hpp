@@ -341,6 +341,16 @@ public:
                                      const std::uint64_t *rows_offsets, float *d_mean, float *d_inv_std, void *stream = nullptr) {
         detail::check(melspec_blm_compute_ragged_device_split(b_, d_pcm, offsets, lengths, n_clips, d_rows, rows_offsets, d_mean, d_inv_std, stream), false);
     }
+    // the ragged batch with its clip table in device memory (melspec_blm_compute_ragged_device_desc): u64 offsets / lengths / output offsets
+    // (nullptr: packed) on the device, a planner kernel instead of host tables; max_total_columns / max_clip_samples bound what the table
+    // may ask for, *d_rejected (device, may be nullptr) receives the number of rejected clips
+    bool supports_desc() const { return melspec_blm_supports_desc(b_) != 0; }
+    void compute_ragged_device_desc(const float *d_pcm, const std::uint64_t *d_offsets, const std::uint64_t *d_lengths, std::uint32_t n_clips, float *d_out,
+                                    const std::uint64_t *d_out_offsets, std::uint64_t max_total_columns, std::uint64_t max_clip_samples,
+                                    std::uint32_t *d_rejected = nullptr, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_ragged_device_desc(b_, d_pcm, d_offsets, d_lengths, n_clips, d_out, d_out_offsets, max_total_columns, max_clip_samples,
+                                                             d_rejected, stream), false);
+    }
     struct Split {
         Array2f rows;                      // (n_mels, cols), un-normalised
         std::vector<float> mean, inv_std;  // (n_mels)

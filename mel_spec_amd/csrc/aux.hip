@@ -239,6 +239,38 @@ int plan_ragged_device(DevicePlan &dp, hipStream_t stream, const float *d_pcm, f
     return MELSPEC_OK;
 }
 
+int blm_plan_ragged_device(DevicePlan &dp, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *d_off, const uint64_t *d_len,
+                           const uint64_t *d_out_off, uint32_t n_clips, const BlmDescGeom &geom, uint64_t max_total_columns, uint64_t max_clip_samples,
+                           uint32_t *d_rejected, BatchPlan &pl, BlmDevicePlanAux &aux) {
+    const uint64_t max_units = blm_desc_max_units(max_total_columns, n_clips);
+    const uint64_t max_blocks = blm_desc_max_blocks(max_units);
+    const size_t bytes = blm_desc_bytes(n_clips, max_blocks);
+    if (dp.used && dp.last != stream) HIP_TRY(hipStreamSynchronize(dp.last));
+    if (bytes > dp.buf.cap && dp.used) HIP_TRY(hipStreamSynchronize(dp.last));
+    int rc = dp.buf.ensure(bytes);
+    if (rc) return rc;
+    dp.used = true; dp.last = stream;
+    BlmPlanParams q{};
+    q.d_off = d_off; q.d_len = d_len; q.d_out_off = d_out_off; q.n_clips = n_clips;
+    q.geom = geom;
+    q.max_total_columns = max_total_columns; q.max_clip_samples = max_clip_samples;
+    q.plan = static_cast<uint64_t *>(dp.buf.p);
+    q.max_blocks = max_blocks;
+    q.d_rejected = d_rejected;
+    hipLaunchKernelGGL(blm_plan_ragged_device_kernel, dim3(1), dim3(1024), 0, stream, q);
+    HIP_TRY(hipGetLastError());
+    const BlmDescTables t = blm_desc_tables(q.plan, n_clips);
+    BatchDesc &b = pl.desc;
+    b = BatchDesc{};
+    b.pcm = d_pcm; b.out = d_out; b.n_clips = n_clips; b.n_units = max_units; b.frames_per_unit = static_cast<int>(kBlmDescFramesPerUnit);
+    b.d_off = t.off; b.d_frames = t.frames; b.d_out_off = t.out_off; b.d_unit_prefix = t.prefix;
+    b.d_unit_block = t.blk;
+    b.d_n_units = t.prefix + n_clips;
+    pl.total_frames = max_total_columns;
+    aux.d_len = t.len; aux.d_valid = t.valid; aux.d_ctr = t.ctr; aux.d_order = t.order;
+    return MELSPEC_OK;
+}
+
 }  // namespace host
 }  // namespace melspec
 

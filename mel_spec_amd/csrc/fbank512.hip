@@ -588,6 +588,7 @@ struct melspec_blm {
     GenericTables gt;
     RaggedScratch ragged;
     StreamBuf aux;              // ragged batches: per-clip sample counts and valid frames, the normaliser's group counter
+    DevicePlan dplan;           // melspec_blm_compute_ragged_device_desc: the plan and that block, written by blm_plan_ragged_device_kernel
     FbankFastTables ft;
     DevBuf d_blob;
     size_t fast_lds = 0;
@@ -664,16 +665,9 @@ void blm_norm_shape_uniform(uint64_t valid, size_t &stride, size_t &per, int &pe
     }
     if (per > 64) per = 64;
 }
-// ragged batches: rows staged whole in LDS like the uniform pass (sized for the longest clip), groups of rows from a counter
-void blm_norm_shape_ragged(uint64_t longest, size_t &stride, size_t &per, int &per_cu) {
-    stride = (static_cast<size_t>(longest) + 3 + 31) & ~static_cast<size_t>(31);
-    if ((stride / 4) % 2 == 0) stride += 4;
-    const size_t fixed = (2 * 64 + kBlmNormThreads + 4 * 64 + 4) * sizeof(float);
-    per = (static_cast<size_t>(38) * 1024 - fixed) / (stride * sizeof(float));
-    per_cu = 4;
-    if (per < 4) { per = (static_cast<size_t>(150) * 1024 - fixed) / (stride * sizeof(float)); per_cu = 1; }
-    if (per > 64) per = 64;
-}
+// ragged batches: blm_norm_shape_ragged (blm_desc_plan.hpp: the planner kernel of the _desc call evaluates it too) -- rows staged whole in
+// LDS like the uniform pass (sized for the longest clip), groups of rows from a counter
+static_assert(kBlmDescNormThreads == kBlmNormThreads && kBlmDescFramesPerUnit == kFbFPW && kBlmDescUnitBlock == kUnitBlock, "blm_desc_plan.hpp restates the kernels' constants");
 
 // the fused kernels' parameters of a batch of this context (fbank_fast_params' counterpart); the caller adds what its kind of batch has
 FbankFastParams blm_fast_params(const melspec_blm *b, const BatchDesc &desc) {
@@ -824,6 +818,35 @@ int launch_blm_norm_ragged(melspec_blm *b, const BlmNormRows &r, uint64_t longes
     if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, split ? "blm_normalize_ragged_io_kernel launch failed" : "blm_normalize_ragged_kernel launch failed");
     return MELSPEC_OK;
 }
+
+// ... in place over a batch planned on the device: `longest` is the valid frames of the caller's bound on a clip's samples, which sizes the
+// launch; d_order: the order of a row's sum of squares, noted by the planner (blm_normalize_ragged_desc_kernel says what for)
+int launch_blm_norm_ragged_desc(melspec_blm *b, float *rows_at, uint32_t n_clips, const BatchDesc &desc, const BlmDevicePlanAux &aux, uint64_t longest, hipStream_t s) {
+    const int nm = b->cfg.n_mels;
+    const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+    size_t stride, per;
+    int per_cu;
+    blm_desc_norm_launch(longest, stride, per, per_cu);
+    BlmNormRaggedDescParams q{};
+    BlmNormRaggedParams &rp = q.r;
+    rp.out = rows_at; rp.d_out_off = desc.d_out_off; rp.d_cols = desc.d_frames; rp.d_valid = aux.d_valid;
+    rp.n_clips = n_clips; rp.n_mels = nm;
+    rp.ctr = aux.d_ctr;
+    q.d_order = aux.d_order;
+    if (per < 1 || longest >= (1ull << 31)) {
+        hipLaunchKernelGGL(blm_normalize_ragged_desc_slow_kernel, dim3(grid_for((rows + kBlmNormThreads - 1) / kBlmNormThreads, b->dev.cus, 4)), dim3(kBlmNormThreads), 0, s, q);
+        if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, "blm_normalize_ragged_desc_slow_kernel launch failed");
+        return MELSPEC_OK;
+    }
+    static std::atomic<uint64_t> attr_done;
+    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(blm_normalize_ragged_desc_kernel)", &blm_normalize_ragged_desc_kernel)) return rc;
+    rp.rows_per_group = static_cast<int>(per); rp.lds_stride = static_cast<int>(stride);
+    rp.longest = static_cast<uint32_t>(longest);
+    const size_t lds = (per * stride + 2 * per + kBlmNormThreads + kBlmNormInfo * per + 4) * sizeof(float);
+    hipLaunchKernelGGL(blm_normalize_ragged_desc_kernel, dim3(grid_for((rows + per - 1) / per, b->dev.cus, per_cu)), dim3(kBlmNormThreads), lds, s, q);
+    if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, "blm_normalize_ragged_desc_kernel launch failed");
+    return MELSPEC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -903,7 +926,7 @@ void melspec_blm_destroy(melspec_blm *b) {
     if (b->dev.device >= 0) (void)hipSetDevice(b->dev.device);
     if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
     b->d_blob.release(); b->f32.d_blob.release(); b->h2d.release(); b->d2h.release(); b->gt.release(); b->ragged.release(); b->aux.release(); b->pipe.release(); b->rows32.release();
-    b->stats.release();
+    b->stats.release(); b->dplan.release();
     delete b;
 }
 
@@ -1038,6 +1061,40 @@ static int blm_ragged(melspec_blm *b, const void *vd_pcm, const uint64_t *h_offs
 int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                       uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
     return blm_ragged(b, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, 0);
+}
+
+// The same with the clip table in device memory: see include/melspec_hip.h.  The plan, d_len / d_valid and the normaliser's counter come
+// from blm_plan_ragged_device_kernel; the launch is blm_ragged's, sized from the caller's two bounds -- n_units is the bound, the true count
+// is at d_n_units, which every kernel route512 picks for a kLayout batch reads once per wave before its first round (batch_n_units in
+// fbank512_wave_body.inc: one value for the whole workgroup, the planner having finished before the launch starts).
+int melspec_blm_supports_desc(const melspec_blm *b) { return b && b->fast ? 1 : 0; }
+
+int melspec_blm_compute_ragged_device_desc(melspec_blm *b, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths, uint32_t n_clips,
+                                           float *d_out, const uint64_t *d_out_offsets, uint64_t max_total_columns, uint64_t max_clip_samples,
+                                           uint32_t *d_rejected, void *stream) {
+    if (!b) return fail(MELSPEC_ERR_INVALID_ARG, "blm is NULL");
+    if (!b->fast) return fail(MELSPEC_ERR_UNSUPPORTED, "ragged batches need the fused kernel (n_fft = 512, win_length = 400)");
+    if (n_clips == 0 || max_total_columns == 0 || max_clip_samples == 0) return MELSPEC_OK;
+    if (!d_pcm || !d_out || !d_offsets || !d_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "device pointer is NULL");
+    const BlmDescGeom geom{static_cast<uint32_t>(b->cfg.n_fft), static_cast<uint32_t>(b->cfg.hop_length), static_cast<uint32_t>(b->cfg.pad_to), b->cfg.center ? 1u : 0u,
+                           static_cast<uint32_t>(b->cfg.n_mels)};
+    if (!blm_desc_bounds_ok(geom, max_total_columns, max_clip_samples))
+        return fail(MELSPEC_ERR_UNSUPPORTED, "max_total_columns (< 2^40) or max_clip_samples (a row of < 2^31 columns) is too large for the device plan");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
+    BatchPlan pl;
+    BlmDevicePlanAux aux{};
+    int rc = blm_plan_ragged_device(b->dplan, s, d_pcm, d_out, d_offsets, d_lengths, d_out_offsets, n_clips, geom, max_total_columns, max_clip_samples, d_rejected, pl, aux);
+    if (rc) return rc;
+    FbankFastParams fp = blm_fast_params(b, pl.desc);
+    fp.b.mel_major = 1;
+    fp.b.sync_rounds = kNemoSync;
+    fp.d_len = aux.d_len;
+    fp.d_valid = aux.d_valid;
+    if ((rc = launch_nemo_mel(b, fp, 0, s))) return rc;
+    if (b->cfg.normalize_per_feature)
+        rc = launch_blm_norm_ragged_desc(b, d_out, n_clips, pl.desc, aux, blm_desc_valid_frames(geom, max_clip_samples), s);
+    return rc;
 }
 
 // ---- int16 PCM in / f16, bf16 rows out: see include/melspec_hip.h ----
@@ -1240,7 +1297,8 @@ int melspec_blm_release_scratch(melspec_blm *b) {
     if (int rc = b->aux.release_after(b->stream)) return rc;
     if (int rc = b->rows32.release_after(b->stream)) return rc;
     if (int rc = b->stats.release_after(b->stream)) return rc;
-    b->pipe.release(); b->ragged.release(); b->h2d.release(); b->d2h.release();
+    if (b->dplan.used && b->dplan.last != b->stream) HIP_TRY(hipStreamSynchronize(b->dplan.last));
+    b->pipe.release(); b->ragged.release(); b->dplan.release(); b->h2d.release(); b->d2h.release();
     return MELSPEC_OK;
 }
 

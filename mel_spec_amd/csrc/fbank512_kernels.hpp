@@ -721,6 +721,78 @@ __global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normali
     const uint64_t *const d_src_off = p.d_out_off, *const d_dst_off = p.d_out_off;
 #include "fbank512_norm_ragged_body.inc"
 }
+
+// ... for a batch planned on the device (melspec_blm_compute_ragged_device_desc).  The host sizes that launch from the caller's bound on
+// the longest clip, which may be far above the batch's own longest clip; the rows staged per workgroup follow the bound, and with them
+// the threads a row has (PP).  The planner kernel, which sees the true lengths, notes how many threads share a row's sum of squares in
+// the launch of melspec_blm_compute_ragged_device for the same tables (blm_desc_norm_order, blm_desc_plan.hpp; never more than PP): the
+// first d_order[0] threads of a row sum in that order, and 1 / std is that call's, bit for bit, whatever the bound.
+struct BlmNormRaggedDescParams {
+    BlmNormRaggedParams r;
+    const uint32_t *d_order;
+};
+__global__ __launch_bounds__(kBlmNormThreads) MS_NORM_OCCUPANCY void blm_normalize_ragged_desc_kernel(const BlmNormRaggedDescParams q) {
+    const BlmNormRaggedParams &p = q.r;
+    using Out = float;
+    constexpr bool kSplit = false;
+    const float *const src = p.out;
+    Out *const dst = p.out;
+    const uint64_t *const d_src_off = p.d_out_off, *const d_dst_off = p.d_out_off;
+    const int launch_pp = kBlmNormThreads / p.rows_per_group;
+    const int noted = __builtin_amdgcn_readfirstlane(static_cast<int>(q.d_order[0]));
+    const int order = noted >= 1 && noted <= launch_pp ? noted : launch_pp;
+#define MS_NORM_RAGGED_ORDER order
+#include "fbank512_norm_ragged_body.inc"
+#undef MS_NORM_RAGGED_ORDER
+}
+
+// The same when the bound's rows do not fit LDS: a thread per row from HBM, as blm_normalize_kernel's rows_per_group == 0 form -- but a
+// batch whose own longest clip does fit is summed, serially, in the order the LDS pass of the host-table call has (d_order[0] partial sums
+// of four accumulators each, folded four at a time; (v - mean) * (1 / sd)), and only a batch that the host-table call sends down this path
+// too (d_order[0] == 0) gets that path's left fold and its division.
+__global__ __launch_bounds__(kBlmNormThreads) void blm_normalize_ragged_desc_slow_kernel(const BlmNormRaggedDescParams q) {
+    const BlmNormRaggedParams &p = q.r;
+    const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
+    const uint32_t order = q.d_order[0];
+    for (uint64_t row = (uint64_t)blockIdx.x * kBlmNormThreads + threadIdx.x; row < rows; row += (uint64_t)gridDim.x * kBlmNormThreads) {
+        const uint64_t clip = row / p.n_mels, m = row - clip * p.n_mels;
+        const uint32_t valid = static_cast<uint32_t>(p.d_valid[clip]);
+        if (valid == 0) continue;
+        float *r = p.out + p.d_out_off[clip] + m * p.d_cols[clip];
+        if (order == 0) {
+            float mean, sd;
+            blm_row_stats_slow(r, valid, mean, sd);
+            for (uint32_t k = 0; k < valid; ++k) r[k] = f32_div_rn(r[k] - mean, sd);
+            continue;
+        }
+        float s = 0.0f;
+        for (uint32_t k = 0; k < valid; ++k) s += r[k];
+        const float mean = f32_div_rn(s, static_cast<float>(valid));
+        float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
+        for (uint32_t pt = 0; pt < order; ++pt) {
+            float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
+            uint32_t k = pt;
+            for (; k + 3 * order < valid; k += 4 * order) {
+                const float c0 = r[k] - mean, c1 = r[k + order] - mean, c2 = r[k + 2 * order] - mean, c3 = r[k + 3 * order] - mean;
+                a0 += c0 * c0; a1 += c1 * c1; a2 += c2 * c2; a3 += c3 * c3;
+            }
+            for (; k < valid; k += order) {
+                const float c = r[k] - mean;
+                a0 += c * c;
+            }
+            const float part = (a0 + a1) + (a2 + a3);
+            if (pt >= (order & ~3u) || (pt & 3u) == 0) q0 += part;
+            else if ((pt & 3u) == 1) q1 += part;
+            else if ((pt & 3u) == 2) q2 += part;
+            else q3 += part;
+        }
+        float denom = static_cast<float>(valid) - 1.0f;
+        denom = denom < 1.0f ? 1.0f : denom;
+        const float sd = __builtin_sqrtf(f32_div_rn((q0 + q1) + (q2 + q3), denom)) + 1e-5f;
+        const float rsd = f32_div_rn(1.0f, sd);
+        for (uint32_t k = 0; k < valid; ++k) r[k] = (r[k] - mean) * rsd;
+    }
+}
 #endif
 
 // CMN (src/fbank.rs:224-233): per clip and mel column subtract the f32 mean over the clip's frames.  The reference's

@@ -6,6 +6,15 @@
 //   Out, kSplit           the row type written; false: in place, true: src -> dst
 //   src, dst              the f32 rows read and the rows written (in place: the same)
 //   d_src_off, d_dst_off  per clip the first element in src / dst
+// and may define MS_NORM_RAGGED_ORDER (blm_normalize_ragged_desc_kernel): the number of threads, at most PP, that share a row's sum of squares
+// -- the order of that sum -- where it is not the launch's own PP; without the macro the text below is what it always was.
+#ifndef MS_NORM_RAGGED_ORDER
+#define MS_NORM_RAGGED_ORDER PP
+#define MS_NORM_RAGGED_IN_ORDER(pt) true
+#define MS_NORM_RAGGED_ORDER_DEFAULT
+#else
+#define MS_NORM_RAGGED_IN_ORDER(pt) ((pt) < MS_NORM_RAGGED_ORDER)
+#endif
     extern __shared__ __attribute__((aligned(16))) float tile[];
     const uint64_t rows = (uint64_t)p.n_clips * p.n_mels;
     const int tid = threadIdx.x;
@@ -82,18 +91,18 @@
         __syncthreads();
         {
             const int r = tid / PP, pt = tid - r * PP;
-            if (r < nr) {
+            if (r < nr && MS_NORM_RAGGED_IN_ORDER(pt)) {
                 const uint32_t valid = info[kInfo * r + 2];
                 const uint32_t a = (src_f + info[kInfo * r]) & 3u;
                 const float *row = tile + (size_t)r * S + a;
                 const float mean = stat[2 * r];
                 float a0 = 0.0f, a1 = 0.0f, a2 = 0.0f, a3 = 0.0f;
                 uint32_t k = pt;
-                for (; k + 3 * PP < valid; k += 4 * PP) {
-                    const float c0 = row[k] - mean, c1 = row[k + PP] - mean, c2 = row[k + 2 * PP] - mean, c3 = row[k + 3 * PP] - mean;
+                for (; k + 3 * MS_NORM_RAGGED_ORDER < valid; k += 4 * MS_NORM_RAGGED_ORDER) {
+                    const float c0 = row[k] - mean, c1 = row[k + MS_NORM_RAGGED_ORDER] - mean, c2 = row[k + 2 * MS_NORM_RAGGED_ORDER] - mean, c3 = row[k + 3 * MS_NORM_RAGGED_ORDER] - mean;
                     a0 += c0 * c0; a1 += c1 * c1; a2 += c2 * c2; a3 += c3 * c3;
                 }
-                for (; k < valid; k += PP) {
+                for (; k < valid; k += MS_NORM_RAGGED_ORDER) {
                     const float c = row[k] - mean;
                     a0 += c * c;
                 }
@@ -105,8 +114,8 @@
             const float *pp = part + tid * PP;
             float q0 = 0.0f, q1 = 0.0f, q2 = 0.0f, q3 = 0.0f;
             int i = 0;
-            for (; i + 3 < PP; i += 4) { q0 += pp[i]; q1 += pp[i + 1]; q2 += pp[i + 2]; q3 += pp[i + 3]; }
-            for (; i < PP; ++i) q0 += pp[i];
+            for (; i + 3 < MS_NORM_RAGGED_ORDER; i += 4) { q0 += pp[i]; q1 += pp[i + 1]; q2 += pp[i + 2]; q3 += pp[i + 3]; }
+            for (; i < MS_NORM_RAGGED_ORDER; ++i) q0 += pp[i];
             float denom = static_cast<float>(info[kInfo * tid + 2]) - 1.0f;
             denom = denom < 1.0f ? 1.0f : denom;
             const float sd = __builtin_sqrtf(f32_div_rn((q0 + q1) + (q2 + q3), denom)) + 1e-5f;
@@ -151,3 +160,8 @@
         }
         __syncthreads();
     }
+#ifdef MS_NORM_RAGGED_ORDER_DEFAULT
+#undef MS_NORM_RAGGED_ORDER
+#undef MS_NORM_RAGGED_ORDER_DEFAULT
+#endif
+#undef MS_NORM_RAGGED_IN_ORDER

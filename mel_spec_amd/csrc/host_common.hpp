@@ -44,6 +44,7 @@
 #include "tables.hpp"
 #include "ctx_route.hpp"
 #include "fused512_route.hpp"
+#include "blm_desc_plan.hpp"
 
 namespace melspec {
 namespace host {
@@ -335,6 +336,16 @@ struct DevicePlan {
 int plan_ragged_device(DevicePlan &dp, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *d_off, const uint64_t *d_len,
                        const uint64_t *d_out_off, uint32_t n_clips, uint64_t frame_len, uint64_t frame_shift, uint32_t words_per_frame,
                        int frames_per_unit, uint64_t max_total_frames, BatchPlan &pl);      // aux.hip
+// The NeMo / Parakeet frontend's form (blm_plan_ragged_device_kernel; blm_desc_plan.hpp has the layout and the rules): the batch in pl,
+// d_len / d_valid / the normaliser's counter and sum order in the same buffer, the number of rejected clips at d_rejected (may be null)
+struct BlmDevicePlanAux {
+    const uint64_t *d_len, *d_valid;
+    unsigned *d_ctr;
+    const uint32_t *d_order;
+};
+int blm_plan_ragged_device(DevicePlan &dp, hipStream_t stream, const float *d_pcm, float *d_out, const uint64_t *d_off, const uint64_t *d_len,
+                           const uint64_t *d_out_off, uint32_t n_clips, const BlmDescGeom &geom, uint64_t max_total_columns, uint64_t max_clip_samples,
+                           uint32_t *d_rejected, BatchPlan &pl, BlmDevicePlanAux &aux);      // aux.hip
 
 inline unsigned grid_for(uint64_t units, int cus, int per_cu) {
     const uint64_t cap = static_cast<uint64_t>(cus > 0 ? cus : 256) * per_cu;

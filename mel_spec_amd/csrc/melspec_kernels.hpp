@@ -7,7 +7,7 @@
 //   fbank512_kernels.hpp     fused 512-point family: fbank512_wave_kernel (Kaldi / NeMo / Whisper-512, f64 and f32),
 //                            fbank512_clip_kernel, cmn_kernel, blm_normalize[_ragged]_kernel
 //   generic_kernels.hpp      generic_frame_kernel, generic_stft_kernel, pow2_frame_kernel, mel_stage[_jobs]_kernel (f64)
-//   aux_kernels.hpp          stream_scatter / stream_carry, plan_ragged_device_kernel, synth_pcm_kernel
+//   aux_kernels.hpp          stream_scatter / stream_carry, plan_ragged_device_kernel, blm_plan_ragged_device_kernel, synth_pcm_kernel
 #pragma once
 #include "kernels_common.hpp"
 #include "whisper400_kernels.hpp"

@@ -765,6 +765,18 @@ def blm_compute_ragged_split(fe: BatchLogMelSpectrogram, clips) -> list:
     return [(r, stat[0, i].copy(), stat[1, i].copy()) if r.shape[1] else (r, None, None) for i, r in enumerate(rows)]
 
 
+# -- the ragged call with its clip table in device memory (melspec_blm_compute_ragged_device_desc): module-level for the same reason -----------
+def blm_compute_ragged_device_desc(fe: BatchLogMelSpectrogram, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
+                                   max_total_columns: int, max_clip_samples: int, d_rejected: int = 0, stream: int = 0) -> None:
+    """compute_ragged_device with the u64 tables (offsets, lengths, output offsets in floats; d_out_offsets 0 = packed in clip order) read from
+    device memory by a planner kernel: per accepted clip the bits of compute_ragged_device on the same tables.  max_total_columns bounds
+    the sum of the clips' padded frames, max_clip_samples a clip's length; a longer clip is rejected (no rows), a batch past the total
+    is rejected whole, and the u32 at d_rejected (0 = not wanted) receives the number of rejected clips.  Asynchronous on `stream`."""
+    _check(lib().melspec_blm_compute_ragged_device_desc(fe._h, C.c_void_p(d_pcm), C.c_void_p(d_offsets), C.c_void_p(d_lengths), n_clips, C.c_void_p(d_out),
+                                                        C.c_void_p(d_out_offsets) if d_out_offsets else None, max_total_columns, max_clip_samples,
+                                                        C.c_void_p(d_rejected) if d_rejected else None, C.c_void_p(stream)))
+
+
 class SparseMelFilterbank:
     """SparseMelFilterbank (src/mel.rs:40-168) + log_mel_spectrogram / norm_mel / norm_mel_vec (:436-469) on the GPU (melspec_bank_*)."""
 

@@ -89,6 +89,10 @@ unsafe extern "C" {
     fn melspec_blm_supports_split(b: *const BlmHandle) -> c_int;
     fn melspec_blm_compute_uniform_device_split(b: *mut BlmHandle, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, d_rows: *mut f32,
                                                 d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_blm_supports_desc(b: *const BlmHandle) -> c_int;
+    fn melspec_blm_compute_ragged_device_desc(b: *mut BlmHandle, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
+                                              d_out: *mut f32, d_out_offsets: *const u64, max_total_columns: u64, max_clip_samples: u64,
+                                              d_rejected: *mut u32, stream: *mut c_void) -> c_int;
     fn melspec_blm_compute_ragged_device_split(b: *mut BlmHandle, d_pcm: *const f32, h_offsets: *const u64, h_lengths: *const u64, n_clips: u32,
                                                d_rows: *mut f32, h_rows_offsets: *const u64, d_mean: *mut f32, d_inv_std: *mut f32,
                                                stream: *mut c_void) -> c_int;
@@ -836,6 +840,25 @@ impl HipBatchLogMel {
         }
         check(melspec_blm_compute_ragged_device_split(self.b, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_rows,
                                                       rows_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), d_mean, d_inv_std, stream))
+    }
+    /// Additive: does this frontend take ragged batches whose clip table lives in device memory (the fused geometry, as the ragged call)?
+    pub fn supports_desc(&self) -> bool {
+        unsafe { melspec_blm_supports_desc(self.b) != 0 }
+    }
+    /// Additive: the ragged batch with its clip table in device memory -- `d_offsets` / `d_lengths` (samples) and `d_out_offsets` (floats,
+    /// null: packed in clip order) are device pointers to `n_clips` u64 each, read by a planner kernel on `stream`; nothing is copied back.
+    /// Clip `c` -> `[n_mels][cols_c]` at `d_out + d_out_offsets[c]`, the bits of the host-table ragged call.  A clip longer than
+    /// `max_clip_samples` is rejected (no rows); if the accepted clips' columns sum to more than `max_total_columns` every clip is; the u32
+    /// at `d_rejected` (device, may be null) receives the number of rejected clips.
+    ///
+    /// # Safety
+    /// The three tables must hold `n_clips` entries on the device; every clip of at most `max_clip_samples` samples must lie inside the buffer
+    /// behind `d_pcm`; `d_out` must hold `n_mels * max_total_columns` floats (packed), or every clip's rows where `d_out_offsets` puts them.
+    pub unsafe fn compute_ragged_device_desc(&mut self, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32, d_out: *mut f32,
+                                             d_out_offsets: *const u64, max_total_columns: u64, max_clip_samples: u64, d_rejected: *mut u32,
+                                             stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_blm_compute_ragged_device_desc(self.b, d_pcm, d_offsets, d_lengths, n_clips, d_out, d_out_offsets, max_total_columns, max_clip_samples,
+                                                     d_rejected, stream))
     }
     /// Additive: `compute` without the normaliser's pass: `(rows (n_mels, cols), mean, inv_std)` of one host clip.
     pub fn compute_split(&mut self, samples: &[f32]) -> Result<(ndarray::Array2<f32>, Vec<f32>, Vec<f32>), HipError> {
