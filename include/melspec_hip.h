@@ -563,7 +563,8 @@ int melspec_blm_compute_host_io(melspec_blm *b, const void *samples, int pcm_dty
  * A clip_len without a valid frame returns MELSPEC_OK and writes nothing.  Supported: the fused geometry (n_fft 512 / win_length 400)
  * with the 80- or 128-mel Slaney bank, both precision modes (melspec_blm_supports_split == 1; the condition of the 16-bit ends); every
  * other context returns MELSPEC_ERR_UNSUPPORTED, names its geometry in melspec_last_error and touches no buffer.  Uniform batches,
- * ragged batches (below) and the single host clip; f32 samples in and f32 rows out only: no 16-bit ends. */
+ * ragged batches (below) and the single host clip; these three calls take f32 samples and write f32 rows, the _split_io calls further
+ * below have the 16-bit ends. */
 int melspec_blm_supports_split(const melspec_blm *b);
 int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
                                              uint32_t n_clips, float *d_rows, float *d_mean, float *d_inv_std, void *stream);
@@ -584,14 +585,52 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
  * MELSPEC_PRECISION_F32 A takes 0.74 x (80 mels) / 0.65 x (128 mels) the time of C and 1.16 x / 1.19 x of B; in the default (f64) mode
  * 0.96 x / 0.86 x of C and 1.37 x / 1.41 x of B.  A beats C in both modes there -- at 80 mels in f64 by 4 % only, a margin inside the
  * spread of the timed calls -- because the ragged normaliser is dearer than the uniform one, not because the f64 kernel got faster.
- * Not offered: int16 PCM in or 16-bit rows out for the split, a device-table (_desc) form of the split (the frontend's plain ragged call has
- * one: melspec_blm_compute_ragged_device_desc), a ragged form of the Kaldi split (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
+ * Not offered: a device-table (_desc) form of the split (the frontend's plain ragged call has one: melspec_blm_compute_ragged_device_desc),
+ * a ragged form of the Kaldi split (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
 int melspec_blm_compute_ragged_device_split(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                             uint32_t n_clips, float *d_rows, const uint64_t *h_rows_offsets, float *d_mean,
                                             float *d_inv_std, void *stream);
 /* One clip from host memory: rows = [n_mels][cols] (capacity in floats), mean / inv_std = [n_mels]; *n_rows = n_mels, *n_cols = cols. */
 int melspec_blm_compute_host_split(melspec_blm *b, const float *samples, size_t n_samples, float *rows, size_t rows_capacity_floats,
                                    float *mean, float *inv_std, size_t *n_rows, size_t *n_cols);
+/* ---- the split output with 16-bit ends: int16 PCM in, f16 / bf16 rows out, f32 mean and 1 / std ----------------------------------------
+ * The two contracts above joined, nothing new invented -- what a server that holds int16 PCM and wants half-precision features has been
+ * building from parts: 2 bytes read per sample, 2 bytes written per element, no scratch rows and no second pass (the normalised _io call
+ * writes f32 rows into a scratch and reads them back: about 800 of its 1120 bytes per frame at 80 mels).
+ *   samples   MELSPEC_PCM_S16: int16 * 2^-15, exactly; the call behaves as the f32 split call on the batch converted by
+ *             `v as f32 / 32768.0`, pre-emphasis applied to the converted samples.
+ *   d_rows    every element is the element the f32 split call writes, rounded to nearest even ONCE (a NaN stays a NaN); pad columns are
+ *             +0; pad columns and clips without a frame behave as in the f32 split calls.
+ *   d_mean, d_inv_std  f32, packed [clip][n_mels]: THE BITS of the f32 split call -- the statistics of the f32 values, not of the rounded
+ *             rows (as the normalised _io call defines its statistics) --, a function of the clip's samples, its length and the precision
+ *             mode only.  A consumer's (row - mean) * inv_std therefore carries the row's rounding (half an ulp of the row type) times
+ *             inv_std.
+ * Strides, offsets and capacities count ELEMENTS; natural alignment of the element type is enough (a clip may start at an odd int16
+ * sample, rows at an odd 16-bit element).  Supported where melspec_blm_supports_split is, for every valid (pcm, out) pair
+ * (melspec_blm_supports_split_io == 1); (F32, F32) is handed to the f32 split calls as it is.  Checked in this order: NULL context, the
+ * dtype codes (MELSPEC_ERR_INVALID_ARG), then the f32 split call's own checks in its order -- an unsupported context
+ * (MELSPEC_ERR_UNSUPPORTED, the split call's message naming the geometry, no buffer touched), nothing to do (MELSPEC_OK), NULL tables /
+ * pointers --, then a pointer misaligned for its element type (MELSPEC_ERR_INVALID_ARG).  Only the partials scratch of the f32 split
+ * calls is used, in stream order; the rows scratch of the normalised _io call never is.  Stream-ordered and asynchronous like the f32
+ * split calls.  One mel kernel serves the uniform and the ragged call (csrc/fbank512_stats_io_kernels.hpp); none of its twenty
+ * instantiations uses scratch memory (profiles/blm_split_io_resources.txt).
+ * What it costs (ms per call + synchronise, profiles/blm_split_io.txt; A: this call (S16, F16); B: melspec_blm_compute_*_io (S16, F16)
+ * with normalize_per_feature = 1, the call A replaces; C: the f32 split call on f32 samples; D: torch int16 -> f32, C, torch f32 -> f16): 1024 x 10 s uniform / 1024 clips of 2-20 s ragged, 80 and 128 mels; the widest interquartile range of the rounds was 0.10-0.19 ms, so
+ * differences below about 15 % are inside the spread.  MELSPEC_PRECISION_F32: A takes 0.87 x / 0.79 x (uniform, 80 / 128 mels) and
+ * 0.73 x / 0.64 x (ragged) the time of B, 0.87-0.91 x of C and 0.42-0.45 x of D; beyond the spread that is "A below B" for the ragged
+ * shapes and "A below D" everywhere, NOT for A against C or against the uniform B.  Default (f64) mode: on uniform batches A is SLOWER
+ * than B, 1.50 x / 1.27 x -- the f64 stats kernel's per-round merge, as for the f32 split above --, ragged 1.00 x / 0.89 x; 0.94-0.98 x
+ * of C; 0.57-0.62 x of D (below D beyond the spread everywhere).  Set the F32 mode where the call is used for speed; in f64 the call is
+ * kept for its contract -- 16-bit rows with f32 statistics of the f32 values, and no rows scratch. */
+int melspec_blm_supports_split_io(const melspec_blm *b, int pcm_dtype, int out_dtype);
+int melspec_blm_compute_uniform_device_split_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                                uint32_t n_clips, void *d_rows, int out_dtype, float *d_mean, float *d_inv_std, void *stream);
+int melspec_blm_compute_ragged_device_split_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                               const uint64_t *h_lengths, uint32_t n_clips, void *d_rows, int out_dtype,
+                                               const uint64_t *h_rows_offsets, float *d_mean, float *d_inv_std, void *stream);
+/* One clip from host memory: the int16 bytes go up, the 16-bit rows (capacity in elements) and the two f32 vectors come back. */
+int melspec_blm_compute_host_split_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *rows, int out_dtype,
+                                      size_t rows_capacity_elems, float *mean, float *inv_std, size_t *n_rows, size_t *n_cols);
 /* Arithmetic of the fused kernel (n_fft 512 / win_length 400, 80 or 128 mels).  MELSPEC_PRECISION_F32: f32 window, FFT, power and
  * projection -- the reference's own arithmetic type for this frontend (src/mel.rs:251-252,356-357), as far from the f64 evaluation of
  * its definition as upstream's f32 code is (2.4e-4 on jfk_f32le.wav) at ~0.8 x the time.  AUTO (default) / F64: f64 up to |X|^2, within 1e-4

@@ -368,6 +368,34 @@ public:
         return s;
     }
 
+    // additive: the split output with 16-bit ends (melspec_hip.h) -- int16 PCM in, f16 / bf16 rows out (the f32 split call's rows rounded
+    // once), f32 mean and inv_std (the f32 split call's bits); strides, offsets and capacities count elements
+    bool supports_split_io(int pcm_dtype, int out_dtype) const { return melspec_blm_supports_split_io(b_, pcm_dtype, out_dtype) != 0; }
+    void compute_uniform_device_split_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_rows,
+                                         int out_dtype, float *d_mean, float *d_inv_std, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_uniform_device_split_io(b_, d_pcm, pcm_dtype, clip_stride, clip_len, n_clips, d_rows, out_dtype, d_mean, d_inv_std, stream), false);
+    }
+    void compute_ragged_device_split_io(const void *d_pcm, int pcm_dtype, const std::uint64_t *offsets, const std::uint64_t *lengths, std::uint32_t n_clips,
+                                        void *d_rows, int out_dtype, const std::uint64_t *rows_offsets, float *d_mean, float *d_inv_std, void *stream = nullptr) {
+        detail::check(melspec_blm_compute_ragged_device_split_io(b_, d_pcm, pcm_dtype, offsets, lengths, n_clips, d_rows, out_dtype, rows_offsets, d_mean, d_inv_std,
+                                                                 stream), false);
+    }
+    struct SplitS16 {
+        std::vector<std::uint16_t> rows;   // (n_mels, cols) row-major, the bit patterns of out_dtype, un-normalised
+        std::size_t cols = 0;
+        std::vector<float> mean, inv_std;  // (n_mels)
+    };
+    SplitS16 compute_split_s16(const std::vector<std::int16_t> &samples, int out_dtype) {
+        SplitS16 s;
+        s.rows.assign(n_mels_ * melspec_blm_padded_frames(b_, samples.size()), 0);
+        s.mean.assign(n_mels_, 0.0f);
+        s.inv_std.assign(n_mels_, 0.0f);
+        std::size_t rows = 0;
+        detail::check(melspec_blm_compute_host_split_io(b_, samples.data(), MELSPEC_PCM_S16, samples.size(), s.rows.data(), out_dtype, s.rows.size(), s.mean.data(),
+                                                        s.inv_std.data(), &rows, &s.cols), false);
+        return s;
+    }
+
     // additive: 16-bit ends (MELSPEC_PCM_*, MELSPEC_OUT_* of melspec_hip.h); strides, offsets and lengths count elements
     bool supports_io(int pcm_dtype, int out_dtype) const { return melspec_blm_supports_io(b_, pcm_dtype, out_dtype) != 0; }
     void compute_uniform_device_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_out,

@@ -6,10 +6,12 @@
 #include "fbank512_kaldi_io_kernels.hpp"
 #include "fbank512_stats_kernels.hpp"
 #include "fbank512_stats_ragged_kernels.hpp"
+#include "fbank512_stats_io_kernels.hpp"
 #include "fbank512_stream_kernels.hpp"
 #include "fbank512_nemo_stream_kernels.hpp"
 #include "stream_banks_io_kernels.hpp"
 #include "blm_stats_plan.hpp"
+#include "blm_split_io_plan.hpp"
 #include "blm_stream_plan.hpp"
 #include "fbank_stream_plan.hpp"
 #include "stat_bank.hpp"
@@ -1285,6 +1287,168 @@ int melspec_blm_compute_host_split(melspec_blm *b, const float *samples, size_t 
     HIP_TRY(hipMemcpyAsync(rows, d_rows, need * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(mean, d_rows + need, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipMemcpyAsync(inv_std, d_rows + need + nm, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    if (n_cols) *n_cols = static_cast<size_t>(c);
+    return MELSPEC_OK;
+}
+
+// ---- the split output with int16 PCM in / f16, bf16 rows out: see include/melspec_hip.h ----
+// The f32 split calls above with the mel kernel's (sample, row) sibling (fbank512_stats_io_kernels.hpp): the same plans -- they count
+// elements --, the same launch shape and LDS, the same partials scratch and finish kernels; b->rows32 is never touched.  (F32, F32) IS the
+// call above.
+int melspec_blm_supports_split_io(const melspec_blm *b, int pcm_dtype, int out_dtype) {
+    return b && blm_split_io_pcm_known(pcm_dtype) && blm_split_io_out_known(out_dtype) && blm_stats_ok(b) ? 1 : 0;
+}
+
+// the verdict of an argument check as the call's status
+static int blm_split_io_verdict(const melspec_blm *b, const BlmStatsArgs &a) {
+    if (a.verdict != kBlmStatsFail) return MELSPEC_OK;
+    if (a.msg) return fail(a.status, a.msg);
+    g_last_error = blm_stats_unsupported(b);
+    return a.status;
+}
+
+// one launch of the mel kernel of combination io behind the stats kernel of route r
+static int launch_stats_io(const Launch512 &l, int io, const FbankStatsRaggedParams &q, const Lds512Sizes &z, int cus, hipStream_t s) {
+    static std::atomic<uint64_t> attr_done[kBlmSplitIoKernels];          // one bit per device: function attributes are per device
+    const int at = blm_split_io_slot(l.kernel, io);
+    const FbankStatsIoKernel kernel = nemo_stats_io_kernel(l.kernel, io);
+    if (at < 0 || !kernel) return fail(MELSPEC_ERR_INTERNAL, "launch_stats_io: the object has no kernel for this batch");
+    if (int rc = allow_big_lds_once(attr_done[at], "hipFuncSetAttribute(fbank512_nemo_stats_io_kernel)", kernel)) return rc;
+    hipLaunchKernelGGL(kernel, dim3(grid512(l, q.f.b.n_units, cus)), dim3(l.waves * 64), lds512(l.lds, z), s, q);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+int melspec_blm_compute_uniform_device_split_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips,
+                                                void *d_rows, int out_dtype, float *d_mean, float *d_inv_std, void *stream) {
+    int io;
+    const BlmStatsArgs codes = blm_split_io_codes(b != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kBlmStatsFail) return blm_split_io_verdict(b, codes);
+    if (io == 0) return melspec_blm_compute_uniform_device_split(b, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_rows), d_mean, d_inv_std, stream);
+    const uint64_t valid = blm_valid_frames(b, clip_len), cols = blm_padded(b, valid);
+    const BlmStatsArgs a = blm_split_io_args(blm_stats_ok(b), n_clips, cols, d_pcm, d_rows, d_mean, d_inv_std, io);
+    if (a.verdict != kBlmStatsGo) return blm_split_io_verdict(b, a);
+    const int nm = b->cfg.n_mels;
+    const Route512 r = route512(blm_shape(b), Batch512::kStats);
+    BlmStatsPlan sp;
+    if (!blm_stats_plan(cols, n_clips, nm, info_of(r.run.kernel).f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
+    int rc;
+    if ((rc = b->stats.ensure(static_cast<size_t>(sp.part_bytes) + 16, s))) return rc;
+    // the f32 split call's batch; the plan counts elements, the kernel reads the two pointers as its own types
+    BatchPlan pl = plan_uniform(static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), clip_stride, valid, n_clips, nm, kFbFPW, cols, true);
+    pl.desc.units_per_clip = sp.units_per_clip;
+    pl.desc.n_units = sp.n_units;
+    FbankStatsRaggedParams q{};
+    q.f = blm_fast_params(b, pl.desc);
+    q.f.b.sync_rounds = kNemoSync;
+    apply_route(r, q.f, b->f32);
+    q.f.clip_len = static_cast<long long>(clip_len);
+    q.d_part = static_cast<float2 *>(b->stats.p());          // [clip * blocks_per_clip + block][n_mels]: the layout blm_stats_finish_kernel reads
+    if ((rc = launch_stats_io(r.run, io, q, blm_lds(b), b->dev.cus, s))) return rc;
+    BlmStatsFinishParams fq{};
+    fq.part = q.d_part; fq.mean = d_mean; fq.inv_std = d_inv_std; fq.valid = valid;
+    fq.n_clips = n_clips; fq.blocks_per_clip = sp.blocks_per_clip; fq.block_frames = sp.block_frames; fq.n_mels = nm;
+    const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+    hipLaunchKernelGGL(blm_stats_finish_kernel, dim3(grid_for((rows + kBlmStatsFinishThreads - 1) / kBlmStatsFinishThreads, b->dev.cus, 8)), dim3(kBlmStatsFinishThreads), 0, s, fq);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+
+int melspec_blm_compute_ragged_device_split_io(melspec_blm *b, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
+                                               void *d_rows, int out_dtype, const uint64_t *h_rows_offsets, float *d_mean, float *d_inv_std, void *stream) {
+    int io;
+    const BlmStatsArgs codes = blm_split_io_codes(b != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kBlmStatsFail) return blm_split_io_verdict(b, codes);
+    if (io == 0)
+        return melspec_blm_compute_ragged_device_split(b, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_rows), h_rows_offsets, d_mean, d_inv_std, stream);
+    const bool ok = blm_stats_ok(b);
+    std::vector<uint64_t> cols, aux;          // the clips' columns; lengths, valid frames (the kernels' d_len / d_valid)
+    uint64_t most = 0;
+    if (ok && n_clips && h_offsets && h_lengths) {
+        cols.resize(n_clips);
+        aux.resize(2 * static_cast<size_t>(n_clips));
+        for (uint32_t i = 0; i < n_clips; ++i) {
+            const uint64_t valid = blm_valid_frames(b, h_lengths[i]);
+            cols[i] = blm_padded(b, valid);
+            aux[i] = h_lengths[i];
+            aux[n_clips + i] = valid;
+            most = std::max(most, cols[i]);
+        }
+    }
+    const BlmStatsArgs a = blm_split_io_ragged_args(ok, n_clips, h_offsets, h_lengths, most, d_pcm, d_rows, d_mean, d_inv_std, io);
+    if (a.verdict != kBlmStatsGo) return blm_split_io_verdict(b, a);
+    const int nm = b->cfg.n_mels;
+    const Route512 r = route512(blm_shape(b), Batch512::kStats);
+    BlmStatsRaggedPlan sp;
+    if (!blm_stats_plan_ragged(cols.data(), n_clips, nm, info_of(r.run.kernel).f32, sp)) return fail(MELSPEC_ERR_UNSUPPORTED, "the batch is too large for the split output's plan");
+    HIP_TRY(hipSetDevice(b->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : b->stream;
+    int rc;
+    if ((rc = b->stats.ensure(static_cast<size_t>(sp.part_bytes) + 16, s))) return rc;
+    if ((rc = b->aux.ensure(aux.size() * sizeof(uint64_t), s))) return rc;
+    const uint64_t *d_aux = static_cast<const uint64_t *>(b->aux.p());
+    HIP_TRY(hipMemcpyAsync(b->aux.p(), aux.data(), aux.size() * sizeof(uint64_t), hipMemcpyHostToDevice, s));    // pageable source: staged before the call returns
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    rc = plan_ragged(b->ragged, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), h_offsets, cols, h_rows_offsets, n_clips, nm, kFbFPW, pl, slot, false, sp.waves);
+    if (!rc && pl.desc.n_units != sp.n_units) rc = fail(MELSPEC_ERR_INTERNAL, "the split output's ragged plan and its batch plan disagree");
+    if (!rc) {
+        FbankStatsRaggedParams q{};
+        q.f = blm_fast_params(b, pl.desc);
+        q.f.b.mel_major = 1;
+        q.f.b.sync_rounds = kNemoSync;
+        apply_route(r, q.f, b->f32);
+        q.f.d_len = d_aux;
+        q.f.d_valid = d_aux + n_clips;
+        q.d_part = static_cast<float2 *>(b->stats.p());
+        rc = launch_stats_io(r.run, io, q, blm_lds(b), b->dev.cus, s);
+        if (!rc) {
+            BlmStatsFinishRaggedParams fq{};
+            fq.part = q.d_part; fq.mean = d_mean; fq.inv_std = d_inv_std; fq.d_valid = q.f.d_valid; fq.d_unit_prefix = pl.desc.d_unit_prefix;
+            fq.n_clips = n_clips; fq.waves = sp.waves; fq.block_frames = sp.block_frames; fq.n_mels = nm;
+            const uint64_t rows = static_cast<uint64_t>(n_clips) * nm;
+            hipLaunchKernelGGL(blm_stats_finish_ragged_kernel, dim3(grid_for((rows + kBlmStatsFinishThreads - 1) / kBlmStatsFinishThreads, b->dev.cus, 8)), dim3(kBlmStatsFinishThreads), 0, s, fq);
+            if (hipGetLastError() != hipSuccess) rc = fail(MELSPEC_ERR_INTERNAL, "blm_stats_finish_ragged_kernel launch failed");
+        }
+    }
+    plan_ragged_done(slot, s);
+    return rc;
+}
+
+// One clip from host memory: the int16 bytes go up, the 16-bit rows and the two f32 vectors come back (the statistics behind the rows in
+// the context's device-to-host buffer, at the next multiple of four bytes).
+int melspec_blm_compute_host_split_io(melspec_blm *b, const void *samples, int pcm_dtype, size_t n_samples, void *rows, int out_dtype, size_t rows_capacity_elems,
+                                      float *mean, float *inv_std, size_t *n_rows, size_t *n_cols) {
+    int io;
+    const BlmStatsArgs codes = blm_split_io_codes(b != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kBlmStatsFail) return blm_split_io_verdict(b, codes);
+    if (io == 0) return melspec_blm_compute_host_split(b, static_cast<const float *>(samples), n_samples, static_cast<float *>(rows), rows_capacity_elems, mean, inv_std, n_rows, n_cols);
+    if (n_rows) *n_rows = static_cast<size_t>(b->cfg.n_mels);
+    if (n_cols) *n_cols = 0;
+    const uint64_t c = blm_padded(b, blm_valid_frames(b, n_samples));
+    const uint64_t nm = static_cast<uint64_t>(b->cfg.n_mels), need = c * nm;
+    const size_t in_bytes = blm_split_io_pcm_bytes(pcm_dtype), out_bytes = blm_split_io_out_bytes(out_dtype);
+    const size_t stats_at = (static_cast<size_t>(need) * out_bytes + 3) & ~static_cast<size_t>(3);
+    if (blm_stats_ok(b) && c != 0) {        // (an unsupported context: the device call words the error)
+        if (!samples || !rows) return fail(MELSPEC_ERR_INVALID_ARG, "samples/rows is NULL");
+        if (!mean || !inv_std) return fail(MELSPEC_ERR_INVALID_ARG, "mean / inv_std is NULL");
+        if (rows_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+        HIP_TRY(hipSetDevice(b->dev.device));
+        int rc;
+        if ((rc = b->h2d.ensure(n_samples * in_bytes))) return rc;
+        if ((rc = b->d2h.ensure(stats_at + 2 * nm * sizeof(float)))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->h2d.p, samples, n_samples * in_bytes, hipMemcpyHostToDevice, b->stream));
+    }
+    char *d_rows = static_cast<char *>(b->d2h.p);
+    float *d_stats = d_rows ? reinterpret_cast<float *>(d_rows + stats_at) : nullptr;
+    const int rc = melspec_blm_compute_uniform_device_split_io(b, b->h2d.p, pcm_dtype, n_samples, n_samples, 1, d_rows, out_dtype, d_stats, d_stats ? d_stats + nm : nullptr, b->stream);
+    if (rc || c == 0) return rc;
+    HIP_TRY(hipMemcpyAsync(rows, d_rows, need * out_bytes, hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(mean, d_stats, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipMemcpyAsync(inv_std, d_stats + nm, nm * sizeof(float), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     if (n_cols) *n_cols = static_cast<size_t>(c);
     return MELSPEC_OK;

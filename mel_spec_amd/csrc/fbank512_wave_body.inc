@@ -12,6 +12,14 @@
 // MS_FB512_CLIP_ORG0 (fbank512_nemo_stream_kernel, fbank512_nemo_stream_kernels.hpp: NeMo flavour, parameter q around p): the window origin
 // of a clip's first frame is the clip's own, q.d_org0[clip], instead of the batch's p.org0; without the macro the text below is what it
 // always was.
+// MS_FB512_FRESH_FL (fbank512_nemo_stats_io_kernel, fbank512_stats_io_kernels.hpp): phase 2b's three row addresses in the wave's slice
+// (fb_phase2_split: p, p + r, p - r) are derived from the lane's frame once per unit instead of being held across the unit loop -- the
+// twelve-wave 128-mel kernel with int16 samples in is one VGPR short; without the macro the text below is what it always was.
+#ifdef MS_FB512_FRESH_FL
+#define MS_FB512_PHASE2_FL fresh_lane_value(fl)
+#else
+#define MS_FB512_PHASE2_FL fl
+#endif
     using L = FbankLayout<T>;
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
     const int tid = threadIdx.x;
@@ -132,7 +140,7 @@
             for (int i = 0; i < 8; ++i) part[i] = {partner16(own[8 + i].re), partner16(own[8 + i].im)};
             if (FLAVOR == kFlavorWhisper) fb_phase2_split<T, true, sizeof(T) == 8>(fl, j, act, tblob, own, part, slice);      // f32: the amplitude form (fbank_tables.hpp)
             // NeMo: power spectra always (src/mel.rs:356-357) -- the magnitude form stays out of its unit loop (742 -> ~400 instructions in phase 2)
-            else if (FLAVOR == kFlavorNemo || use_power) fb_phase2_split<T, true>(fl, j, act, tblob, own, part, slice);
+            else if (FLAVOR == kFlavorNemo || use_power) fb_phase2_split<T, true>(MS_FB512_PHASE2_FL, j, act, tblob, own, part, slice);
             else fb_phase2_split<T, false>(fl, j, act, tblob, own, part, slice);
         }
         __builtin_amdgcn_wave_barrier();
@@ -266,3 +274,4 @@
         sreduce(staged.round - 1, tid);
 #endif
     }
+#undef MS_FB512_PHASE2_FL

@@ -765,6 +765,74 @@ def blm_compute_ragged_split(fe: BatchLogMelSpectrogram, clips) -> list:
     return [(r, stat[0, i].copy(), stat[1, i].copy()) if r.shape[1] else (r, None, None) for i, r in enumerate(rows)]
 
 
+# -- the split output with 16-bit ends (melspec_blm_*_split_io): int16 PCM in, f16 / bf16 rows out, f32 mean and 1 / std; module-level for
+# the same reason.  Rows are the f32 split call's rows rounded to nearest even once, the statistics are its bits; strides, offsets and
+# capacities count elements. ---------------------------------------------------------------------------------------------------------------
+def blm_supports_split_io(fe: BatchLogMelSpectrogram, pcm_dtype: int, out_dtype: int) -> bool:
+    return bool(lib().melspec_blm_supports_split_io(fe._h, pcm_dtype, out_dtype))
+
+
+def blm_compute_uniform_device_split_io(fe: BatchLogMelSpectrogram, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int,
+                                        out_dtype: int, d_mean: int, d_inv_std: int, stream: int = 0) -> None:
+    """compute_uniform_device_split with `pcm_dtype` samples in and `out_dtype` rows out: d_rows = [clip][n_mels][cols] of the row type,
+    d_mean / d_inv_std = [clip][n_mels] f32.  Asynchronous on `stream`."""
+    _check(lib().melspec_blm_compute_uniform_device_split_io(fe._h, C.c_void_p(d_pcm), pcm_dtype, clip_stride, clip_len, n_clips, C.c_void_p(d_rows), out_dtype,
+                                                             C.c_void_p(d_mean), C.c_void_p(d_inv_std), C.c_void_p(stream)))
+
+
+def blm_compute_ragged_device_split_io(fe: BatchLogMelSpectrogram, d_pcm: int, pcm_dtype: int, offsets, lengths, d_rows: int, out_dtype: int, d_mean: int,
+                                       d_inv_std: int, rows_offsets=None, stream: int = 0) -> None:
+    """blm_compute_ragged_device_split with `pcm_dtype` samples in and `out_dtype` rows out; offsets and rows_offsets count elements of their
+    types.  Asynchronous on `stream`."""
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_blm_compute_ragged_device_split_io(fe._h, C.c_void_p(d_pcm), pcm_dtype, p_off, p_len, tabs[0].shape[0], C.c_void_p(d_rows), out_dtype, p_out,
+                                                            C.c_void_p(d_mean), C.c_void_p(d_inv_std), C.c_void_p(stream)))
+
+
+def blm_compute_split_io(fe: BatchLogMelSpectrogram, samples, out_dtype=None):
+    """One host clip -> (rows (n_mels, cols), mean (n_mels,), inv_std (n_mels,)): melspec_blm_compute_host_split_io.  An np.int16 array
+    is taken as 16-bit PCM (value = sample / 32768, exactly); out_dtype "f16" returns np.float16 rows, "bf16" the bfloat16 bit patterns
+    as np.uint16; mean and inv_std are np.float32."""
+    x, pcm = _pcm_clip(samples)
+    out = _out_code(out_dtype)
+    cols = fe.padded_frames(x.shape[0])
+    nm = fe.config.n_mels
+    rows, mean, inv_std = np.zeros((nm, cols), _OUT_NUMPY[out]), np.zeros(nm, np.float32), np.zeros(nm, np.float32)
+    r, c = C.c_size_t(0), C.c_size_t(0)
+    _check(lib().melspec_blm_compute_host_split_io(fe._h, x.ctypes.data_as(C.c_void_p), pcm, x.shape[0], rows.ctypes.data_as(C.c_void_p), out, rows.size,
+                                                   _fp(mean), _fp(inv_std), C.byref(r), C.byref(c)))
+    assert r.value == nm and c.value == cols
+    return rows, mean, inv_std
+
+
+def blm_compute_ragged_split_io(fe: BatchLogMelSpectrogram, clips, out_dtype=None) -> list:
+    """list of 1-D host arrays of any lengths (all np.int16 = 16-bit PCM, otherwise f32) -> list of (rows (n_mels, cols) of out_dtype,
+    mean (n_mels,), inv_std (n_mels,)), one launch; a clip without a valid frame gives (zeros((n_mels, 0)), None, None)"""
+    arrs = [np.asarray(c).reshape(-1) for c in clips]
+    pcm = PCM_S16 if arrs and all(a.dtype == np.int16 for a in arrs) else PCM_F32
+    in_t = np.int16 if pcm == PCM_S16 else np.float32
+    arrs = [np.ascontiguousarray(a, dtype=in_t) for a in arrs]
+    out = _out_code(out_dtype)
+    out_t = np.dtype(_OUT_NUMPY[out])
+    lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
+    flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, in_t)
+    shapes, total = fe._packed(lens)
+    nm, n = fe.config.n_mels, len(shapes)
+    if n == 0:
+        return []
+    din, drows, dstat = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * out_t.itemsize, 16)), DeviceBuffer(2 * n * nm * 4)
+    try:
+        din.upload(flat)
+        blm_compute_ragged_device_split_io(fe, din.ptr, pcm, offs, lens, drows.ptr, out, dstat.ptr, dstat.ptr + n * nm * 4)
+        fe.synchronize()
+        rows = _split(drows.download((max(total, 1),), out_t)[:total], shapes)
+        stat = dstat.download((2, n, nm))
+    finally:
+        din.free(); drows.free(); dstat.free()
+    return [(r, stat[0, i].copy(), stat[1, i].copy()) if r.shape[1] else (r, None, None) for i, r in enumerate(rows)]
+
+
 # -- the ragged call with its clip table in device memory (melspec_blm_compute_ragged_device_desc): module-level for the same reason -----------
 def blm_compute_ragged_device_desc(fe: BatchLogMelSpectrogram, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
                                    max_total_columns: int, max_clip_samples: int, d_rejected: int = 0, stream: int = 0) -> None:

@@ -98,6 +98,15 @@ unsafe extern "C" {
                                                stream: *mut c_void) -> c_int;
     fn melspec_blm_compute_host_split(b: *mut BlmHandle, samples: *const f32, n_samples: usize, rows: *mut f32, rows_capacity_floats: usize,
                                       mean: *mut f32, inv_std: *mut f32, n_rows: *mut usize, n_cols: *mut usize) -> c_int;
+    fn melspec_blm_supports_split_io(b: *const BlmHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_blm_compute_uniform_device_split_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64,
+                                                   n_clips: u32, d_rows: *mut c_void, out_dtype: c_int, d_mean: *mut f32, d_inv_std: *mut f32,
+                                                   stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_ragged_device_split_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, h_offsets: *const u64,
+                                                  h_lengths: *const u64, n_clips: u32, d_rows: *mut c_void, out_dtype: c_int,
+                                                  h_rows_offsets: *const u64, d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_blm_compute_host_split_io(b: *mut BlmHandle, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, rows: *mut c_void, out_dtype: c_int,
+                                         rows_capacity_elems: usize, mean: *mut f32, inv_std: *mut f32, n_rows: *mut usize, n_cols: *mut usize) -> c_int;
     fn melspec_blm_supports_io(b: *const BlmHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
     fn melspec_blm_compute_uniform_device_io(b: *mut BlmHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
                                              d_out: *mut c_void, out_dtype: c_int, stream: *mut c_void) -> c_int;
@@ -871,6 +880,47 @@ impl HipBatchLogMel {
                                            &mut rows, &mut got_cols)
         })?;
         Ok((ndarray::Array2::from_shape_vec((self.n_mels, got_cols), flat).expect("shape"), mean, inv_std))
+    }
+    /// Additive: the split output with 16-bit ends -- does this frontend compute it for `pcm_dtype` samples and `out_dtype` rows?
+    pub fn supports_split_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_blm_supports_split_io(self.b, pcm_dtype, out_dtype) != 0 }
+    }
+    /// Additive: `compute_uniform_device_split` with `pcm_dtype` samples in and `out_dtype` rows out (the f32 call's rows rounded once);
+    /// mean and inv_std stay f32 and are the f32 call's bits.  Strides count elements.
+    ///
+    /// # Safety
+    /// the device pointers must be valid for the batch on this frontend's device.
+    pub unsafe fn compute_uniform_device_split_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                                  d_rows: *mut c_void, out_dtype: i32, d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void)
+                                                  -> Result<(), HipError> {
+        check(melspec_blm_compute_uniform_device_split_io(self.b, d_pcm, pcm_dtype, clip_stride, clip_len, n_clips, d_rows, out_dtype, d_mean, d_inv_std, stream))
+    }
+    /// Additive: the ragged form of the same.
+    ///
+    /// # Safety
+    /// the device pointers must be valid for the batch on this frontend's device.
+    pub unsafe fn compute_ragged_device_split_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, offsets: &[u64], lengths: &[u64], d_rows: *mut c_void,
+                                                 out_dtype: i32, rows_offsets: Option<&[u64]>, d_mean: *mut f32, d_inv_std: *mut f32, stream: *mut c_void)
+                                                 -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        if let Some(o) = rows_offsets {
+            assert_eq!(o.len(), offsets.len());
+        }
+        check(melspec_blm_compute_ragged_device_split_io(self.b, d_pcm, pcm_dtype, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_rows, out_dtype,
+                                                         rows_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), d_mean, d_inv_std, stream))
+    }
+    /// Additive: `compute_split` on 16-bit PCM into `out_dtype` rows (`OUT_F16` / `OUT_BF16`), returned as their bit patterns
+    /// (n_mels, cols) row-major, with the f32 mean and inv_std.
+    pub fn compute_split_s16(&mut self, samples: &[i16], out_dtype: i32) -> Result<(Vec<u16>, usize, Vec<f32>, Vec<f32>), HipError> {
+        let cols = unsafe { melspec_blm_padded_frames(self.b, samples.len()) };
+        let mut flat = vec![0u16; self.n_mels * cols];
+        let (mut mean, mut inv_std) = (vec![0.0f32; self.n_mels], vec![0.0f32; self.n_mels]);
+        let (mut rows, mut got_cols) = (0usize, 0usize);
+        check(unsafe {
+            melspec_blm_compute_host_split_io(self.b, samples.as_ptr() as *const c_void, PCM_S16, samples.len(), flat.as_mut_ptr() as *mut c_void, out_dtype,
+                                              flat.len(), mean.as_mut_ptr(), inv_std.as_mut_ptr(), &mut rows, &mut got_cols)
+        })?;
+        Ok((flat, got_cols, mean, inv_std))
     }
     /// Additive: does this frontend take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` features (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?
     pub fn supports_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
