@@ -1004,8 +1004,10 @@ def test_nemo_frontend_batch(gpu, oracle):
 
 @pytest.mark.parametrize("seconds,frames", [(3, 301), (30, 3001), (50, 5001)])
 def test_nemo_per_feature_normalisation_row_lengths(gpu, oracle, seconds, frames):
-    """normalize_per_feature (src/mel.rs:721-749) through the three builds of the row kernel: rows held in
-    16 or 48 registers per lane, and the three-pass fallback for longer clips."""
+    """normalize_per_feature (src/mel.rs:721-749) through the three shapes blm_norm_shape_uniform (fbank512.hip) gives the normaliser,
+    which stages whole rows in LDS: 301 frames -- rows of 324 floats, 28 to a workgroup of 38 KB, four workgroups per CU; 3 001 and
+    5 001 frames -- fewer than four rows fit in 38 KB, so one workgroup per CU with 150 KB, 12 rows of 3 012 floats and 7 rows of
+    5 028 (fewer rows per workgroup: more threads share a row's sum of squares, another order of that sum)."""
     kw = dict(n_mels=80, preemphasis=0.97, normalize_per_feature=True)
     fe = gpu.BatchLogMelSpectrogram(gpu.BatchLogMelConfig(**kw))
     x = oracle.synth_pcm(3, seconds * 16000)
