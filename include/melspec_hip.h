@@ -430,6 +430,60 @@ int melspec_fbank_compute_ragged_device_io(melspec_fbank *fb, const void *d_pcm,
 int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples,
                                   void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames);
 
+/* ---- the Kaldi split output for ragged batches and with 16-bit ends: int16 PCM in, f16 / bf16 rows out, f32 means -------------------
+ * melspec_fbank_compute_uniform_device_split (above) carried to what an ASR server in front of a Kaldi-style encoder has -- int16 PCM of
+ * mixed lengths -- and wants -- half-precision features: 2 bytes read per sample, 2 bytes written per element, 4 * num_mel_bins bytes of
+ * means per clip, no scratch rows and no second pass (the _io calls with CMN write f32 rows into a scratch and read them back).
+ *   samples   MELSPEC_PCM_S16: int16 * 2^-15, exactly; the call behaves as on the batch converted by `v as f32 / 32768.0`.
+ *   d_rows    clip c: [frames_c][num_mel_bins] at d_rows + h_rows_offsets[c] ELEMENTS (NULL: packed in clip order).  Every element is the
+ *             f32 element an object with the same config and apply_cmn = 0 writes through melspec_fbank_compute_uniform_device /
+ *             _ragged_device, rounded to nearest even ONCE (a NaN stays a NaN); for (., F32) rows those are its bits.
+ *   d_means   [n_clips][num_mel_bins] f32, always packed: THE BITS melspec_fbank_compute_uniform_device_split gives for that clip alone
+ *             -- the means of the f32 values by the fixed summation tree of the fused path, not of the rounded rows --, a function of
+ *             the clip's samples and length only: not of its place in the batch, the other clips, the output offsets, the dtype
+ *             combination or what ran before.  A clip without a frame has no rows and its mean slots are +0.0, as the uniform Kaldi split
+ *             reports them (the NeMo split leaves such slots untouched; this one does not).
+ * melspec_fbank_compute_ragged_device_split is the f32 form (f32 samples, f32 rows) and runs on every object with apply_cmn, by the
+ * routing of melspec_fbank_compute_ragged_device: large batches on the workgroup-per-clip kernel, everything else on the wave kernel (or
+ * the generic one) followed by the CMN pass, which then writes the means and leaves the rows -- both sum by the same tree.  For it,
+ * d_rows[c][f][m] - d_means[c][m] in f32 is, bit for bit, what melspec_fbank_compute_ragged_device stores.
+ * The _split_io calls take every valid (pcm, out) pair; (F32, F32) is handed to the f32 split calls as it is.  The other five run where
+ * melspec_fbank_supports_split_io == 1: the condition of melspec_fbank_supports_io (the fused path with the compile-time 80-bin Kaldi
+ * bank, not after melspec_fbank_use_generic) with use_power and apply_cmn on.  Checked in this order: NULL object; the dtype codes
+ * (MELSPEC_ERR_INVALID_ARG); apply_cmn off (MELSPEC_ERR_INVALID_ARG, as the uniform split); an unsupported object
+ * (MELSPEC_ERR_UNSUPPORTED, melspec_last_error names the geometry, no buffer touched); n_clips == 0 (OK); NULL tables; no frame in the
+ * whole batch (OK; the mean slots are zeroed when d_means is given); NULL device pointers, NULL d_means; a pointer misaligned for its
+ * element type (MELSPEC_ERR_INVALID_ARG).  Strides, offsets and capacities count ELEMENTS; natural alignment of the element type is
+ * enough (a clip may start at an odd int16 sample, a clip's rows at an odd 16-bit element).  A clip of 2^31 frames or more returns
+ * MELSPEC_ERR_UNSUPPORTED.  Stream-ordered and asynchronous; the tables are read before the call returns; the rows scratch of the _io
+ * calls is never touched.
+ * The 16-bit calls always run one kernel, fbank512_clip_split_io_kernel (csrc/fbank512_kaldi_split_io_kernels.hpp: the workgroup-per-clip
+ * kernel with typed loads and stores, always in split mode; ten instantiations, none with scratch memory,
+ * profiles/fbank_split_io_resources.txt), with one workgroup per clip at a time: a batch of fewer clips than the device has CUs is
+ * correct but leaves CUs idle.
+ * What it costs (MI355X, 1024 clips, 80 bins, ms per call + synchronise, median of 30 rounds, tools/fbank_split_io_bench.py,
+ * profiles/fbank_split_io.txt; A: this call (S16, F16); B: melspec_fbank_compute_*_device_io (S16, F16) with CMN, the call A replaces;
+ * C: the f32 split on f32 samples; D: torch int16 -> f32, C, torch f32 -> f16):
+ *     config 3 (1024 x 10 s)     A 0.594   B 0.788   C 0.615   D 1.224     A / B 0.75   A / C 0.97   A / D 0.49
+ *     ragged, 2-20 s per clip    A 0.682   B 0.996   C 0.700   D 1.389     A / B 0.68   A / C 0.97   A / D 0.49
+ * The widest interquartile range of the rounds was 0.07 / 0.09 ms: A is below B and D beyond the spread, and NOT below C beyond it -- the
+ * kernel is bound by its f64 instructions like fbank512_clip_kernel, and halving its bytes buys 3 %.  The gain is over the two-kernel
+ * _io call and over the casts around the f32 split.
+ * Not offered: a path over many CUs for a few long clips with 16-bit ends (use the f32 ragged split, which has one), and a device-table
+ * (_desc) form of any Kaldi split. */
+int melspec_fbank_supports_split_io(const melspec_fbank *fb, int pcm_dtype, int out_dtype);
+int melspec_fbank_compute_ragged_device_split(melspec_fbank *fb, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                              uint32_t n_clips, float *d_rows, const uint64_t *h_rows_offsets, float *d_means, void *stream);
+int melspec_fbank_compute_uniform_device_split_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                                  uint32_t n_clips, void *d_rows, int out_dtype, float *d_means, void *stream);
+int melspec_fbank_compute_ragged_device_split_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                                 const uint64_t *h_lengths, uint32_t n_clips, void *d_rows, int out_dtype,
+                                                 const uint64_t *h_rows_offsets, float *d_means, void *stream);
+/* One clip from host memory: the int16 bytes go up, the 16-bit rows (capacity in elements; too small: MELSPEC_ERR_CAPACITY) and the
+ * num_mel_bins means come back; *n_frames = the clip's frames. */
+int melspec_fbank_compute_host_split_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples, void *rows, int out_dtype,
+                                        size_t rows_capacity_elems, float *means, size_t *n_frames);
+
 /* ---- NeMo/Parakeet log-mel frontend: replaces BatchLogMelSpectrogram (src/mel.rs:171-418) ------- */
 
 /* BatchLogMelConfig (src/mel.rs:171-208). */
@@ -504,7 +558,7 @@ int melspec_blm_compute_ragged_device(melspec_blm *b, const float *d_pcm, const 
  * itself, which this figure counts only as time.
  * Not offered: a _desc form of the split output (its rounds wait for every wave of the workgroup -- "a round with a wave missing would
  * never end", blm_stats_plan.hpp -- so a unit count that only the device knows needs a design of its own); _desc with int16 PCM in or
- * 16-bit rows out; a ragged Kaldi split. */
+ * 16-bit rows out. */
 int melspec_blm_supports_desc(const melspec_blm *b);     /* 1: the fused geometry (n_fft 512 / win_length 400), as the ragged call */
 int melspec_blm_compute_ragged_device_desc(melspec_blm *b, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths,
                                            uint32_t n_clips, float *d_out, const uint64_t *d_out_offsets, uint64_t max_total_columns,
@@ -585,8 +639,8 @@ int melspec_blm_compute_uniform_device_split(melspec_blm *b, const float *d_pcm,
  * MELSPEC_PRECISION_F32 A takes 0.74 x (80 mels) / 0.65 x (128 mels) the time of C and 1.16 x / 1.19 x of B; in the default (f64) mode
  * 0.96 x / 0.86 x of C and 1.37 x / 1.41 x of B.  A beats C in both modes there -- at 80 mels in f64 by 4 % only, a margin inside the
  * spread of the timed calls -- because the ragged normaliser is dearer than the uniform one, not because the f64 kernel got faster.
- * Not offered: a device-table (_desc) form of the split (the frontend's plain ragged call has one: melspec_blm_compute_ragged_device_desc),
- * a ragged form of the Kaldi split (melspec_fbank_compute_uniform_device_split); the f64 kernel's known slowness (its per-round merge) is as it was. */
+ * Not offered: a device-table (_desc) form of the split (the frontend's plain ragged call has one: melspec_blm_compute_ragged_device_desc);
+ * the f64 kernel's known slowness (its per-round merge) is as it was. */
 int melspec_blm_compute_ragged_device_split(melspec_blm *b, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
                                             uint32_t n_clips, float *d_rows, const uint64_t *h_rows_offsets, float *d_mean,
                                             float *d_inv_std, void *stream);

@@ -227,6 +227,37 @@ public:
         if (frames) *frames = got;
         return out;
     }
+    // additive: the split output for ragged batches and with 16-bit ends (melspec_hip.h) -- the rows before CMN (16-bit rows: rounded
+    // once) and the clips' f32 column means (the uniform f32 split's bits); strides, offsets and capacities count elements
+    bool supports_split_io(int pcm_dtype, int out_dtype) const { return melspec_fbank_supports_split_io(fb_, pcm_dtype, out_dtype) != 0; }
+    void compute_ragged_device_split(const float *d_pcm, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths, float *d_rows,
+                                     float *d_means, const std::uint64_t *rows_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_fbank_compute_ragged_device_split(fb_, d_pcm, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), d_rows,
+                                                                rows_offsets, d_means, stream), false);
+    }
+    void compute_uniform_device_split_io(const void *d_pcm, int pcm_dtype, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, void *d_rows,
+                                         int out_dtype, float *d_means, void *stream = nullptr) {
+        detail::check(melspec_fbank_compute_uniform_device_split_io(fb_, d_pcm, pcm_dtype, clip_stride, clip_len, n_clips, d_rows, out_dtype, d_means, stream), false);
+    }
+    void compute_ragged_device_split_io(const void *d_pcm, int pcm_dtype, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths,
+                                        void *d_rows, int out_dtype, float *d_means, const std::uint64_t *rows_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_fbank_compute_ragged_device_split_io(fb_, d_pcm, pcm_dtype, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()),
+                                                                   d_rows, out_dtype, rows_offsets, d_means, stream), false);
+    }
+    struct SplitS16 {
+        std::vector<std::uint16_t> rows;   // (frames, num_mel_bins) row-major, the bit patterns of out_dtype, before CMN
+        std::size_t frames = 0;
+        std::vector<float> means;          // (num_mel_bins)
+    };
+    SplitS16 compute_split_s16(const std::vector<std::int16_t> &samples, int out_dtype) {
+        SplitS16 s;
+        const std::size_t nm = static_cast<std::size_t>(melspec_fbank_num_mel_bins(fb_));
+        s.rows.assign(melspec_fbank_num_frames(fb_, samples.size()) * nm, 0);
+        s.means.assign(nm, 0.0f);
+        detail::check(melspec_fbank_compute_host_split_io(fb_, samples.data(), MELSPEC_PCM_S16, samples.size(), s.rows.data(), out_dtype, s.rows.size(), s.means.data(),
+                                                          &s.frames), false);
+        return s;
+    }
     // what the device calls above need from a class that does not hand out its handle: wait for a call that ran on the object's own
     // stream (stream == nullptr), and give back the scratch a 16-bit CMN call grows
     void synchronize(void *stream = nullptr) { detail::check(melspec_fbank_synchronize(fb_, stream), false); }

@@ -90,6 +90,11 @@ SIGNATURES = {
     "melspec_fbank_compute_uniform_device_io": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp]),
     "melspec_fbank_compute_ragged_device_io": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, _vp, C.c_int, _u64p, _vp]),
     "melspec_fbank_compute_host_io": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp, C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "melspec_fbank_supports_split_io": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "melspec_fbank_compute_ragged_device_split": (C.c_int, [_vp, _vp, _u64p, _u64p, C.c_uint32, _vp, _u64p, _vp, _vp]),
+    "melspec_fbank_compute_uniform_device_split_io": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp, _vp]),
+    "melspec_fbank_compute_ragged_device_split_io": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, _vp, C.c_int, _u64p, _vp, _vp]),
+    "melspec_fbank_compute_host_split_io": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp, C.c_int, C.c_size_t, _f32p, C.POINTER(C.c_size_t)]),
     "melspec_blm_supports_io": (C.c_int, [_vp, C.c_int, C.c_int]),
     "melspec_blm_compute_uniform_device_io": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_int, _vp]),
     "melspec_blm_compute_ragged_device_io": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, _vp, C.c_int, _u64p, _vp]),

@@ -18,6 +18,7 @@ LAB_LIB_PATH = os.path.join(PKG_DIR, "libmelspec_hip_lab.so")   # -DMELSPEC_LAB:
 # their own so that the kernels above keep the instructions they have; the f32 ones get melspec_runs.hip's strategy
 # fbank512_io.hip: the NeMo / Parakeet frontend's kernels with the same 16-bit ends (csrc/fbank512_io_kernels.hpp), out of fbank512.hip for the same reason
 # fbank512_kaldi_io.hip: the Kaldi fbank's (csrc/fbank512_kaldi_io_kernels.hpp), likewise
+# fbank512_kaldi_split_io.hip: the Kaldi fbank's split output with the same 16-bit ends (csrc/fbank512_kaldi_split_io_kernels.hpp: the workgroup-per-clip kernel, rows + means in one pass), likewise
 # fbank512_stats.hip: the NeMo frontend's split output (csrc/fbank512_stats_kernels.hpp: rows + the partials of the row statistics), likewise
 # fbank512_stats_ragged.hip: the split output's ragged form (csrc/fbank512_stats_ragged_kernels.hpp: the same kernels over a ragged batch whose clips have whole rounds), likewise
 # fbank512_stream.hip: the Kaldi fbank's stream bank (csrc/fbank512_stream_kernels.hpp: the plain kernels with a "continues" flag per clip, the column sums), likewise
@@ -25,7 +26,7 @@ LAB_LIB_PATH = os.path.join(PKG_DIR, "libmelspec_hip_lab.so")   # -DMELSPEC_LAB:
 # fbank512_stats_io.hip: the split output with int16 PCM in / f16, bf16 rows out (csrc/fbank512_stats_io_kernels.hpp: one kernel for uniform and ragged batches), likewise
 # stream_banks_io.hip: the two stream banks' fold kernels with a 16-bit row store (csrc/stream_banks_io_kernels.hpp), likewise
 SOURCES = ["host_api.hip", "whisper400.hip", "fbank512.hip", "pow2.hip", "aux.hip", "melspec_runs.hip", "melspec_io_runs.hip", "melspec_io64.hip",
-           "fbank512_io.hip", "fbank512_kaldi_io.hip", "fbank512_stats.hip", "fbank512_stats_ragged.hip", "fbank512_stats_io.hip", "fbank512_stream.hip", "fbank512_nemo_stream.hip", "stream_banks_io.hip"]
+           "fbank512_io.hip", "fbank512_kaldi_io.hip", "fbank512_kaldi_split_io.hip", "fbank512_stats.hip", "fbank512_stats_ragged.hip", "fbank512_stats_io.hip", "fbank512_stream.hip", "fbank512_nemo_stream.hip", "stream_banks_io.hip"]
 UNIT_FLAGS = {"melspec_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "melspec_io_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 
 

@@ -4,6 +4,7 @@
 #include "host_common.hpp"
 #include "fbank512_io_kernels.hpp"
 #include "fbank512_kaldi_io_kernels.hpp"
+#include "fbank512_kaldi_split_io_kernels.hpp"
 #include "fbank512_stats_kernels.hpp"
 #include "fbank512_stats_ragged_kernels.hpp"
 #include "fbank512_stats_io_kernels.hpp"
@@ -12,6 +13,7 @@
 #include "stream_banks_io_kernels.hpp"
 #include "blm_stats_plan.hpp"
 #include "blm_split_io_plan.hpp"
+#include "fbank_split_io_plan.hpp"
 #include "blm_stream_plan.hpp"
 #include "fbank_stream_plan.hpp"
 #include "stat_bank.hpp"
@@ -476,9 +478,11 @@ int melspec_fbank_compute_uniform_device_split(melspec_fbank *fb, const float *d
 
 // Fbank::compute per clip of any length (src/fbank.rs:141): clip c = vd_pcm[h_offsets[c] .. + h_lengths[c]) -> its frames at
 // vd_out + h_out_offsets[c] elements (NULL: packed); CMN per clip.  io: as in fbank_uniform; an _io batch runs on the two-kernel path
-// (the wave-owned kernel, then the CMN per clip), whatever its shape.
+// (the wave-owned kernel, then the CMN per clip), whatever its shape.  d_means (io = 0): the split output, as in fbank_launch -- the rows
+// stay un-normalised and the clips' column means go to d_means[clip][num_mel_bins]; a clip without a frame gets +0.0 there (neither the
+// plan's order nor cmn_kernel visits it).
 static int fbank_ragged(melspec_fbank *fb, const void *vd_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips, void *vd_out,
-                        const uint64_t *h_out_offsets, void *stream, int io) {
+                        const uint64_t *h_out_offsets, void *stream, int io, float *d_means = nullptr) {
     if (n_clips == 0) return MELSPEC_OK;
     if (!h_offsets || !h_lengths) return fail(MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL");
     std::vector<uint64_t> frames(n_clips);
@@ -513,8 +517,10 @@ static int fbank_ragged(melspec_fbank *fb, const void *vd_pcm, const uint64_t *h
         for (uint32_t i = 0; i < n_clips && by_clip; ++i) by_clip = h_out_offsets[i] % 4 == 0;
     BatchPlan pl;
     RaggedSlot *slot = nullptr;
+    if (d_means && std::find(frames.begin(), frames.end(), uint64_t{0}) != frames.end())
+        HIP_TRY(hipMemsetAsync(d_means, 0, static_cast<size_t>(n_clips) * nm * sizeof(float), s));
     rc = plan_ragged(fb->ragged, s, static_cast<const float *>(vd_pcm), d_rows, h_offsets, frames, split ? nullptr : h_out_offsets, n_clips, nm, fused ? kFbFPW : 1, pl, slot, by_clip);
-    if (!rc) rc = fbank_launch(fb, pl, n_clips, longest, s, io, nullptr, vd_out, d_own ? d_own : pl.desc.d_out_off);
+    if (!rc) rc = fbank_launch(fb, pl, n_clips, longest, s, io, d_means, vd_out, d_own ? d_own : pl.desc.d_out_off);
     plan_ragged_done(slot, s);
     return rc;
 }
@@ -523,6 +529,36 @@ int melspec_fbank_compute_ragged_device(melspec_fbank *fb, const float *d_pcm, c
                                         uint32_t n_clips, float *d_out, const uint64_t *h_out_offsets, void *stream) {
     if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
     return fbank_ragged(fb, d_pcm, h_offsets, h_lengths, n_clips, d_out, h_out_offsets, stream, 0);
+}
+
+// the verdict of an argument check of the split calls as the call's status (the unsupported object is worded by the _split_io calls)
+static int fbank_split_verdict(const FbankSplitArgs &a) {
+    if (a.verdict != kFbankSplitFail) return MELSPEC_OK;
+    return a.msg ? fail(a.status, a.msg) : a.status;
+}
+// no clip of the batch has a frame: there are no rows, and the mean of nothing is reported as +0.0 (melspec_fbank_compute_uniform_device_split)
+static int fbank_split_zero_means(melspec_fbank *fb, float *d_means, uint32_t n_clips, void *stream) {
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    HIP_TRY(hipMemsetAsync(d_means, 0, static_cast<size_t>(n_clips) * fb->cfg.num_mel_bins * sizeof(float), stream ? static_cast<hipStream_t>(stream) : fb->stream));
+    return MELSPEC_OK;
+}
+static uint64_t fbank_total_frames(const melspec_fbank *fb, const uint64_t *h_lengths, uint32_t n_clips) {
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_clips; ++i) total += fbank_frames(fb, h_lengths[i]);
+    return total;
+}
+
+// The split output of a ragged batch: melspec_fbank_compute_ragged_device's routing with d_means threaded through -- large batches by clip
+// (fbank512_clip_kernel publishes the means), everything else through the wave kernel (or the generic one) and cmn_kernel, which then
+// writes the means and leaves the rows.  Both sum by the fixed tree: the bits do not depend on the route.
+int melspec_fbank_compute_ragged_device_split(melspec_fbank *fb, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
+                                              float *d_rows, const uint64_t *h_rows_offsets, float *d_means, void *stream) {
+    if (!fb) return fail(MELSPEC_ERR_INVALID_ARG, "fbank is NULL");
+    const uint64_t total = n_clips && h_offsets && h_lengths ? fbank_total_frames(fb, h_lengths, n_clips) : 0;
+    const FbankSplitArgs a = fbank_split_args(fb->cfg.apply_cmn != 0, true, true, n_clips, h_offsets, h_lengths, total, d_pcm, d_rows, d_means, 0);
+    if (a.verdict == kFbankSplitZero) return fbank_split_zero_means(fb, d_means, n_clips, stream);
+    if (a.verdict != kFbankSplitGo) return fbank_split_verdict(a);
+    return fbank_ragged(fb, d_pcm, h_offsets, h_lengths, n_clips, d_rows, h_rows_offsets, stream, 0, d_means);
 }
 
 // The same with the clip table in device memory (see melspec_compute_ragged_device_desc).
@@ -1576,6 +1612,145 @@ int melspec_fbank_compute_host_io(melspec_fbank *fb, const void *samples, int pc
     int io, rc = fbank_io_args(fb, pcm_dtype, out_dtype, io);
     if (rc) return rc;
     return fbank_host(fb, samples, n_samples, out, out_capacity_elems, n_frames, io);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------
+// Kaldi fbank, the split output with int16 PCM in / f16, bf16 rows out (melspec_fbank_compute_*_split_io): see include/melspec_hip.h.
+// One pass: the workgroup-per-clip kernel's (sample, row) sibling (fbank512_kaldi_split_io_kernels.hpp) writes the caller's rows and the
+// clips' means; fb->rows32 is never touched.  The plans are the f32 calls' -- they count elements --, the launch shape is the f32 clip
+// kernel's (route512), the kernel comes from the side table of fbank512_kaldi_split_io.hip.  (F32, F32) IS the f32 split call.
+// ------------------------------------------------------------------------------------
+namespace {
+bool fbank_split_io_supported(const melspec_fbank *fb) { return fbank_split_io_ok(fbank_shape(fb), fb->cfg.num_mel_bins); }       // (apply_cmn is part of the shape: cmn_power)
+
+int fbank_split_io_verdict(const melspec_fbank *fb, const FbankSplitArgs &a) {
+    if (a.verdict != kFbankSplitFail || a.msg) return fbank_split_verdict(a);
+    char geo[320];
+    std::snprintf(geo, sizeof(geo), "sample_rate = %g, frame_length = %d samples, frame_shift = %d samples, num_mel_bins = %d, low_freq = %g, high_freq = %g, use_power = %d",
+                  fb->cfg.sample_rate, fb->frame_len, fb->frame_shift, fb->cfg.num_mel_bins, fb->cfg.low_freq, fb->cfg.high_freq, fb->cfg.use_power);
+    g_last_error = std::string("the split output with int16 PCM / f16, bf16 rows is computed by the fused fbank path with the compile-time 80-bin Kaldi bank on power "
+                               "spectra only (16 kHz, 400-sample frames, any frame shift, 80 bins, low_freq 20, high_freq Nyquist, use_power on); this object is ") + geo +
+                   (fb->use_generic ? " on the generic path (melspec_fbank_use_generic)" : "");
+    return a.status;
+}
+
+// one launch of the kernel of combination io over a uniform or a ragged-by-clip plan; fpc: frames per clip of a uniform batch
+int launch_split_io(melspec_fbank *fb, bool ragged, int io, const BatchPlan &pl, uint64_t fpc, float *d_means, hipStream_t s) {
+    static std::atomic<uint64_t> attr_done[kFbankSplitIoKernels];          // one bit per device: function attributes are per device
+    const int nm = fb->cfg.num_mel_bins;
+    const Launch512 l = route512(fbank_shape(fb), fbank_split_io_batch(ragged)).run;
+    const Lds512Sizes z{fb->fast_lds, 0, nm};
+    const int at = fbank_split_io_slot(ragged, io);
+    const FbankClipSplitIoKernel kernel = kaldi_split_io_kernel(ragged, io);
+    if (at < 0 || !kernel || !is_clip(l.kernel) || lds512(l.lds, z) > kLdsLimit) return fail(MELSPEC_ERR_INTERNAL, "launch_split_io: the object has no kernel for this batch");
+    if (int rc = allow_big_lds_once(attr_done[at], "hipFuncSetAttribute(fbank512_clip_split_io_kernel)", kernel)) return rc;
+    const FbankClipParams q{fbank_fast_params(fb, pl.desc), fpc, 0, d_means};
+    hipLaunchKernelGGL(kernel, dim3(grid512(l, pl.desc.n_units, fb->dev.cus)), dim3(l.waves * 64), lds512(l.lds, z), s, q);
+    HIP_TRY(hipGetLastError());
+    return MELSPEC_OK;
+}
+constexpr uint64_t kSplitIoMaxFrames = 1ull << 31;          // the kernel counts a clip's frames in 31 bits (clip_ragged_ok)
+}  // namespace
+
+extern "C" {
+
+int melspec_fbank_supports_split_io(const melspec_fbank *fb, int pcm_dtype, int out_dtype) {
+    return fb && fbank_split_io_pcm_known(pcm_dtype) && fbank_split_io_out_known(out_dtype) && fbank_split_io_supported(fb) ? 1 : 0;
+}
+
+int melspec_fbank_compute_uniform_device_split_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips,
+                                                  void *d_rows, int out_dtype, float *d_means, void *stream) {
+    int io;
+    const FbankSplitArgs codes = fbank_split_io_codes(fb != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kFbankSplitFail) return fbank_split_verdict(codes);
+    if (io == 0) return melspec_fbank_compute_uniform_device_split(fb, static_cast<const float *>(d_pcm), clip_stride, clip_len, n_clips, static_cast<float *>(d_rows), d_means, stream);
+    const uint64_t fpc = fbank_frames(fb, clip_len);
+    const FbankSplitArgs a = fbank_split_args(fb->cfg.apply_cmn != 0, fbank_split_io_supported(fb), false, n_clips, nullptr, nullptr, fpc, d_pcm, d_rows, d_means, io);
+    if (a.verdict == kFbankSplitZero) return fbank_split_zero_means(fb, d_means, n_clips, stream);
+    if (a.verdict != kFbankSplitGo) return fbank_split_io_verdict(fb, a);
+    if (fpc >= kSplitIoMaxFrames) return fail(MELSPEC_ERR_UNSUPPORTED, "a clip of 2^31 frames or more");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    // the f32 call's batch; the plan counts elements, the kernel reads the two pointers as its own types
+    const BatchPlan pl = plan_uniform(static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), clip_stride, fpc, n_clips, fb->cfg.num_mel_bins, kFbFPW);
+    return launch_split_io(fb, false, io, pl, fpc, d_means, s);
+}
+
+int melspec_fbank_compute_ragged_device_split_io(melspec_fbank *fb, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
+                                                 void *d_rows, int out_dtype, const uint64_t *h_rows_offsets, float *d_means, void *stream) {
+    int io;
+    const FbankSplitArgs codes = fbank_split_io_codes(fb != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kFbankSplitFail) return fbank_split_verdict(codes);
+    if (io == 0)
+        return melspec_fbank_compute_ragged_device_split(fb, static_cast<const float *>(d_pcm), h_offsets, h_lengths, n_clips, static_cast<float *>(d_rows), h_rows_offsets, d_means, stream);
+    const bool ok = fbank_split_io_supported(fb);
+    std::vector<uint64_t> frames;
+    uint64_t total = 0, longest = 0;
+    bool frameless = false;
+    if (ok && n_clips && h_offsets && h_lengths) {
+        frames.resize(n_clips);
+        for (uint32_t i = 0; i < n_clips; ++i) {
+            frames[i] = fbank_frames(fb, h_lengths[i]);
+            total += frames[i];
+            longest = std::max(longest, frames[i]);
+            frameless |= frames[i] == 0;
+        }
+    }
+    const FbankSplitArgs a = fbank_split_args(fb->cfg.apply_cmn != 0, ok, true, n_clips, h_offsets, h_lengths, total, d_pcm, d_rows, d_means, io);
+    if (a.verdict == kFbankSplitZero) return fbank_split_zero_means(fb, d_means, n_clips, stream);
+    if (a.verdict != kFbankSplitGo) return fbank_split_io_verdict(fb, a);
+    if (longest >= kSplitIoMaxFrames) return fail(MELSPEC_ERR_UNSUPPORTED, "a clip of 2^31 frames or more");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : fb->stream;
+    const int nm = fb->cfg.num_mel_bins;
+    // the plan's order ends at the last clip with a frame: the kernel never sees the others, their mean slots are zeroed here
+    if (frameless) HIP_TRY(hipMemsetAsync(d_means, 0, static_cast<size_t>(n_clips) * nm * sizeof(float), s));
+    BatchPlan pl;
+    RaggedSlot *slot = nullptr;
+    int rc = plan_ragged(fb->ragged, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), h_offsets, frames, h_rows_offsets, n_clips, nm, kFbFPW, pl, slot, true);
+    if (!rc) rc = launch_split_io(fb, true, io, pl, 0, d_means, s);
+    plan_ragged_done(slot, s);
+    return rc;
+}
+
+// One clip from host memory: the bytes of the caller's sample type go up, the rows of the caller's row type and the 80 means come back (the
+// means behind the rows in the object's device-to-host buffer, at the next multiple of sixteen bytes).
+int melspec_fbank_compute_host_split_io(melspec_fbank *fb, const void *samples, int pcm_dtype, size_t n_samples, void *rows, int out_dtype, size_t rows_capacity_elems,
+                                        float *means, size_t *n_frames) {
+    int io;
+    const FbankSplitArgs codes = fbank_split_io_codes(fb != nullptr, pcm_dtype, out_dtype, io);
+    if (codes.verdict == kFbankSplitFail) return fbank_split_verdict(codes);
+    if (n_frames) *n_frames = 0;
+    const uint64_t frames = fbank_frames(fb, n_samples);
+    const uint64_t nm = static_cast<uint64_t>(fb->cfg.num_mel_bins), need = frames * nm;
+    const size_t in_bytes = fbank_split_io_pcm_bytes(pcm_dtype), out_bytes = fbank_split_io_out_bytes(out_dtype);
+    // the device call's checks in its order; of the host pointers only whether they are there ((F32, F32) runs on any object; host memory
+    // needs no alignment, the staging buffers have it)
+    static const float here = 0.0f;
+    const FbankSplitArgs a = fbank_split_args(fb->cfg.apply_cmn != 0, io == 0 || fbank_split_io_supported(fb), false, 1, nullptr, nullptr, frames, samples ? &here : nullptr,
+                                              rows ? &here : nullptr, means, 0);
+    if (a.verdict == kFbankSplitZero) {
+        std::fill(means, means + nm, 0.0f);
+        return MELSPEC_OK;
+    }
+    if (a.verdict != kFbankSplitGo) return fbank_split_io_verdict(fb, a);
+    if (rows_capacity_elems < need) return fail(MELSPEC_ERR_CAPACITY, "output buffer too small");
+    HIP_TRY(hipSetDevice(fb->dev.device));
+    const size_t means_at = (static_cast<size_t>(need) * out_bytes + 15) & ~static_cast<size_t>(15);
+    int rc;
+    if ((rc = fb->h2d.ensure(n_samples * in_bytes))) return rc;
+    if ((rc = fb->d2h.ensure(means_at + nm * sizeof(float)))) return rc;
+    HIP_TRY(hipMemcpyAsync(fb->h2d.p, samples, n_samples * in_bytes, hipMemcpyHostToDevice, fb->stream));
+    char *d_rows = static_cast<char *>(fb->d2h.p);
+    float *d_means = reinterpret_cast<float *>(d_rows + means_at);
+    if ((rc = melspec_fbank_compute_uniform_device_split_io(fb, fb->h2d.p, pcm_dtype, n_samples, n_samples, 1, d_rows, out_dtype, d_means, fb->stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(rows, d_rows, need * out_bytes, hipMemcpyDeviceToHost, fb->stream));
+    HIP_TRY(hipMemcpyAsync(means, d_means, nm * sizeof(float), hipMemcpyDeviceToHost, fb->stream));
+    HIP_TRY(hipStreamSynchronize(fb->stream));
+    if (n_frames) *n_frames = static_cast<size_t>(frames);
+    return MELSPEC_OK;
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@
 //     4 + 2 bytes per element instead of 4 + 4.  Its body is cmn_kernel's, the same text included again (fbank512_cmn_body.inc) with
 //     kSplit = true.
 // Instantiated in a translation unit of their own (fbank512_kaldi_io.hip): a new neighbour in a unit changes the schedule of the kernels
-// that are already there.  fbank512_clip_kernel (the workgroup-per-clip form, whose waves wait for each other) has no such variant.
+// that are already there.  fbank512_clip_kernel (the workgroup-per-clip form, whose waves wait for each other) has its typed variant in
+// fbank512_kaldi_split_io_kernels.hpp, for the split output only: these calls, which subtract, stay on the two kernels here.
 #pragma once
 #include "fbank512_kernels.hpp"
 #include "io_types.hpp"

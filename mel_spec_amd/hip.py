@@ -833,6 +833,82 @@ def blm_compute_ragged_split_io(fe: BatchLogMelSpectrogram, clips, out_dtype=Non
     return [(r, stat[0, i].copy(), stat[1, i].copy()) if r.shape[1] else (r, None, None) for i, r in enumerate(rows)]
 
 
+# -- the Kaldi fbank's split output for ragged batches and with 16-bit ends (melspec_fbank_*_split, *_split_io): int16 PCM in, f16 / bf16
+# rows out (the rows before CMN, rounded to nearest even once), f32 means (the uniform f32 split's bits; +0.0 for a clip without a frame);
+# module-level for the same reason.  Strides, offsets and capacities count elements. -------------------------------------------------------
+def fbank_supports_split_io(fb: Fbank, pcm_dtype: int, out_dtype: int) -> bool:
+    return bool(lib().melspec_fbank_supports_split_io(fb._h, pcm_dtype, out_dtype))
+
+
+def fbank_compute_ragged_device_split(fb: Fbank, d_pcm: int, offsets, lengths, d_rows: int, d_means: int, rows_offsets=None, stream: int = 0) -> None:
+    """melspec_fbank_compute_ragged_device_split: clip i = d_pcm[offsets[i] : + lengths[i]] -> its rows before CMN at d_rows + rows_offsets[i]
+    floats (None = packed) and its column means at d_means[i][num_mel_bins].  Asynchronous on `stream`."""
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_fbank_compute_ragged_device_split(fb._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0], C.c_void_p(d_rows), p_out, C.c_void_p(d_means),
+                                                           C.c_void_p(stream)))
+
+
+def fbank_compute_uniform_device_split_io(fb: Fbank, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int, out_dtype: int,
+                                          d_means: int, stream: int = 0) -> None:
+    """compute_uniform_device_split with `pcm_dtype` samples in and `out_dtype` rows out: d_rows = [clip][frame][num_mel_bins] of the row
+    type, d_means = [clip][num_mel_bins] f32.  Asynchronous on `stream`."""
+    _check(lib().melspec_fbank_compute_uniform_device_split_io(fb._h, C.c_void_p(d_pcm), pcm_dtype, clip_stride, clip_len, n_clips, C.c_void_p(d_rows), out_dtype,
+                                                               C.c_void_p(d_means), C.c_void_p(stream)))
+
+
+def fbank_compute_ragged_device_split_io(fb: Fbank, d_pcm: int, pcm_dtype: int, offsets, lengths, d_rows: int, out_dtype: int, d_means: int, rows_offsets=None,
+                                         stream: int = 0) -> None:
+    """fbank_compute_ragged_device_split with `pcm_dtype` samples in and `out_dtype` rows out; offsets and rows_offsets count elements of
+    their types.  Asynchronous on `stream`."""
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_fbank_compute_ragged_device_split_io(fb._h, C.c_void_p(d_pcm), pcm_dtype, p_off, p_len, tabs[0].shape[0], C.c_void_p(d_rows), out_dtype, p_out,
+                                                              C.c_void_p(d_means), C.c_void_p(stream)))
+
+
+def fbank_compute_split_io(fb: Fbank, samples, out_dtype=None):
+    """One host clip -> (rows (frames, num_mel_bins), means (num_mel_bins,)): melspec_fbank_compute_host_split_io.  An np.int16 array is
+    taken as 16-bit PCM (value = sample / 32768, exactly); out_dtype "f16" returns np.float16 rows, "bf16" the bfloat16 bit patterns as
+    np.uint16; the means are np.float32."""
+    x, pcm = _pcm_clip(samples)
+    out = _out_code(out_dtype)
+    nf = fb.num_frames(x.shape[0])
+    rows, means = np.zeros((nf, fb.num_mel_bins), _OUT_NUMPY[out]), np.zeros(fb.num_mel_bins, np.float32)
+    got = C.c_size_t(0)
+    _check(lib().melspec_fbank_compute_host_split_io(fb._h, x.ctypes.data_as(C.c_void_p), pcm, x.shape[0], rows.ctypes.data_as(C.c_void_p), out, rows.size, _fp(means),
+                                                     C.byref(got)))
+    assert got.value == nf
+    return rows, means
+
+
+def fbank_compute_ragged_split_io(fb: Fbank, clips, out_dtype=None) -> list:
+    """list of 1-D host arrays of any lengths (all np.int16 = 16-bit PCM, otherwise f32) -> list of (rows (frames, num_mel_bins) of
+    out_dtype, means (num_mel_bins,)), one launch; a clip without a frame gives (zeros((0, num_mel_bins)), zeros(num_mel_bins))"""
+    arrs = [np.asarray(c).reshape(-1) for c in clips]
+    pcm = PCM_S16 if arrs and all(a.dtype == np.int16 for a in arrs) else PCM_F32
+    in_t = np.int16 if pcm == PCM_S16 else np.float32
+    arrs = [np.ascontiguousarray(a, dtype=in_t) for a in arrs]
+    out = _out_code(out_dtype)
+    out_t = np.dtype(_OUT_NUMPY[out])
+    lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if len(arrs) else np.zeros(0, np.uint64)
+    flat = np.concatenate(arrs) if arrs and int(lens.sum()) else np.zeros(1, in_t)
+    nm, n = fb.num_mel_bins, len(arrs)
+    if n == 0:
+        return []
+    shapes = [(fb.num_frames(int(k)), nm) for k in lens]
+    total = sum(r * c for r, c in shapes)
+    din, drows, dmeans = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * out_t.itemsize, 16)), DeviceBuffer(n * nm * 4)
+    try:
+        din.upload(flat)
+        fbank_compute_ragged_device_split_io(fb, din.ptr, pcm, offs, lens, drows.ptr, out, dmeans.ptr)
+        fb.synchronize()
+        rows = _split(drows.download((max(total, 1),), out_t)[:total], shapes)
+        means = dmeans.download((n, nm))
+    finally:
+        din.free(); drows.free(); dmeans.free()
+    return [(r, means[i].copy()) for i, r in enumerate(rows)]
+
+
 # -- the ragged call with its clip table in device memory (melspec_blm_compute_ragged_device_desc): module-level for the same reason -----------
 def blm_compute_ragged_device_desc(fe: BatchLogMelSpectrogram, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, d_out_offsets: int,
                                    max_total_columns: int, max_clip_samples: int, d_rejected: int = 0, stream: int = 0) -> None:

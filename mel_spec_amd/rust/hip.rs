@@ -76,6 +76,16 @@ unsafe extern "C" {
                                               n_clips: u32, d_out: *mut c_void, out_dtype: c_int, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
     fn melspec_fbank_compute_host_io(fb: *mut FbankHandle, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, out: *mut c_void, out_dtype: c_int,
                                      out_capacity_elems: usize, n_frames: *mut usize) -> c_int;
+    fn melspec_fbank_supports_split_io(fb: *const FbankHandle, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
+    fn melspec_fbank_compute_ragged_device_split(fb: *mut FbankHandle, d_pcm: *const f32, h_offsets: *const u64, h_lengths: *const u64, n_clips: u32,
+                                                 d_rows: *mut f32, h_rows_offsets: *const u64, d_means: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_fbank_compute_uniform_device_split_io(fb: *mut FbankHandle, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64,
+                                                     n_clips: u32, d_rows: *mut c_void, out_dtype: c_int, d_means: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_fbank_compute_ragged_device_split_io(fb: *mut FbankHandle, d_pcm: *const c_void, pcm_dtype: c_int, h_offsets: *const u64,
+                                                    h_lengths: *const u64, n_clips: u32, d_rows: *mut c_void, out_dtype: c_int,
+                                                    h_rows_offsets: *const u64, d_means: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_fbank_compute_host_split_io(fb: *mut FbankHandle, samples: *const c_void, pcm_dtype: c_int, n_samples: usize, rows: *mut c_void, out_dtype: c_int,
+                                           rows_capacity_elems: usize, means: *mut f32, n_frames: *mut usize) -> c_int;
     fn melspec_fbank_compute_batch_host(fb: *mut FbankHandle, samples: *const f32, offsets: *const u64, lengths: *const u64, n_clips: u32,
                                         out: *mut f32, out_offsets: *const u64, cap: usize, total_frames: *mut u64) -> c_int;
     // BatchLogMelSpectrogram (src/mel.rs:171-418)
@@ -758,6 +768,52 @@ impl HipFbank {
                                           flat.len(), &mut got)
         })?;
         Ok((flat, got))
+    }
+    /// Additive: the split output with 16-bit ends is available for this object and this (sample, row) pair.
+    pub fn supports_split_io(&self, pcm_dtype: i32, out_dtype: i32) -> bool {
+        unsafe { melspec_fbank_supports_split_io(self.fb, pcm_dtype as c_int, out_dtype as c_int) != 0 }
+    }
+    /// Additive: the split output of a ragged f32 batch -- the rows before CMN at `rows_offsets` (floats; `None`: packed) and the clips'
+    /// column means, `[clip][num_mel_bins]`.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`; `d_rows` must hold the rows of all clips where the offsets put them and
+    /// `d_means` `offsets.len() * num_mel_bins` floats.
+    pub unsafe fn compute_ragged_device_split(&mut self, d_pcm: *const f32, offsets: &[u64], lengths: &[u64], d_rows: *mut f32, rows_offsets: Option<&[u64]>,
+                                              d_means: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        check(melspec_fbank_compute_ragged_device_split(self.fb, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_rows,
+                                                        rows_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), d_means, stream))
+    }
+    /// Additive: the same for equal clips with `pcm_dtype` samples in and `out_dtype` rows out (rounded once); the means stay f32.
+    ///
+    /// # Safety
+    /// As `compute_uniform_device_io`, plus `d_means` of `n_clips * num_mel_bins` floats.
+    pub unsafe fn compute_uniform_device_split_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, clip_stride: u64, clip_len: u64, n_clips: u32,
+                                                  d_rows: *mut c_void, out_dtype: i32, d_means: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_fbank_compute_uniform_device_split_io(self.fb, d_pcm, pcm_dtype as c_int, clip_stride, clip_len, n_clips, d_rows, out_dtype as c_int, d_means, stream))
+    }
+    /// Additive: ... and for clips of any lengths; offsets count elements of their types.
+    ///
+    /// # Safety
+    /// As `compute_ragged_device_io`, plus `d_means` of `offsets.len() * num_mel_bins` floats.
+    pub unsafe fn compute_ragged_device_split_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, offsets: &[u64], lengths: &[u64], d_rows: *mut c_void,
+                                                 out_dtype: i32, rows_offsets: Option<&[u64]>, d_means: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        check(melspec_fbank_compute_ragged_device_split_io(self.fb, d_pcm, pcm_dtype as c_int, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, d_rows,
+                                                           out_dtype as c_int, rows_offsets.map_or(std::ptr::null(), |o| o.as_ptr()), d_means, stream))
+    }
+    /// Additive: one clip of 16-bit PCM -> (the bf16 rows before CMN as bit patterns, the f32 column means, the frame count).
+    pub fn compute_split_s16_bf16(&mut self, samples: &[i16]) -> Result<(Vec<u16>, Vec<f32>, usize), HipError> {
+        let frames = unsafe { melspec_fbank_num_frames(self.fb, samples.len()) };
+        let mut flat = vec![0u16; frames * self.num_mel_bins];
+        let mut means = vec![0f32; self.num_mel_bins];
+        let mut got = 0usize;
+        check(unsafe {
+            melspec_fbank_compute_host_split_io(self.fb, samples.as_ptr() as *const c_void, PCM_S16, samples.len(), flat.as_mut_ptr() as *mut c_void, OUT_BF16,
+                                                flat.len(), means.as_mut_ptr(), &mut got)
+        })?;
+        Ok((flat, means, got))
     }
 }
 impl Drop for HipFbank {
