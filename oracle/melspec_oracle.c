@@ -534,8 +534,11 @@ void oracle_kaldi_mel_filterbank(double sample_rate, int fft_size, int num_mel_b
     free(hz);
 }
 
-/* src/fbank.rs:141-236 Fbank::compute -> out [frames][num_mel_bins] f32. Returns frames. */
-int64_t oracle_fbank_compute(const oracle_fbank_config *cfg, const float *samples, int64_t len, float *out) {
+/* src/fbank.rs:141-236 Fbank::compute, one body for the f32-writing entry point and the unrounded one: out [frames][num_mel_bins] f32
+ * (CMN applied when the config asks), wide the same rows in double before the f32 rounding and before CMN, energies the mel energies
+ * before the floor; any of the three may be NULL.  Returns frames. */
+static int64_t fbank_compute_body(const oracle_fbank_config *cfg, const float *samples, int64_t len, float *out, double *wide,
+                                  double *energies) {
     const int frame_len = oracle_fbank_frame_length(cfg);
     const int frame_shift = oracle_fbank_frame_shift(cfg);
     const int fft_size = oracle_fbank_fft_size(cfg);
@@ -584,14 +587,16 @@ int64_t oracle_fbank_compute(const oracle_fbank_config *cfg, const float *sample
             double e = 0.0;
             for (int j = fb.row_ptr[m]; j < fb.row_ptr[m + 1]; ++j) e += fb.w[j] * power[fb.bin[j]];
             const double floor_v = (cfg->energy_floor > 0.0) ? cfg->energy_floor : (double)FLT_EPSILON;
+            if (energies) energies[f * nm + m] = e;
             e = fmax(e, floor_v);
             if (cfg->use_log_fbank) e = log(e);
-            out[f * nm + m] = (float)e;
+            if (wide) wide[f * nm + m] = e;
+            if (out) out[f * nm + m] = (float)e;
         }
     }
     /* CMN (src/fbank.rs:224-233): per mel column, f32 mean = sequential f32 sum / n
      * (ndarray's mean() on a strided column view folds left-to-right in f32). */
-    if (cfg->apply_cmn && num_frames > 0) {
+    if (out && cfg->apply_cmn && num_frames > 0) {
         for (int m = 0; m < nm; ++m) {
             float sum = 0.0f;
             for (int64_t f = 0; f < num_frames; ++f) sum = sum + out[f * nm + m];
@@ -602,6 +607,16 @@ int64_t oracle_fbank_compute(const oracle_fbank_config *cfg, const float *sample
     fft_plan_free(&pl); sparse_free(&fb);
     free(window); free(dense); free(cbuf); free(frame_buf); free(power);
     return num_frames;
+}
+
+int64_t oracle_fbank_compute(const oracle_fbank_config *cfg, const float *samples, int64_t len, float *out) {
+    return fbank_compute_body(cfg, samples, len, out, NULL, NULL);
+}
+
+/* The same loops without the f32 rounding: wide [frames][num_mel_bins] = the rows before CMN (apply_cmn is not looked at), energies the
+ * mel energies before the floor.  What the statistic tests measure the f64 kernels against (tests/test_f64_statistics.py). */
+int64_t oracle_fbank_compute_wide(const oracle_fbank_config *cfg, const float *samples, int64_t len, double *wide, double *energies) {
+    return fbank_compute_body(cfg, samples, len, NULL, wide, energies);
 }
 
 /* Many clips through fbank, clips across OpenMP threads. out [clip][frame][mel]. */
@@ -769,11 +784,14 @@ int64_t oracle_blm_compute_f32(const oracle_blm_config *c, const float *samples,
     return padded;
 }
 
-/* Same definition with f64 FFT / power / projection / ln; keeps the f32-rounded inputs of the reference. */
-int64_t oracle_blm_compute_f64(const oracle_blm_config *c, const float *samples, int64_t len, float *out, int64_t *valid_out) {
+/* Same definition with f64 FFT / power / projection / ln; keeps the f32-rounded inputs of the reference.  One body: out the f32 image
+ * (normalised when the config asks), wide [n_mels][padded] = log(e + guard) in double, un-normalised, energies = e; wide and energies
+ * may be NULL and are zero in the pad columns. */
+static int64_t blm_compute_f64_body(const oracle_blm_config *c, const float *samples, int64_t len, float *out, double *wide,
+                                    double *energies, int64_t *valid_out) {
     const int64_t valid = oracle_blm_num_frames(c, len), padded = oracle_blm_padded_frames(c, valid);
     if (valid_out) *valid_out = valid;
-    if (len == 0 || !out) return padded;
+    if (len == 0 || !(out || wide || energies)) return padded;
     const int N = c->n_fft, bins = N / 2 + 1, pad = c->center ? N / 2 : 0;
     float *wave = (float *)malloc(sizeof(float) * (size_t)len), *window = (float *)malloc(sizeof(float) * (size_t)N);
     double *power = (double *)malloc(sizeof(double) * (size_t)bins);
@@ -781,7 +799,11 @@ int64_t oracle_blm_compute_f64(const oracle_blm_config *c, const float *samples,
     sparse_fb fb; double *dense;
     blm_prepare(c, samples, len, wave, window, &fb, &dense);
     fft_plan pl; fft_plan_init(&pl, N);
-    for (int64_t i = 0; i < (int64_t)c->n_mels * padded; ++i) out[i] = 0.0f;
+    for (int64_t i = 0; i < (int64_t)c->n_mels * padded; ++i) {
+        if (out) out[i] = 0.0f;
+        if (wide) wide[i] = 0.0;
+        if (energies) energies[i] = 0.0;
+    }
     for (int64_t f = 0; f < valid; ++f) {
         const int64_t start = f * c->hop_length;
         for (int i = 0; i < N; ++i) {
@@ -794,13 +816,27 @@ int64_t oracle_blm_compute_f64(const oracle_blm_config *c, const float *samples,
         for (int m = 0; m < c->n_mels; ++m) {
             double e = 0.0;
             for (int j = fb.row_ptr[m]; j < fb.row_ptr[m + 1]; ++j) e += (double)(float)fb.w[j] * power[fb.bin[j]];
-            out[(int64_t)m * padded + f] = (float)log(e + (double)c->log_zero_guard);
+            const double v = log(e + (double)c->log_zero_guard);
+            if (energies) energies[(int64_t)m * padded + f] = e;
+            if (wide) wide[(int64_t)m * padded + f] = v;
+            if (out) out[(int64_t)m * padded + f] = (float)v;
         }
     }
-    if (c->normalize_per_feature) blm_normalize(out, c->n_mels, valid, padded);
+    if (out && c->normalize_per_feature) blm_normalize(out, c->n_mels, valid, padded);
     fft_plan_free(&pl); sparse_free(&fb);
     free(dense); free(wave); free(window); free(power); free(buf);
     return padded;
+}
+
+int64_t oracle_blm_compute_f64(const oracle_blm_config *c, const float *samples, int64_t len, float *out, int64_t *valid_out) {
+    return blm_compute_f64_body(c, samples, len, out, NULL, NULL, valid_out);
+}
+
+/* The unrounded twin: wide = log(e + guard) in double, never normalised; energies = e.  Both [n_mels][padded]; with both NULL only the
+ * sizes are returned. */
+int64_t oracle_blm_compute_f64_wide(const oracle_blm_config *c, const float *samples, int64_t len, double *wide, double *energies,
+                                    int64_t *valid_out) {
+    return blm_compute_f64_body(c, samples, len, NULL, wide, energies, valid_out);
 }
 
 /* ------------------------------------------------------------------------- */

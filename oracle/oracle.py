@@ -94,6 +94,8 @@ def lib():
         L.oracle_kaldi_mel_filterbank.argtypes = [C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, f64p]
         L.oracle_fbank_compute.restype = C.c_int64
         L.oracle_fbank_compute.argtypes = [C.POINTER(FbankConfig), f32p, C.c_int64, f32p]
+        L.oracle_fbank_compute_wide.restype = C.c_int64
+        L.oracle_fbank_compute_wide.argtypes = [C.POINTER(FbankConfig), f32p, C.c_int64, f64p, f64p]
         L.oracle_fbank_batch.restype = C.c_int64
         L.oracle_fbank_batch.argtypes = [C.POINTER(FbankConfig), f32p, C.c_int64, C.c_int64, C.c_int, f32p, C.c_int]
         L.oracle_synth_pcm.argtypes = [C.c_uint32, C.c_uint64, C.c_uint64, f32p]
@@ -102,6 +104,8 @@ def lib():
             fn = getattr(L, name)
             fn.restype = C.c_int64
             fn.argtypes = [C.POINTER(BlmConfig), f32p, C.c_int64, f32p, C.POINTER(C.c_int64)]
+        L.oracle_blm_compute_f64_wide.restype = C.c_int64
+        L.oracle_blm_compute_f64_wide.argtypes = [C.POINTER(BlmConfig), f32p, C.c_int64, f64p, f64p, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -344,6 +348,21 @@ def fbank_compute(samples, cfg: FbankConfig | None = None) -> np.ndarray:
     return out
 
 
+def fbank_compute_wide(samples, cfg: FbankConfig | None = None):
+    """Fbank::compute's loops without the f32 rounding -> (rows before CMN, mel energies before the floor), f64 [frames, num_mel_bins]
+    each; apply_cmn is not looked at."""
+    cfg = cfg or fbank_default_config()
+    x = _f32(samples)
+    fl = lib().oracle_fbank_frame_length(C.byref(cfg))
+    fs = lib().oracle_fbank_frame_shift(C.byref(cfg))
+    nf = 0 if x.shape[0] < fl else 1 + (x.shape[0] - fl) // fs
+    wide, e = np.zeros((nf, cfg.num_mel_bins), np.float64), np.zeros((nf, cfg.num_mel_bins), np.float64)
+    if nf:
+        got = lib().oracle_fbank_compute_wide(C.byref(cfg), _p(x, C.c_float), x.shape[0], _p(wide, C.c_double), _p(e, C.c_double))
+        assert got == nf
+    return wide, e
+
+
 def fbank_batch(clips, cfg: FbankConfig | None = None, n_threads=0) -> np.ndarray:
     cfg = cfg or fbank_default_config()
     x = _f32(clips)
@@ -377,6 +396,19 @@ def blm_compute(samples, cfg: BlmConfig | None = None, f64: bool = True):
     if x.shape[0]:
         fn(C.byref(cfg), _p(x, C.c_float), x.shape[0], _p(out, C.c_float), C.byref(valid))
     return out, int(valid.value)
+
+
+def blm_compute_wide(samples, cfg: BlmConfig | None = None):
+    """blm_compute(f64=True) without the f32 rounding and never normalised -> (log(e + guard), e, valid_frames), f64 [n_mels, cols]"""
+    cfg = cfg or blm_default_config()
+    x = _f32(samples).reshape(-1)
+    fn = lib().oracle_blm_compute_f64_wide
+    valid = C.c_int64(0)
+    cols = fn(C.byref(cfg), _p(x, C.c_float), x.shape[0], None, None, C.byref(valid))
+    wide, e = np.zeros((cfg.n_mels, cols), np.float64), np.zeros((cfg.n_mels, cols), np.float64)
+    if x.shape[0]:
+        fn(C.byref(cfg), _p(x, C.c_float), x.shape[0], _p(wide, C.c_double), _p(e, C.c_double), C.byref(valid))
+    return wide, e, int(valid.value)
 
 
 def project_power(filters, power) -> np.ndarray:

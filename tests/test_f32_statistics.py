@@ -57,28 +57,30 @@ G512_128 = (512, 160, SR, 128)
 
 # ---- 1. the yardstick ---------------------------------------------------------------------------------------------------------------
 
-def whisper_f32(x, n_fft, hop, n_mels, sr, *, window=None, bank=None):
+def whisper_f32(x, n_fft, hop, n_mels, sr, *, window=None, bank=None, dtype=np.float32, energies=False):
     """compute_mel_spectrogram_cpu in float32 throughout: frames x Hann, scipy's float32 rfft, re^2 + im^2, the product with the
     float32 mel bank, log10(max(., 1e-10)), the max - 8 clamp of the frame (norm_mel_slice: the maximum is the frame's), (v + 4) / 4.
-    window / bank (f64, rounded here): a perturbed table in place of the oracle's, for the CPU test of the gates."""
+    window / bank (f64, rounded here): a perturbed table in place of the oracle's, for the CPU test of the gates.  dtype: the type
+    everything runs in (np.float64: the unrounded evaluation of tests/test_f64_statistics.py); energies: -> (out, the mel energies)"""
     from oracle import oracle as O
-    f32 = np.float32
+    f32 = np.dtype(dtype).type
     x = np.ascontiguousarray(x, f32)
     nf = 0 if x.shape[0] < n_fft else (x.shape[0] - n_fft) // hop + 1
     if nf == 0:
-        return np.zeros((0, n_mels), f32)
+        return (np.zeros((0, n_mels), f32),) * 2 if energies else np.zeros((0, n_mels), f32)
     w = np.asarray(O.hann_window(n_fft) if window is None else window).astype(f32)
     fb = np.asarray(O.mel_filterbank(sr, n_fft, n_mels) if bank is None else bank).astype(f32)
     frames = np.lib.stride_tricks.sliding_window_view(x, n_fft)[::hop][:nf] * w
     assert frames.dtype == f32
     z = scipy.fft.rfft(frames, axis=1)
-    assert z.dtype == np.complex64
+    assert z.dtype == (np.complex64 if f32 is np.float32 else np.complex128)
     p = z.real * z.real + z.imag * z.imag
-    v = np.log10(np.maximum(p @ fb.T, f32(1e-10)))
+    e = p @ fb.T
+    v = np.log10(np.maximum(e, f32(1e-10)))
     v = np.maximum(v, v.max(axis=1, keepdims=True) - f32(8.0))
     out = (v + f32(4.0)) / f32(4.0)
     assert out.dtype == f32 and out.shape == (nf, n_mels)
-    return out
+    return (out, e) if energies else out
 
 
 # ---- 2. the statistic ---------------------------------------------------------------------------------------------------------------
@@ -94,10 +96,11 @@ class Stats(NamedTuple):
     share: float    # of the values left out of the means (Whisper: at or within 1e-3 of the frame's clamp)
 
 
-def err_stats(got, want, fpu, clamp=True):
+def err_stats(got, want, fpu, clamp=True, bands=None):
     """got / want: per clip [frames, mels] (want: the f64 oracle); e = got - want in float64 over every frame of every clip; the slot of a
     frame is its index in the clip mod fpu.  clamp: a Whisper output -- the values the frame's max - 8 clamp made (in units of the output:
-    want <= the frame's maximum - 2) or nearly made (within 1e-3) are left out of the means."""
+    want <= the frame's maximum - 2) or nearly made (within 1e-3) are left out of the means.  bands: a list that receives the signed
+    mean of e per band (Stats.band is the largest of them in magnitude)."""
     pairs = [(np.asarray(g), np.asarray(w)) for g, w in zip(got, want)]
     for g, w in pairs:
         assert g.shape == w.shape and g.ndim == 2, (g.shape, w.shape)
@@ -110,6 +113,8 @@ def err_stats(got, want, fpu, clamp=True):
     assert n_b.min() >= 2, "a band without values outside the clamp"
     mean_b = np.where(keep, e, 0.0).sum(axis=0) / n_b
     var_b = np.where(keep, (e - mean_b) ** 2, 0.0).sum(axis=0) / (n_b - 1)
+    if bands is not None:
+        bands.append(mean_b)
     slots = [float(np.abs(e[slot == s][keep[slot == s]].mean())) for s in range(fpu) if keep[slot == s].any()]
     return Stats(float(np.abs(e).max()), float(np.abs(e[keep]).mean()), float(np.abs(mean_b).max()), max(slots),
                  float(np.sqrt(var_b / n_b).max()), float(e[keep].mean()), int(e.shape[0]), float(1.0 - keep.mean()))
@@ -127,12 +132,12 @@ def gate_failures(dev, yard, max_tol, margin=MARGIN, must_see=None, bias_margin=
     return [name for name, ok in checks if not ok]
 
 
-def report(rid, dev, yard):
+def report(rid, dev, yard, tag="F32-STATS", tail=""):
     floor_b, floor_s = max(yard.band, 3.0 * yard.se), max(yard.slot, 3.0 * yard.se)
     ratio = max(dev.mean / yard.mean, dev.band / floor_b, dev.slot / floor_s)
-    print(f"\nF32-STATS {rid} frames={dev.frames} max={dev.max:.2e} mean={dev.mean:.2e} bias={dev.band:.2e} slot={dev.slot:.2e} "
+    print(f"\n{tag} {rid} frames={dev.frames} max={dev.max:.2e} mean={dev.mean:.2e} bias={dev.band:.2e} slot={dev.slot:.2e} "
           f"se={dev.se:.1e} off={dev.off:+.2e} | yardstick max={yard.max:.2e} mean={yard.mean:.2e} bias={yard.band:.2e} slot={yard.slot:.2e} se={yard.se:.1e} off={yard.off:+.2e} | "
-          f"mean x{dev.mean / yard.mean:.2f} bias x{dev.band / floor_b:.2f} slot x{dev.slot / floor_s:.2f} ratio={ratio:.2f}")
+          f"mean x{dev.mean / yard.mean:.2f} bias x{dev.band / floor_b:.2f} slot x{dev.slot / floor_s:.2f} ratio={ratio:.2f}{tail}")
 
 
 def check(rid, dev, yard, max_tol, must_see=None, bias_margin=None):
