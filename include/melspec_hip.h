@@ -174,8 +174,58 @@ int melspec_stft_host(melspec_ctx *ctx, const float *samples, size_t n_samples, 
 int melspec_mel_from_stft_device(melspec_ctx *ctx, const void *d_spec, int dtype, int full, uint64_t n_frames, float *d_out, void *stream);
 int melspec_mel_from_stft_host(melspec_ctx *ctx, const void *spec, int dtype, int full, size_t n_frames, float *out, size_t out_capacity_floats);
 
+/* ---- Whisper features as the encoders were trained on them: centred STFT, clip-wide clamp ------------------------------------
+ * melspec_compute_* is the reference's streaming-friendly variant (un-centred frames, each clamped against its OWN maximum).
+ * openai-whisper's log_mel_spectrogram, Hugging Face's WhisperFeatureExtractor and whisper.cpp compute something else, and these
+ * calls compute that.  For a clip x of n samples and the call's pad_to (0: the clip as it is; 480000: Whisper's 30 s; any value
+ * >= 400 is legal, 1..399 is MELSPEC_ERR_INVALID_ARG):
+ *   1. s = x when pad_to == 0, else x[:pad_to] followed by zeros up to pad_to samples; P = len(s).  P < 400: no frames, and the
+ *      clip's maximum (split calls) is -10.
+ *   2. T = P / 160 frames (integer division): the centred STFT's last frame is dropped -- 3000 frames for 30 s.
+ *   3. frame t = r[160 t .. 160 t + 400) of r = reflect_pad(s, 200) (numpy.pad(mode = "reflect"), torch.stft(center = True)).
+ *   4. raw[t][m] = log10(max(E, 1e-10)): periodic Hann, 400-point DFT, |X|^2, the context's Slaney bank -- what the context does.
+ *   5. g = the maximum of raw over the WHOLE clip.
+ *   6. out[t][m] = (max(raw[t][m], g - 8) + 4) / 4.
+ * This is WhisperFeatureExtractor (pad / trim first, then the centred STFT).  openai-whisper pads the waveform by 30 s, transforms and
+ * trims the frames afterwards: it differs in frame T - 1 only, and only when n > pad_to - 200 (that frame then sees samples past pad_to
+ * instead of their reflection).
+ *
+ * Contexts: melspec_create(.., 400, 160, 16000.0, 80 | 128) -- the set of melspec_supports_io; every other context gets
+ * MELSPEC_ERR_UNSUPPORTED and its output is untouched (melspec_whisper_supports says which).  f32 PCM in, f32 out.
+ * Precision (melspec_set_precision): F64 runs the f64 six-frame kernel (80 and 128 mels); F32 the f32 six-frame run kernel at 80 mels and
+ * the f64 kernel at 128; AUTO runs the f64 kernel -- the guard, the vote and the in-kernel recompute are calibrated for, and store
+ * through, the per-frame clamp, so AUTO's promise (within 1e-4 of the f64 evaluation on every input) is kept by computing in f64 here.
+ * The frames that reflect or straddle the end of the samples (a handful per clip) are computed in f64 whatever the mode.
+ * melspec_whisper_kernel_name names the kernel of the current mode.
+ * NOT covered, left for later: int16 PCM in, f16 / bf16 out; the device-resident clip table (_desc); the sharded object; the stream bank.
+ *
+ * The device calls are stream-ordered and asynchronous (stream NULL: the context's), they do not synchronise with the host and allocate
+ * nothing of the caller's; the scratch of the normalised calls (raw rows, one maximum word per clip) is the context's grow-only scratch
+ * (melspec_release_scratch gives it back).
+ * Normalised output: per clip [T][n_mels] (mel_major == 0) or [n_mels][T] (mel_major != 0: the layout the encoders take) at
+ * d_out + h_out_offsets[i] floats (NULL: packed in clip order; uniform: always packed).  With pad_to != 0 every clip has the same T.
+ * Split output: d_rows [T][n_mels] per clip = the raw values of step 4 (f32; at d_rows + h_rows_offsets[i], NULL: packed),
+ * d_clip_max[n_clips] = g.  Nothing is clamped and no second pass runs: the consumer folds step 6 into its first read. */
+int melspec_whisper_supports(const melspec_ctx *ctx);
+size_t melspec_whisper_num_frames(const melspec_ctx *ctx, size_t n_samples, size_t pad_to);   /* 0 on a context the calls do not cover */
+const char *melspec_whisper_kernel_name(const melspec_ctx *ctx);
+int melspec_whisper_compute_uniform_device(melspec_ctx *ctx, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips,
+                                           uint64_t pad_to, float *d_out, int mel_major, void *stream);
+int melspec_whisper_compute_ragged_device(melspec_ctx *ctx, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                          uint32_t n_clips, uint64_t pad_to, float *d_out, const uint64_t *h_out_offsets, int mel_major,
+                                          void *stream);
+int melspec_whisper_compute_uniform_device_split(melspec_ctx *ctx, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len,
+                                                 uint32_t n_clips, uint64_t pad_to, float *d_rows, float *d_clip_max, void *stream);
+int melspec_whisper_compute_ragged_device_split(melspec_ctx *ctx, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                                uint32_t n_clips, uint64_t pad_to, float *d_rows, const uint64_t *h_rows_offsets,
+                                                float *d_clip_max, void *stream);
+/* One clip from host memory: upload, the device call, download; synchronous.  out_capacity_floats >= T * n_mels, *n_frames = T. */
+int melspec_whisper_compute_host(melspec_ctx *ctx, const float *samples, size_t n_samples, size_t pad_to, float *out,
+                                 size_t out_capacity_floats, int mel_major, size_t *n_frames);
+
 /* The context's scratch only grows (pipeline buffers sized by the largest chunk, the precision guard's queue of 4 B per frame of
- * the largest batch, ragged plans): this waits for the context's queued work and gives all of it back.  The next call re-allocates. */
+ * the largest batch, ragged plans, the raw rows of the melspec_whisper_* calls): this waits for the context's queued work and gives all
+ * of it back.  The next call re-allocates. */
 int melspec_release_scratch(melspec_ctx *ctx);
 /* Pinned host memory (cudaMallocHost of src/cuda.rs:185-199): buffers from here skip the staging copy of the host calls. */
 int melspec_host_alloc(void **p, size_t bytes);

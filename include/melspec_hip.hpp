@@ -145,6 +145,40 @@ public:
         for (std::size_t f = 0; f < frames.size(); ++f) res[f].assign(out.begin() + f * nm, out.begin() + (f + 1) * nm);
         return res;
     }
+    // ---- Whisper features as the encoders were trained on them (melspec_whisper_*: centred STFT, pad / trim to pad_to, clip-wide clamp) ----
+    bool supports_whisper() const { return melspec_whisper_supports(ctx_) != 0; }
+    std::size_t whisper_num_frames(std::size_t n_samples, std::size_t pad_to = 480000) const { return melspec_whisper_num_frames(ctx_, n_samples, pad_to); }
+    const char *whisper_kernel_name() const { return melspec_whisper_kernel_name(ctx_); }
+    // one host clip -> [n_mels][T] (mel_major: what the encoders take) or [T][n_mels], flat
+    std::vector<float> whisper_features(const std::vector<float> &samples, std::size_t pad_to = 480000, bool mel_major = true, std::size_t *n_frames = nullptr) {
+        const std::size_t T = whisper_num_frames(samples.size(), pad_to);
+        std::vector<float> out(T * static_cast<std::size_t>(melspec_n_mels(ctx_)) + 1);
+        std::size_t nf = 0;
+        detail::check(melspec_whisper_compute_host(ctx_, samples.data(), samples.size(), pad_to, out.data(), out.size(), mel_major ? 1 : 0, &nf), false);
+        out.resize(nf * static_cast<std::size_t>(melspec_n_mels(ctx_)));
+        if (n_frames) *n_frames = nf;
+        return out;
+    }
+    // device pointers in and out, asynchronous on `stream` (nullptr: the context's)
+    void whisper_uniform_device(const float *d_pcm, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, std::uint64_t pad_to, float *d_out,
+                                bool mel_major = true, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_uniform_device(ctx_, d_pcm, clip_stride, clip_len, n_clips, pad_to, d_out, mel_major ? 1 : 0, stream), false);
+    }
+    void whisper_ragged_device(const float *d_pcm, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths, std::uint64_t pad_to,
+                               float *d_out, const std::uint64_t *out_offsets = nullptr, bool mel_major = true, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device(ctx_, d_pcm, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), pad_to, d_out,
+                                                            out_offsets, mel_major ? 1 : 0, stream), false);
+    }
+    // split output: raw log10 rows [T][n_mels] per clip + the clips' maxima; the consumer folds (max(x, g - 8) + 4) / 4 into its first read
+    void whisper_uniform_device_split(const float *d_pcm, std::uint64_t clip_stride, std::uint64_t clip_len, std::uint32_t n_clips, std::uint64_t pad_to,
+                                      float *d_rows, float *d_clip_max, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_uniform_device_split(ctx_, d_pcm, clip_stride, clip_len, n_clips, pad_to, d_rows, d_clip_max, stream), false);
+    }
+    void whisper_ragged_device_split(const float *d_pcm, const std::vector<std::uint64_t> &offsets, const std::vector<std::uint64_t> &lengths, std::uint64_t pad_to,
+                                     float *d_rows, float *d_clip_max, const std::uint64_t *rows_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device_split(ctx_, d_pcm, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), pad_to,
+                                                                  d_rows, rows_offsets, d_clip_max, stream), false);
+    }
     melspec_ctx *raw() { return ctx_; }
 
 private:

@@ -83,6 +83,14 @@ SIGNATURES = {
     "melspec_compute_batch_host": (C.c_int, [_vp, _f32p, _u64p, _u64p, C.c_uint32, _f32p, _u64p, C.c_size_t, _u64p]),
     "melspec_mel_from_stft_device": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_uint64, _vp, _vp]),
     "melspec_mel_from_stft_host": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_size_t, _f32p, C.c_size_t]),
+    "melspec_whisper_supports": (C.c_int, [_vp]),
+    "melspec_whisper_num_frames": (C.c_size_t, [_vp, C.c_size_t, C.c_size_t]),
+    "melspec_whisper_kernel_name": (C.c_char_p, [_vp]),
+    "melspec_whisper_compute_uniform_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp]),
+    "melspec_whisper_compute_ragged_device": (C.c_int, [_vp, _vp, _u64p, _u64p, C.c_uint32, C.c_uint64, _vp, _u64p, C.c_int, _vp]),
+    "melspec_whisper_compute_uniform_device_split": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _vp, _vp, _vp]),
+    "melspec_whisper_compute_ragged_device_split": (C.c_int, [_vp, _vp, _u64p, _u64p, C.c_uint32, C.c_uint64, _vp, _u64p, _vp, _vp]),
+    "melspec_whisper_compute_host": (C.c_int, [_vp, _f32p, C.c_size_t, C.c_size_t, _f32p, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
     "melspec_release_scratch": (C.c_int, [_vp]),
     "melspec_fbank_release_scratch": (C.c_int, [_vp]),
     "melspec_blm_release_scratch": (C.c_int, [_vp]),

@@ -221,6 +221,7 @@ void melspec_destroy(melspec_ctx *c) {
     c->fix.release();
     c->dplan.release();
     c->pipe.release();
+    c->wc.release(); c->wc_h2d.release(); c->wc_d2h.release();
     c->st_start.release(); c->st_len.release(); c->st_off.release(); c->st_w.release(); c->st_jw.release(); c->st_job.release();
     delete c;
 }
@@ -645,6 +646,8 @@ int melspec_release_scratch(melspec_ctx *c) {
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->pipe.release();
     c->ragged.release();
+    if (int rc = c->wc.release_after(c->stream)) return rc;
+    c->wc_h2d.release(); c->wc_d2h.release();
     c->fix.list.release();
     c->fix.used = false;
     return MELSPEC_OK;

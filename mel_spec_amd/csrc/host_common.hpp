@@ -12,6 +12,8 @@
 //   stat_bank.hpp   StatBank<B>: the Kaldi fbank's and the NeMo frontend's stream bank, written once over BankCore; their traits and the ABI's forwards are in fbank512.hip
 //   stat_bank_tail.hpp  the table those banks send behind a push's entries (no HIP: host-testable)
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
+//   whisper_centered.hip  the centred Whisper features (melspec_whisper_*): raw rows + clip maxima from the six-frame kernels, the finalise pass
+//   whisper_centered_plan.hpp  their frame classes, tables and argument checks (no HIP: host-testable)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -484,6 +486,22 @@ struct FixState {
 constexpr unsigned long long kAutoMinFrames = 256;
 constexpr unsigned long long kStatFromGated = 1ull << 39;
 
+// Scratch of the centred Whisper features (whisper_centered.hip), grow-only, used in stream order: the raw rows and the clip-maximum words of
+// the normalised calls, the gathered samples of the edge frames, the ring its tables travel through
+struct WcScratch {
+    StreamBuf rows, slots, edge_pcm;
+    RaggedScratch ring;
+    void release() { rows.release(); slots.release(); edge_pcm.release(); ring.release(); }
+    // `synced`: a stream the caller has just synchronised
+    int release_after(hipStream_t synced) {
+        int rc = rows.release_after(synced);
+        if (!rc) rc = slots.release_after(synced);
+        if (!rc) rc = edge_pcm.release_after(synced);
+        ring.release();
+        return rc;
+    }
+};
+
 struct melspec_ctx {
     DeviceInfo dev;
     int fft_size = 0, hop_size = 0, n_mels = 0;
@@ -541,6 +559,8 @@ struct melspec_ctx {
     RaggedScratch ragged;
     DevicePlan dplan;
     HostPipe pipe;          // chunked H2D / kernels / D2H pipeline of the host entry points (host_pipe.hpp)
+    WcScratch wc;           // melspec_whisper_*
+    DevBuf wc_h2d, wc_d2h;  // melspec_whisper_compute_host's staging
 };
 
 namespace melspec {

@@ -1,6 +1,8 @@
 // whisper400_six64_body.inc -- the body of whisper400_six64_kernel, included once per kernel that shares it (whisper400_kernels.hpp; the
 // *_io_* kernels of whisper400_io_kernels.hpp) with MS_SIX64_IN / MS_SIX64_OUT = its sample and row types.  Text, not a function, like
 // whisper400_six_runs_body.inc: the existing kernel must compile to the instructions it has.
+// MS_SIX64_RAW (whisper_centered_kernels.hpp alone): the raw rows and the clip maximum of the centred Whisper features, as in
+// whisper400_six_runs_body.inc.
     constexpr int WAVES = kSix64Waves;
     if (p.gate != nullptr && *p.gate != p.gate_value) return;        // the batch was light: the f32 launch has finished it
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsw[];
@@ -24,6 +26,9 @@
     const int *starts = reinterpret_cast<const int *>(fblob + SixBlob::kMelStart) + j;
     const bool stats = p.stat.acc != nullptr;
     unsigned flagged = 0;
+#ifdef MS_SIX64_RAW
+    int rmax = 0;
+#endif
 
     ClipRunT<MS_SIX64_IN, MS_SIX64_OUT> cr;
     if (!cr.init(p.b, (uint64_t)xcd_logical_block() * WAVES + wave, (uint64_t)gridDim.x * WAVES)) {
@@ -31,6 +36,9 @@
         return;
     }
     for (; cr.unit < cr.end; ++cr.unit) {
+#ifdef MS_SIX64_RAW
+        if (cr.unit >= cr.c_end) { six_raw_flush(wc_slots, wc_slot_map, cr.clip, lane, rmax); rmax = 0; }
+#endif
         cr.enter(p.b);
         const uint64_t f0 = (cr.unit - cr.c_start) * kSixFrames;
         const uint64_t left = cr.c_frames - f0;
@@ -60,8 +68,16 @@
         }
         __builtin_amdgcn_wave_barrier();
         MS_SIX64_OUT *out_tile = cr.c_out + f0 * (uint64_t)n_mels;
+#ifdef MS_SIX64_RAW
+        const bool flag = false;
+        six_raw_store<NSLOTS>(fl, j, act, n_mels, vals, out_tile, rmax);
+#else
         const bool flag = six_phase4<NSLOTS, false, true>(fl, j, act, act, n_mels, slice, vals, out_tile, 0);
+#endif
         __builtin_amdgcn_wave_barrier();
         if (stats) flagged += static_cast<unsigned>(__builtin_popcount(frame_mask<kSixLanes, kSixFrames>(__builtin_amdgcn_ballot_w64(flag))));
     }
+#ifdef MS_SIX64_RAW
+    six_raw_flush(wc_slots, wc_slot_map, cr.clip, lane, rmax);
+#endif
     guard_wave_done(p.stat, wg_done, WAVES, lane, flagged);

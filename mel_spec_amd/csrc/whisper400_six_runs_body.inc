@@ -2,6 +2,9 @@
 // MS_SIX_RUNS_WAVES = the waves of its workgroup and MS_SIX_RUNS_IN / MS_SIX_RUNS_OUT = its sample and row types (float; the *_io_* kernels of
 // whisper400_io_kernels.hpp: their template parameters).  Text, not a function: the sixteen-wave kernel of the bench workload must compile to the
 // instructions it has (a shared __device__ body taking the parameters by reference changed its schedule: 5552 -> 5571 instructions).
+// MS_SIX_RUNS_RAW (defined by whisper_centered_kernels.hpp alone; preprocessor lines leave no token in the other kernels): no guard, no frame
+// maximum and no clamp -- the raw log10 rows and the clip maximum of the centred Whisper features (six_raw_store / six_raw_flush there; the
+// kernel declares wc_slots / wc_slot_map in front of this text).
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *blob = lds;
     const int tid = threadIdx.x;
@@ -19,7 +22,12 @@
     SixLayout::row_offsets(j, uoff, voff);
     const int n_mels = Lens::kStatic ? Lens::kMels : p.n_mels;
     const int *starts = reinterpret_cast<const int *>(blob + SixBlob::kMelStart) + j;
+#ifdef MS_SIX_RUNS_RAW
+    constexpr bool guard = false;
+    int rmax = 0;                    // this lane's running maximum of the biased values of the clip the run is in
+#else
     const bool guard = p.fix.tab != nullptr;
+#endif
 
 #ifdef MELSPEC_LAB_STAMPS
     if (guard && tid == 0) p.fix.list[p.b.n_units + 4096 + (uint64_t)gridDim.x * MS_SIX_RUNS_WAVES + blockIdx.x] = __builtin_amdgcn_s_memrealtime();
@@ -40,6 +48,9 @@
     bool may_leave = true;
     auto unit = [&](auto pre) __attribute__((always_inline)) -> uint64_t {
         constexpr bool kPre = decltype(pre)::value;
+#ifdef MS_SIX_RUNS_RAW
+        if (cr.unit >= cr.c_end) { six_raw_flush(wc_slots, wc_slot_map, cr.clip, lane, rmax); rmax = 0; }      // the run leaves a clip (ClipRunT::enter's condition)
+#endif
         cr.enter(p.b);
         const uint64_t f0 = (cr.unit - cr.c_start) * kSixFrames;
         const uint64_t left = cr.c_frames - f0;
@@ -74,7 +85,12 @@
         }
         __builtin_amdgcn_wave_barrier();
         MS_SIX_RUNS_OUT *out_tile = cr.c_out + f0 * (uint64_t)n_mels;
+#ifdef MS_SIX_RUNS_RAW
+        const bool flag = false;
+        six_raw_store<NSLOTS>(fl, j, act, n_mels, vals, out_tile, rmax);
+#else
         const bool flag = six_phase4<NSLOTS, false, true>(fl, j, act, act, n_mels, slice, vals, out_tile, 0);
+#endif
         __builtin_amdgcn_wave_barrier();
         uint64_t any = 0;
         if (guard) {
@@ -109,6 +125,9 @@
         }
     }
     for (; cr.unit < cr.end; ++cr.unit) unit(std::false_type{});
+#ifdef MS_SIX_RUNS_RAW
+    six_raw_flush(wc_slots, wc_slot_map, cr.clip, lane, rmax);
+#endif
     // the units whose frames tripped the precision guard, again, in f64
     unsigned redone = 0;
     FixTw tw;

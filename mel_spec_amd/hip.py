@@ -921,6 +921,91 @@ def blm_compute_ragged_device_desc(fe: BatchLogMelSpectrogram, d_pcm: int, d_off
                                                         C.c_void_p(d_rejected) if d_rejected else None, C.c_void_p(stream)))
 
 
+# ---- Whisper features as the encoders were trained on them (melspec_whisper_*: centred STFT, pad / trim, clip-wide clamp) ----
+# Module-level functions on a HipMelSpectrogram `mel` (the frontend classes' attributes are a pinned set, tests/test_python_surface.py).
+def supports_whisper(mel: HipMelSpectrogram) -> bool:
+    return bool(lib().melspec_whisper_supports(mel._h))
+
+
+def whisper_kernel_name(mel: HipMelSpectrogram) -> str:
+    return lib().melspec_whisper_kernel_name(mel._h).decode()
+
+
+def whisper_num_frames(mel: HipMelSpectrogram, n_samples: int, pad_to: int = 480000) -> int:
+    return int(lib().melspec_whisper_num_frames(mel._h, int(n_samples), int(pad_to)))
+
+
+def whisper_uniform_device(mel: HipMelSpectrogram, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, pad_to: int = 480000,
+                           mel_major: bool = True, stream: int = 0) -> None:
+    """Device pointers in and out, asynchronous on `stream`: per clip [n_mels][T] (mel_major) or [T][n_mels], packed."""
+    _check(lib().melspec_whisper_compute_uniform_device(mel._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips, pad_to, C.c_void_p(d_out),
+                                                        1 if mel_major else 0, C.c_void_p(stream)))
+
+
+def whisper_ragged_device(mel: HipMelSpectrogram, d_pcm: int, offsets, lengths, d_out: int, pad_to: int = 480000, out_offsets=None, mel_major: bool = True,
+                          stream: int = 0) -> None:
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+    _check(lib().melspec_whisper_compute_ragged_device(mel._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0], pad_to, C.c_void_p(d_out), p_out,
+                                                       1 if mel_major else 0, C.c_void_p(stream)))
+
+
+def whisper_uniform_device_split(mel: HipMelSpectrogram, d_pcm: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int, d_clip_max: int,
+                                 pad_to: int = 480000, stream: int = 0) -> None:
+    """Raw log10 rows [T][n_mels] per clip and the clips' maxima; nothing is clamped (the consumer folds (max(x, g - 8) + 4) / 4 in)."""
+    _check(lib().melspec_whisper_compute_uniform_device_split(mel._h, C.c_void_p(d_pcm), clip_stride, clip_len, n_clips, pad_to, C.c_void_p(d_rows),
+                                                              C.c_void_p(d_clip_max), C.c_void_p(stream)))
+
+
+def whisper_ragged_device_split(mel: HipMelSpectrogram, d_pcm: int, offsets, lengths, d_rows: int, d_clip_max: int, pad_to: int = 480000, rows_offsets=None,
+                                stream: int = 0) -> None:
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_whisper_compute_ragged_device_split(mel._h, C.c_void_p(d_pcm), p_off, p_len, tabs[0].shape[0], pad_to, C.c_void_p(d_rows), p_out,
+                                                             C.c_void_p(d_clip_max), C.c_void_p(stream)))
+
+
+def whisper_features(mel: HipMelSpectrogram, samples, pad_to: int = 480000, mel_major: bool = True) -> np.ndarray:
+    """One host clip -> [n_mels, T] (mel_major: what the encoders take) or [T, n_mels]; pad_to = 0: the clip as it is."""
+    x = _f32(samples).reshape(-1)
+    T = whisper_num_frames(mel, x.shape[0], pad_to)
+    out = np.empty((mel.n_mels, T) if mel_major else (T, mel.n_mels), np.float32)
+    nf = C.c_size_t(0)
+    _check(lib().melspec_whisper_compute_host(mel._h, _fp(x) if x.size else None, x.shape[0], pad_to, _fp(out) if out.size else None, out.size,
+                                              1 if mel_major else 0, C.byref(nf)))
+    assert nf.value == T
+    return out
+
+
+def _whisper_batch(mel: HipMelSpectrogram, clips, pad_to: int, mel_major: bool, split: bool):
+    flat, offs, lens = _flatten(clips)
+    n = len(lens)
+    Ts = [whisper_num_frames(mel, int(l), pad_to) for l in lens]
+    total = sum(Ts) * mel.n_mels
+    d_in, d_out, d_max = DeviceBuffer(flat.nbytes), DeviceBuffer(max(total, 1) * 4), DeviceBuffer(max(n, 1) * 4)
+    try:
+        d_in.upload(flat)
+        if split:
+            whisper_ragged_device_split(mel, d_in.ptr, offs, lens, d_out.ptr, d_max.ptr, pad_to)
+        else:
+            whisper_ragged_device(mel, d_in.ptr, offs, lens, d_out.ptr, pad_to, None, mel_major)
+        mel.synchronize()
+        out = d_out.download((total,)) if total else np.zeros(0, np.float32)
+        g = d_max.download((n,)) if split and n else np.zeros(0, np.float32)
+    finally:
+        d_in.free(); d_out.free(); d_max.free()
+    shapes = [(mel.n_mels, T) if (mel_major and not split) else (T, mel.n_mels) for T in Ts]
+    return _split(out, shapes), g
+
+
+def whisper_features_batch(mel: HipMelSpectrogram, clips, pad_to: int = 480000, mel_major: bool = True) -> list:
+    """List of 1-D host clips -> list of [n_mels, T_i] (or [T_i, n_mels]) arrays, one ragged device call."""
+    return _whisper_batch(mel, clips, pad_to, mel_major, False)[0]
+
+
+def whisper_split(mel: HipMelSpectrogram, clips, pad_to: int = 480000):
+    """List of 1-D host clips -> (list of raw log10 rows [T_i, n_mels], the clips' maxima [n_clips])."""
+    return _whisper_batch(mel, clips, pad_to, False, True)
+
+
 class SparseMelFilterbank:
     """SparseMelFilterbank (src/mel.rs:40-168) + log_mel_spectrogram / norm_mel / norm_mel_vec (:436-469) on the GPU (melspec_bank_*)."""
 

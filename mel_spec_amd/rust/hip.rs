@@ -1250,6 +1250,21 @@ unsafe extern "C" {
                                      d_out: *mut f32, h_out_offsets: *const u64, stream: *mut c_void) -> c_int;
     fn melspec_compute_ragged_device_desc(ctx: *mut Ctx, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
                                           d_out: *mut f32, d_out_offsets: *const u64, max_total_frames: u64, stream: *mut c_void) -> c_int;
+    // Whisper features as the encoders were trained on them: centred STFT, pad / trim, clip-wide clamp
+    fn melspec_whisper_supports(ctx: *const Ctx) -> c_int;
+    fn melspec_whisper_num_frames(ctx: *const Ctx, n_samples: usize, pad_to: usize) -> usize;
+    fn melspec_whisper_kernel_name(ctx: *const Ctx) -> *const c_char;
+    fn melspec_whisper_compute_uniform_device(ctx: *mut Ctx, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, pad_to: u64,
+                                              d_out: *mut f32, mel_major: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_ragged_device(ctx: *mut Ctx, d_pcm: *const f32, h_offsets: *const u64, h_lengths: *const u64, n_clips: u32,
+                                             pad_to: u64, d_out: *mut f32, h_out_offsets: *const u64, mel_major: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_uniform_device_split(ctx: *mut Ctx, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, pad_to: u64,
+                                                    d_rows: *mut f32, d_clip_max: *mut f32, stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_ragged_device_split(ctx: *mut Ctx, d_pcm: *const f32, h_offsets: *const u64, h_lengths: *const u64, n_clips: u32,
+                                                   pad_to: u64, d_rows: *mut f32, h_rows_offsets: *const u64, d_clip_max: *mut f32,
+                                                   stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_host(ctx: *mut Ctx, samples: *const f32, n_samples: usize, pad_to: usize, out: *mut f32, out_capacity_floats: usize,
+                                    mel_major: c_int, n_frames: *mut usize) -> c_int;
     // int16 PCM in / f16, bf16 rows out
     fn melspec_supports_io(ctx: *const Ctx, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
     fn melspec_compute_uniform_device_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
@@ -1403,6 +1418,73 @@ impl HipMelSpectrogram {
                                           std::ptr::null(), std::ptr::null_mut())
         })?;
         Ok(frames)
+    }
+
+    /// Can this context compute the Whisper features the encoders were trained on (`whisper_features`)?  n_fft 400, hop 160, 16 kHz, 80 or 128 mels.
+    pub fn supports_whisper(&self) -> bool {
+        unsafe { melspec_whisper_supports(self.ctx) != 0 }
+    }
+
+    /// Frames of a clip of `n_samples` under `pad_to` (0: the clip as it is; 480000: Whisper's 30 s -> 3000).
+    pub fn whisper_num_frames(&self, n_samples: usize, pad_to: usize) -> usize {
+        unsafe { melspec_whisper_num_frames(self.ctx, n_samples, pad_to) }
+    }
+
+    /// One host clip -> Whisper's features: the clip padded / trimmed to `pad_to` samples, centred STFT, clamp against the maximum of the
+    /// whole clip, `(x + 4) / 4`; flat `[n_mels][T]` (`mel_major`) or `[T][n_mels]`.  Returns (values, T).
+    pub fn whisper_features(&mut self, samples: &[f32], pad_to: usize, mel_major: bool) -> Result<(Vec<f32>, usize), HipError> {
+        let frames = self.whisper_num_frames(samples.len(), pad_to);
+        let mut out = vec![0f32; frames * self.n_mels + 1];
+        let mut nf = 0usize;
+        check(unsafe {
+            melspec_whisper_compute_host(self.ctx, samples.as_ptr(), samples.len(), pad_to, out.as_mut_ptr(), out.len(), mel_major as c_int, &mut nf)
+        })?;
+        out.truncate(nf * self.n_mels);
+        Ok((out, nf))
+    }
+
+    /// `whisper_features` on equal-length clips in device memory, packed output; asynchronous until `synchronize`.
+    ///
+    /// # Safety
+    /// `d_pcm` must be valid for `n_clips * clip_stride` samples and `d_out` for `n_clips * T * n_mels` floats.
+    pub unsafe fn whisper_uniform_device(&mut self, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, pad_to: u64, d_out: *mut f32,
+                                         mel_major: bool, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_uniform_device(self.ctx, d_pcm, clip_stride, clip_len, n_clips, pad_to, d_out, mel_major as c_int, stream))
+    }
+
+    /// ... on clips of any lengths, packed in clip order.
+    ///
+    /// # Safety
+    /// Every clip must lie inside the buffer behind `d_pcm`, and `d_out` must hold the features of all clips.
+    pub unsafe fn whisper_ragged_device(&mut self, d_pcm: *const f32, offsets: &[u64], lengths: &[u64], pad_to: u64, d_out: *mut f32, mel_major: bool,
+                                        stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        check(melspec_whisper_compute_ragged_device(self.ctx, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, pad_to, d_out,
+                                                    std::ptr::null(), mel_major as c_int, stream))
+    }
+
+    /// Split output: the raw `log10` rows `[T][n_mels]` of every clip and the clips' maxima; nothing is clamped, the consumer folds
+    /// `(max(x, g - 8) + 4) / 4` into its first read.
+    ///
+    /// # Safety
+    /// As `whisper_uniform_device`; `d_clip_max` must hold `n_clips` floats.
+    pub unsafe fn whisper_uniform_device_split(&mut self, d_pcm: *const f32, clip_stride: u64, clip_len: u64, n_clips: u32, pad_to: u64, d_rows: *mut f32,
+                                               d_clip_max: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_uniform_device_split(self.ctx, d_pcm, clip_stride, clip_len, n_clips, pad_to, d_rows, d_clip_max, stream))
+    }
+
+    /// # Safety
+    /// As `whisper_ragged_device`; `d_clip_max` must hold one float per clip.
+    pub unsafe fn whisper_ragged_device_split(&mut self, d_pcm: *const f32, offsets: &[u64], lengths: &[u64], pad_to: u64, d_rows: *mut f32,
+                                              d_clip_max: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        assert_eq!(offsets.len(), lengths.len());
+        check(melspec_whisper_compute_ragged_device_split(self.ctx, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, pad_to, d_rows,
+                                                          std::ptr::null(), d_clip_max, stream))
+    }
+
+    /// The kernel the Whisper features run on in the current precision mode.
+    pub fn whisper_kernel_name(&self) -> String {
+        unsafe { std::ffi::CStr::from_ptr(melspec_whisper_kernel_name(self.ctx)).to_string_lossy().into_owned() }
     }
 
     /// Does this context take `pcm_dtype` samples (`PCM_F32`, `PCM_S16`) and write `out_dtype` rows (`OUT_F32`, `OUT_F16`, `OUT_BF16`)?

@@ -66,7 +66,8 @@ NOTES = {
 asm = {}
 with tempfile.TemporaryDirectory() as tmp:
     procs = {}
-    for unit in sorted({u for u, _, _ in LEGS.values()} | {"melspec_runs.hip", "whisper400.hip", "fbank512.hip", "melspec_io_runs.hip", "melspec_io64.hip", "fbank512_io.hip", "fbank512_kaldi_io.hip", "fbank512_stats.hip", "fbank512_stats_ragged.hip"}):
+    for unit in sorted({u for u, _, _ in LEGS.values()} | {"melspec_runs.hip", "whisper400.hip", "fbank512.hip", "melspec_io_runs.hip", "melspec_io64.hip", "fbank512_io.hip", "fbank512_kaldi_io.hip", "fbank512_stats.hip", "fbank512_stats_ragged.hip",
+                                                              "whisper_centered.hip", "whisper_centered_runs.hip"}):
         out = os.path.join(tmp, unit + ".s")
         procs[unit] = (out, subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-S", "--cuda-device-only", "-o", out,
                                              os.path.join(B.CSRC, unit)] + B.UNIT_FLAGS.get(unit, []), stderr=subprocess.DEVNULL))
