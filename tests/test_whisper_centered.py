@@ -4,7 +4,11 @@ on the GPU against tests/whisper_centered_ref.py, compared whole: every value of
 Gates, taken from tests/test_whole_batch.py: F64_TOL = 2e-6 on normalised values in AUTO and F64 (both run the f64 kernel here), F32_TOL =
 6e-4 in F32 -- a clip-wide clamp is never below the per-frame clamp, so for every band the new error is at most the old one plus the error
 of g.  Raw rows of the split calls are compared directly in F64 only, at 4 x F64_TOL (the raw scale is four times the normalised one); in
-F32 after folding step 6 in numpy.  The fold of the split output against the normalised call: 5e-7, two f32 ulps at magnitude 2."""
+F32 after folding step 6 in numpy.  The fold of the split output against the normalised call: 5e-7, two f32 ulps at magnitude 2.
+
+Every check_batch also asserts that a clip's returned maximum is, bit for bit, the float32 maximum of its returned raw rows (both are
+`biased - 16.0f` of the same bits).  run_norm / run_split take caller-chosen output offsets and a shift of the output pointer, and check
+that every float outside the clips' outputs keeps its sentinel.  The statistics of the raw rows: tests/test_whisper_centered_stats.py."""
 import ctypes as C
 
 import numpy as np
@@ -61,44 +65,59 @@ def upload(clips):
     return d, offs, lens
 
 
-def run_norm(mel, clips, pad_to, mel_major, stream=0):
-    """the ragged normalised call -> list of [T_i][n_mels] (mel-major results transposed back)"""
+def _place(Ts, n_mels, offsets):
+    """where each clip's T_i x n_mels floats start (None: packed in clip order) and the floats the whole output spans"""
+    sizes = [T * n_mels for T in Ts]
+    if offsets is None:
+        offsets = [int(v) for v in np.concatenate([[0], np.cumsum(sizes)[:-1]])] if sizes else []
+    offsets = [int(o) for o in offsets]
+    return offsets, sizes, max([o + n for o, n in zip(offsets, sizes)] + [0])
+
+
+def _collect(flat, offsets, sizes, shift):
+    """the clips' floats out of a downloaded output; every float the call had no business with -- the `shift` floats in front of the
+    pointer it was given and the gaps between caller-chosen offsets -- still holds the sentinel"""
+    used = np.zeros(flat.shape[0], bool)
+    for o, n in zip(offsets, sizes):
+        assert not used[shift + o:shift + o + n].any(), "the test's own offsets overlap"
+        used[shift + o:shift + o + n] = True
+    assert np.all(flat[~used] == SENTINEL), "a float outside the clips' outputs was overwritten"
+    return [flat[shift + o:shift + o + n] for o, n in zip(offsets, sizes)]
+
+
+def run_norm(mel, clips, pad_to, mel_major, stream=0, out_offsets=None, shift=0):
+    """the ragged normalised call -> list of [T_i][n_mels] (mel-major results transposed back).  out_offsets: h_out_offsets, in floats;
+    shift: d_out is advanced by that many floats past the fenced buffer's 16-byte aligned start"""
     d, offs, lens = upload(clips)
     Ts = [R.num_frames(int(n), pad_to) for n in lens]
-    out = Fenced(sum(Ts) * mel.n_mels)
+    where, sizes, span = _place(Ts, mel.n_mels, out_offsets)
+    out = Fenced(span + shift)
     try:
-        M.whisper_ragged_device(mel, d.ptr, offs, lens, out.ptr, pad_to, None, mel_major, stream)
+        M.whisper_ragged_device(mel, d.ptr, offs, lens, out.ptr + 4 * shift, pad_to, None if out_offsets is None else where, mel_major, stream)
         mel.synchronize(stream)
-        flat = out.get()
+        parts = _collect(out.get(), where, sizes, shift)
     finally:
         d.free(); out.free()
-    res, cur = [], 0
-    for T in Ts:
-        a = flat[cur:cur + T * mel.n_mels]
-        res.append(a.reshape(mel.n_mels, T).T.copy() if mel_major else a.reshape(T, mel.n_mels).copy())
-        cur += T * mel.n_mels
-    return res
+    return [a.reshape(mel.n_mels, T).T.copy() if mel_major else a.reshape(T, mel.n_mels).copy() for a, T in zip(parts, Ts)]
 
 
-def run_split(mel, clips, pad_to, d_max=None):
-    """the ragged split call -> (list of raw rows [T_i][n_mels], g [n_clips]); d_max: a Fenced to use (and keep) for the maxima"""
+def run_split(mel, clips, pad_to, d_max=None, rows_offsets=None, shift=0):
+    """the ragged split call -> (list of raw rows [T_i][n_mels], g [n_clips]); d_max: a Fenced to use (and keep) for the maxima;
+    rows_offsets: h_rows_offsets, in floats; shift: as in run_norm, for d_rows"""
     d, offs, lens = upload(clips)
     Ts = [R.num_frames(int(n), pad_to) for n in lens]
-    rows = Fenced(sum(Ts) * mel.n_mels)
+    where, sizes, span = _place(Ts, mel.n_mels, rows_offsets)
+    rows = Fenced(span + shift)
     mx = d_max or Fenced(len(clips))
     try:
-        M.whisper_ragged_device_split(mel, d.ptr, offs, lens, rows.ptr, mx.ptr, pad_to)
+        M.whisper_ragged_device_split(mel, d.ptr, offs, lens, rows.ptr + 4 * shift, mx.ptr, pad_to, None if rows_offsets is None else where)
         mel.synchronize()
-        flat, g = rows.get(), mx.get().copy()
+        parts, g = _collect(rows.get(), where, sizes, shift), mx.get().copy()
     finally:
         d.free(); rows.free()
         if d_max is None:
             mx.free()
-    res, cur = [], 0
-    for T in Ts:
-        res.append(flat[cur:cur + T * mel.n_mels].reshape(T, mel.n_mels).copy())
-        cur += T * mel.n_mels
-    return res, g
+    return [a.reshape(T, mel.n_mels).copy() for a, T in zip(parts, Ts)], g
 
 
 _REF = {}
@@ -134,6 +153,8 @@ def check_batch(mel, key, clips, pad_to, tol, raw_direct, what):
         assert np.array_equal(mm[i], fm[i]), f"{what}: clip {i}: mel-major and frame-major bits differ"
         w_n = max(w_n, worst(fm[i], nrm))
         w_g = max(w_g, abs(float(g[i]) - gw))
+        if raw.shape[0]:          # the maximum is `biased - 16.0f` of the bits of one of the stored values: exactly the largest of them
+            assert g[i] == np.float32(rows[i].max()), f"{what}: clip {i}: maximum {g[i]!r}, the largest returned value {rows[i].max()!r}"
         folded = R.fold_f32(rows[i], g[i])
         w_f = max(w_f, worst(folded, fm[i].astype(np.float64)))
         if raw_direct:
@@ -393,3 +414,247 @@ def test_arguments(oracle):
     mel.set_precision("f32")
     assert "six_runs_raw" in M.whisper_kernel_name(mel)
     d.free(); out.free(); mx.free(); mel.close()
+
+
+# ---- the finalise pass's tiles of 64 frames: full and partial last tiles, the 16-byte path on and off, the live / silent boundary in and on a tile ----
+MODES = [(80, None, F64_TOL), (80, "f32", F32_TOL), (128, None, F64_TOL)]          # None: the mode the suite runs in (the f64 kernel)
+MODE_IDS = ["80-f64", "80-f32", "128-f64"]
+TILE_T = [63, 64, 65, 66, 67, 68, 127, 128, 129, 132]
+TILE_PADS = {10240: 64, 10880: 68, 20480: 128}
+TILE_PAD_N = [0, 1000, 10040, 10239, 20000]
+
+
+def same(a, b):
+    return a.shape == b.shape and np.array_equal(a, b)
+
+
+def _shifted(mel, clips, pad_to, fm, rows, g, what):
+    """the same calls with the output pointer one and two floats past its 16-byte aligned start: the same bits, nothing outside them"""
+    for shift in (1, 2):
+        for mel_major in (True, False):
+            got = run_norm(mel, clips, pad_to, mel_major, shift=shift)
+            assert all(same(a, b) for a, b in zip(got, fm)), f"{what}: d_out + {shift} floats, mel_major {mel_major}"
+        r, gg = run_split(mel, clips, pad_to, shift=shift)
+        assert all(same(a, b) for a, b in zip(r, rows)) and np.array_equal(gg, g), f"{what}: d_rows + {shift} floats"
+
+
+@pytest.mark.parametrize("n_mels,mode,tol", MODES, ids=MODE_IDS)
+def test_finalize_tiles(oracle, n_mels, mode, tol):
+    """T around one and two tiles, at pad_to = 0 (n = 160 T): each clip alone, then all of them as one batch"""
+    clips = [noise(500 + T, 160 * T, oracle) for T in TILE_T]
+    mel = make(n_mels, mode)
+    alone = []
+    for T, c in zip(TILE_T, clips):
+        assert R.frame_classes(c.shape[0], 0) == (T, T - 3, T)
+        fm, rows, g = check_batch(mel, ("tile", T), [c], 0, tol, mode != "f32", f"T {T} mels {n_mels} mode {mode}")
+        assert fm[0].shape == (T, n_mels)
+        alone.append((fm[0], rows[0], g[0]))
+        if T in (64, 68, 128):
+            _shifted(mel, [c], 0, fm, rows, g, f"T {T}")
+    fm, rows, g = check_batch(mel, "tile-all", clips, 0, tol, mode != "f32", f"T {TILE_T} in one batch, mels {n_mels} mode {mode}")
+    for i, (a, r, m) in enumerate(alone):
+        assert same(fm[i], a) and same(rows[i], r) and g[i] == m, f"T {TILE_T[i]} alone differs from the clip inside the batch"
+    mel.close()
+
+
+@pytest.mark.parametrize("n_mels,mode,tol", MODES, ids=MODE_IDS)
+def test_finalize_tiles_at_the_silent_boundary(oracle, n_mels, mode, tol):
+    """pad_to of exactly one tile, a tile and four frames, two tiles: every frame silent, the boundary inside the first tile, exactly on the
+    tile's edge (first_silent == 64), two frames past it, and (pad_to 20480) near the end of the second tile"""
+    clips = [noise(600 + i, n, oracle) for i, n in enumerate(TILE_PAD_N)]
+    mel = make(n_mels, mode)
+    for pad_to, T in TILE_PADS.items():
+        cls = [R.frame_classes(n, pad_to) for n in TILE_PAD_N]
+        assert [c[0] for c in cls] == [T] * len(clips)
+        assert [c[2] for c in cls] == [0, 8, 64, min(66, T), min(127, T)], cls
+        fm, rows, g = check_batch(mel, ("tile-pad", pad_to), clips, pad_to, tol, mode != "f32", f"pad_to {pad_to} n {TILE_PAD_N} mels {n_mels} mode {mode}")
+        for i, c in enumerate(cls):
+            assert np.all(rows[i][c[2]:] == np.float32(-10.0)), "a silent frame's raw row is not exactly -10"
+            lo = np.float32(np.float32(g[i]) - np.float32(8.0))
+            assert np.all(fm[i][c[2]:] == (np.maximum(np.float32(-10.0), lo) + np.float32(4.0)) * np.float32(0.25)), "a silent frame's normalised row"
+        _shifted(mel, clips, pad_to, fm, rows, g, f"pad_to {pad_to}")
+    mel.close()
+
+
+# ---- caller-chosen output offsets: h_out_offsets / h_rows_offsets -----------------------------------------------------------------------------
+def _gapped(Ts, n_mels, gaps, order):
+    """offsets, in floats, that lay the clips out in `order` with gaps[k] spare floats in front of the k-th one laid down"""
+    offs, cur = [0] * len(Ts), 0
+    for k, i in enumerate(order):
+        cur += gaps[k]
+        offs[i] = cur
+        cur += Ts[i] * n_mels
+    return offs
+
+
+@pytest.mark.parametrize("n_mels", [80, 128])
+@pytest.mark.parametrize("pad_to", [0, 10240])
+def test_caller_chosen_offsets(oracle, pad_to, n_mels):
+    """the packed call's bits, clip by clip, wherever the caller puts them -- in clip order and reversed, with gaps that leave some clips'
+    first float off a multiple of four (the mel-major 16-byte path is off for them: T = 64, 68, 128 among them) and some on one; every
+    float of every gap keeps its sentinel (run_norm / run_split check that).  pad_to 10240: T = 64 for all, with all-silent clips and
+    silent tails -- the fill pass on caller-chosen offsets"""
+    lens = [160 * 64, 160 * 128 + 35, 5000, 160 * 68, 1360, 160 * 100 + 7] if pad_to == 0 else [1000, 10040, 0, 5000, 20000, 10239]
+    clips = [noise(800 + i, n, oracle) for i, n in enumerate(lens)]
+    Ts = [R.num_frames(n, pad_to) for n in lens]
+    assert Ts == ([64, 128, 31, 68, 8, 100] if pad_to == 0 else [64] * 6)
+    mel = make(n_mels)
+    fm, rows, g = check_batch(mel, ("offsets", pad_to), clips, pad_to, F64_TOL, True, f"offsets: the packed call, pad_to {pad_to} mels {n_mels}")
+    for order in (list(range(6)), list(range(5, -1, -1))):
+        offs = _gapped(Ts, n_mels, [0, 1, 3, 5, 2, 7], order)
+        full = [(o & 3) for o, T in zip(offs, Ts) if T % 4 == 0 and T >= 64]
+        assert 0 in full and any(full), "the offsets do not turn the 16-byte path both on and off"
+        for mel_major in (True, False):
+            got = run_norm(mel, clips, pad_to, mel_major, out_offsets=offs)
+            for i in range(6):
+                assert same(got[i], fm[i]), f"clip {i} at float {offs[i]}, mel_major {mel_major}"
+        r, gg = run_split(mel, clips, pad_to, rows_offsets=offs)
+        for i in range(6):
+            assert same(r[i], rows[i]), f"clip {i}: raw rows at float {offs[i]}"
+        assert np.array_equal(gg, g)
+    mel.close()
+
+
+# ---- the uniform calls: a stride past the clip, a stride of zero, trimming more than one clip ---------------------------------------------------
+def _uniform(mel, d_ptr, stride, n, k, pad_to):
+    """the three uniform calls -> (mel-major transposed back [k][T][mels], frame-major, raw rows, maxima)"""
+    T, nm = R.num_frames(n, pad_to), mel.n_mels
+    mm, fm, rows, mx = Fenced(k * T * nm), Fenced(k * T * nm), Fenced(k * T * nm), Fenced(k)
+    try:
+        M.whisper_uniform_device(mel, d_ptr, stride, n, k, mm.ptr, pad_to, True)
+        M.whisper_uniform_device(mel, d_ptr, stride, n, k, fm.ptr, pad_to, False)
+        M.whisper_uniform_device_split(mel, d_ptr, stride, n, k, rows.ptr, mx.ptr, pad_to)
+        mel.synchronize()
+        return mm.get().reshape(k, nm, T).transpose(0, 2, 1), fm.get().reshape(k, T, nm), rows.get().reshape(k, T, nm), mx.get().copy()
+    finally:
+        mm.free(); fm.free(); rows.free(); mx.free()
+
+
+def test_uniform_strides_and_trim(oracle):
+    from mel_spec_amd.hip import DeviceBuffer
+    n, k = 2400, 5
+    clips = [noise(400 + i, n, oracle) for i in range(k)]
+    mel = make(80)
+    # clip_stride > clip_len: what lies between the clips is not the call's to read (1e3 there would be heard in every edge frame)
+    stride = n + 37
+    buf = np.full(stride * k, 1e3, np.float32)
+    for i, c in enumerate(clips):
+        buf[i * stride:i * stride + n] = c
+    d = DeviceBuffer(buf.nbytes)
+    d.upload(buf)
+    for pad_to in (0, 4800):
+        fm_w, rows_w, g_w = check_batch(mel, "uniform-5", clips, pad_to, F64_TOL, True, f"five clips of 2400, pad_to {pad_to}")
+        mm, fm, rows, g = _uniform(mel, d.ptr, stride, n, k, pad_to)
+        for i in range(k):
+            assert same(mm[i], fm_w[i]) and same(fm[i], fm_w[i]) and same(rows[i], rows_w[i]), f"stride {stride}, pad_to {pad_to}, clip {i}"
+        assert np.array_equal(g, g_w)
+        # clip_stride == 0: the same clip n_clips times
+        mm, fm, rows, g = _uniform(mel, d.ptr, 0, n, 3, pad_to)
+        for i in range(3):
+            assert same(mm[i], fm_w[0]) and same(fm[i], fm_w[0]) and same(rows[i], rows_w[0]) and g[i] == g_w[0], f"stride 0, pad_to {pad_to}, copy {i}"
+    d.free()
+    # trim: clip_len > pad_to, more than one clip
+    d = DeviceBuffer(n * k * 4)
+    d.upload(np.concatenate(clips))
+    cut = [c[:1600] for c in clips]
+    fm_w, rows_w, g_w = check_batch(mel, "uniform-5-trimmed", cut, 1600, F64_TOL, True, "five clips of 2400 trimmed to 1600")
+    mm, fm, rows, g = _uniform(mel, d.ptr, n, n, k, 1600)
+    assert fm.shape == (k, 10, 80)
+    for i in range(k):
+        assert same(mm[i], fm_w[i]) and same(fm[i], fm_w[i]) and same(rows[i], rows_w[i]), f"trimmed clip {i}"
+    assert np.array_equal(g, g_w)
+    d.free()
+    # the host call trims too
+    x = noise(410, 9000, oracle)
+    assert same(M.whisper_features(mel, x, 4800), M.whisper_features(mel, x[:4800], 4800))
+    assert same(M.whisper_features(mel, x, 4800).T, run_norm(mel, [x[:4800]], 4800, True)[0])
+    mel.close()
+
+
+# ---- a clip without a frame in the middle of a batch that has frames ------------------------------------------------------------------------
+@pytest.mark.parametrize("mode,tol", [(None, F64_TOL), ("f32", F32_TOL)], ids=["f64", "f32"])
+def test_clips_without_a_frame_inside_a_batch(oracle, mode, tol):
+    lens = [1360, 0, 399, 700, 200, 5000]
+    clips = [noise(900 + i, n, oracle) for i, n in enumerate(lens)]
+    mel = make(80, mode)
+    fm, rows, g = check_batch(mel, "frameless", clips, 0, tol, mode != "f32", f"lengths {lens}, mode {mode}")
+    for i in (1, 2, 4):
+        assert g[i] == np.float32(-10.0) and rows[i].shape == (0, 80) and fm[i].shape == (0, 80)
+    for i in (0, 3, 5):          # their rows and words are where they would be without the frameless clips between them
+        for mel_major in (True, False):
+            assert same(run_norm(mel, [clips[i]], 0, mel_major)[0], fm[i]), f"clip {i} alone, mel_major {mel_major}"
+        r1, g1 = run_split(mel, [clips[i]], 0)
+        assert same(r1[0], rows[i]) and g1[0] == g[i], f"clip {i} alone: raw rows / maximum"
+    mel.close()
+
+
+# ---- 128 mels (the 15-slot f64 kernel) with runs that cross clips; F32 mode at 128 mels is the f64 kernel ----------------------------------------
+def test_ragged_1100_at_128_mels(oracle):
+    clips = _ragged_1100(oracle)
+    mel = make(128, "f64")
+    assert "six64_raw_kernel<15" in M.whisper_kernel_name(mel)
+    fm, rows, g = check_batch(mel, "ragged-1100", clips, 0, F64_TOL, True, "1100 ragged clips, 128 mels, f64")
+    mel.set_precision("f32")
+    assert "six64_raw_kernel<15" in M.whisper_kernel_name(mel) and "six_runs_raw" not in M.whisper_kernel_name(mel)
+    fm32 = run_norm(mel, clips, 0, True)
+    rows32, g32 = run_split(mel, clips, 0)
+    for i in range(len(clips)):
+        assert same(fm32[i], fm[i]) and same(rows32[i], rows[i]), f"clip {i}: F32 mode at 128 mels differs from F64 mode"
+    assert np.array_equal(g32, g)
+    mel.close()
+
+
+# ---- pad_to other than 4800 / 480000 on the device --------------------------------------------------------------------------------------------
+DEVICE_PADS = [400, 401, 559, 560, 4799, 4801, 4959]
+
+
+def _pad_lengths(pad_to):
+    ns = [0, 1, 200, 399, 400, 560, pad_to - 201, pad_to - 200, pad_to - 1, pad_to, pad_to + 1, pad_to + 500]
+    return [n for k, n in enumerate(ns) if n >= 0 and n not in ns[:k]]
+
+
+@pytest.mark.parametrize("n_mels,mode,tol", MODES, ids=MODE_IDS)
+def test_pad_to_on_the_device(oracle, n_mels, mode, tol):
+    mel = make(n_mels, mode)
+    for pad_to in DEVICE_PADS:
+        lens = _pad_lengths(pad_to)
+        for n in lens:
+            assert M.whisper_num_frames(mel, n, pad_to) == R.num_frames(n, pad_to) == pad_to // 160
+        clips = [noise(1200 + i, n, oracle) for i, n in enumerate(lens)]
+        check_batch(mel, ("device-pad", pad_to), clips, pad_to, tol, mode != "f32", f"pad_to {pad_to} n {lens} mels {n_mels} mode {mode}")
+    mel.close()
+
+
+# ---- quiet input: values on the 1e-10 floor, a hole of digital silence in the interior of a loud clip --------------------------------------------
+QUIET = ["1e-4", "1e-5", "1e-6", "hole"]
+
+
+def _quiet_clips():
+    x = np.random.default_rng(9000).standard_normal(9000)
+    clips = [(s * x).astype(np.float32) for s in (1e-4, 1e-5, 1e-6)]
+    hole = (0.1 * x).astype(np.float32)
+    hole[3000:6000] = 0.0          # frames 20 .. 36 of 56 read zeros only; they are interior: transformed, not filled
+    return clips + [hole]
+
+
+@pytest.mark.parametrize("n_mels,mode,tol", MODES, ids=MODE_IDS)
+def test_quiet_input(oracle, n_mels, mode, tol):
+    clips = _quiet_clips()
+    want = ref("quiet", clips, 0, n_mels)
+    on_floor = [float(np.mean(w[0] == -10.0)) for w in want]
+    print(f"quiet input, {n_mels} mels: share of the reference's values on the floor {on_floor}, maxima {[w[1] for w in want]}")
+    assert on_floor[2] == 1.0 and want[2][1] == -10.0 and 0.05 <= on_floor[1] <= 0.25 and -7.0 < want[0][1] < -6.0
+    if n_mels == 80:
+        assert on_floor[0] == 0.0
+    assert R.frame_classes(9000, 0) == (56, 54, 56)
+    assert np.all(want[3][0][20:37] == -10.0) and not np.any(want[3][0][:20] == -10.0) and not np.any(want[3][0][37:] == -10.0)
+    mel = make(n_mels, mode)
+    results = [check_batch(mel, ("quiet", QUIET[i]), [c], 0, tol, mode != "f32", f"quiet {QUIET[i]} mels {n_mels} mode {mode}") for i, c in enumerate(clips)]
+    fm, rows, g = check_batch(mel, "quiet", clips, 0, tol, mode != "f32", f"quiet, all four in one batch, mels {n_mels} mode {mode}")
+    for i in range(len(clips)):
+        assert same(fm[i], results[i][0][0]) and same(rows[i], results[i][1][0]) and g[i] == results[i][2][0]
+        # what the code promises of the floor: no raw value under -10, no normalised value under the clip's clamp
+        assert np.all(rows[i] >= np.float32(-10.0)) and g[i] >= np.float32(-10.0)
+        lo = np.float32(np.float32(g[i]) - np.float32(8.0))
+        assert np.all(fm[i] >= (lo + np.float32(4.0)) * np.float32(0.25))
+    mel.close()

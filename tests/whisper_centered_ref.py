@@ -28,6 +28,20 @@ def num_frames(n: int, pad_to: int) -> int:
     return 0 if P < N_FFT else P // HOP
 
 
+def frame_classes(n: int, pad_to: int):
+    """(T, interior, first_silent): frames [0, 2) and [2 + interior, first_silent) read mirrored samples or straddle the end of the
+    caller's samples (the library's edge frames), [2, 2 + interior) are ordinary un-centred frames, [first_silent, T) read zeros only --
+    the rule of the library's host plan (wc_clip), restated"""
+    P = pad_to if pad_to else n
+    n_eff = min(n, P)
+    T = 0 if P < N_FFT else P // HOP
+    if T == 0 or n_eff == 0:
+        return T, 0, 0
+    t_max = (n_eff - PAD) // HOP if n_eff >= PAD else 0
+    interior = t_max - 1 if t_max >= 2 else 0
+    return T, interior, min(max(-(-(n_eff + PAD) // HOP), 2), T)
+
+
 @functools.lru_cache(maxsize=None)
 def filters(n_mels: int) -> np.ndarray:
     return O.mel_filterbank(16000.0, N_FFT, n_mels)
