@@ -197,7 +197,8 @@ int melspec_mel_from_stft_host(melspec_ctx *ctx, const void *spec, int dtype, in
  * through, the per-frame clamp, so AUTO's promise (within 1e-4 of the f64 evaluation on every input) is kept by computing in f64 here.
  * The frames that reflect or straddle the end of the samples (a handful per clip) are computed in f64 whatever the mode.
  * melspec_whisper_kernel_name names the kernel of the current mode.
- * NOT covered, left for later: int16 PCM in, f16 / bf16 out; the device-resident clip table (_desc); the sharded object; the stream bank.
+ * int16 PCM in and f16 / bf16 out: the melspec_whisper_*_io calls in the 16-bit section below.
+ * NOT covered, left for later: the device-resident clip table (_desc); the sharded object; the stream bank.
  *
  * The device calls are stream-ordered and asynchronous (stream NULL: the context's), they do not synchronise with the host and allocate
  * nothing of the caller's; the scratch of the normalised calls (raw rows, one maximum word per clip) is the context's grow-only scratch
@@ -321,6 +322,37 @@ int melspec_compute_ragged_device_io(melspec_ctx *ctx, const void *d_pcm, int pc
 /* melspec_compute_host with 16-bit ends: the int16 bytes are what crosses the bus, and so are the 16-bit rows. */
 int melspec_compute_host_io(melspec_ctx *ctx, const void *samples, int pcm_dtype, size_t n_samples,
                             void *out, int out_dtype, size_t out_capacity_elems, size_t *n_frames);
+
+/* The centred Whisper features (the melspec_whisper_* calls above) with the same 16-bit ends.  Everything said there holds -- frame
+ * count, pad / trim, precision modes and melspec_whisper_kernel_name, stream ordering, the context's scratch -- and everything said at
+ * the top of this section: MELSPEC_PCM_S16 gives the bits of the f32 call on the batch converted by `v as f32 / 32768.0`, MELSPEC_OUT_F16 /
+ * _BF16 the round-to-nearest-even of the f32 value the f32 call writes; strides, offsets, lengths and capacities count ELEMENTS; only the
+ * natural alignment of the element type is required (an int16 clip may start at an odd sample, a 16-bit output at an odd element).
+ *   Normalised calls: the raw rows and the clip maximum stay f32 in the context's scratch, the clamp runs in f32, and the value is rounded
+ *   once, at the final store.
+ *   Split calls: d_rows holds the raw log10 values in out_dtype; d_clip_max stays f32 and holds the bits of the f32 split call's -- the
+ *   maximum is taken over the f32 values before rounding.  Rounding is monotone, so round(g) is the largest stored value of the clip.  A
+ *   silent row is exactly -10 (representable in both 16-bit types); a clip without a frame writes only g = -10.
+ * All six (pcm_dtype, out_dtype) combinations are computed on the contexts of melspec_whisper_supports (melspec_whisper_supports_io == 1);
+ * (F32, F32) is the f32 call: same kernels, same bits.  Every other context returns MELSPEC_ERR_UNSUPPORTED and leaves its output untouched.
+ * Statuses: an unknown dtype code is MELSPEC_ERR_INVALID_ARG, checked right after the NULL context; a d_pcm, d_out or d_rows that is not
+ * aligned to its element type is MELSPEC_ERR_INVALID_ARG, checked with the device pointers; everything else is the f32 calls' order.
+ * NOT covered: the device-resident clip table (_desc); the sharded object; the stream bank. */
+int melspec_whisper_supports_io(const melspec_ctx *ctx, int pcm_dtype, int out_dtype);
+int melspec_whisper_compute_uniform_device_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                              uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype, int mel_major, void *stream);
+int melspec_whisper_compute_ragged_device_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                             const uint64_t *h_lengths, uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype,
+                                             const uint64_t *h_out_offsets, int mel_major, void *stream);
+int melspec_whisper_compute_uniform_device_split_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
+                                                    uint32_t n_clips, uint64_t pad_to, void *d_rows, int out_dtype, float *d_clip_max,
+                                                    void *stream);
+int melspec_whisper_compute_ragged_device_split_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets,
+                                                   const uint64_t *h_lengths, uint32_t n_clips, uint64_t pad_to, void *d_rows, int out_dtype,
+                                                   const uint64_t *h_rows_offsets, float *d_clip_max, void *stream);
+/* One clip from host memory: the int16 bytes are what crosses the bus, and so are the 16-bit features.  out_capacity_elems >= T * n_mels. */
+int melspec_whisper_compute_host_io(melspec_ctx *ctx, const void *samples, int pcm_dtype, size_t n_samples, size_t pad_to, void *out,
+                                    int out_dtype, size_t out_capacity_elems, int mel_major, size_t *n_frames);
 
 /* Benchmark helper (the reference's #[ignore] Instant-timed benches, src/cuda.rs:547-613): runs
  * `warmup` untimed and `iters` timed melspec_compute_uniform_device calls on the context's own

@@ -52,7 +52,11 @@
         int opaque0 = 0;
         asm volatile("" : "+s"(opaque0));
         const double *tbi = tb + opaque0;
+#ifdef MS_SIX64_RAW
+        six64_phases12<MS_SIX64_IN, true>(fl, j, act, rofs, p.hop, tbi, src, rows, slice);        // int16 samples: all loads in front of the first conversion (six64_phase1)
+#else
         six64_phases12(fl, j, act, rofs, p.hop, tbi, src, rows, slice);
+#endif
         __builtin_amdgcn_wave_barrier();
         MS_PRIO(2);
         float vals[NSLOTS];

@@ -1,108 +1,30 @@
 // whisper_centered.hip -- the centred Whisper features (melspec_whisper_*, include/melspec_hip.h has the semantics): the f64 raw kernels
 // and the small kernels of whisper_centered_kernels.hpp, their launches and the C ABI.  Default scheduling strategy; the f32 raw kernel is
-// emitted by whisper_centered_runs.hip with melspec_runs.hip's.
+// emitted by whisper_centered_runs.hip with melspec_runs.hip's.  The kernels with int16 PCM in / f16, bf16 out (melspec_whisper_*_io) are
+// emitted by whisper_centered_io.hip / whisper_centered_io_runs.hip and launched from here: one wc_run for all six combinations.
 //
 // One call is, on its stream:  the tables' upload (the interior's plan through plan_ragged, everything else in one slot of the feature's
 // own ring) -> wc_prepare_kernel (maximum words, edge samples) -> the raw kernel on the interior -> the f64 raw kernel on the edge frames
 // -> wc_finalize_kernel (normalised calls) or wc_fill_kernel + wc_clip_max_kernel (split calls).
 #include "host_common.hpp"
-#include "whisper_centered_kernels.hpp"
+#include "whisper_centered_io_kernels.hpp"
 
 namespace melspec {
 extern template __global__ void whisper400_six_runs_raw_kernel<kSixMaxSlots, LensSix80>(const WcRawParams);      // whisper_centered_runs.hip
 template __global__ void whisper400_six64_raw_kernel<kSixMaxSlots, LensSix80>(const WcRaw64Params);
 template __global__ void whisper400_six64_raw_kernel<kSixWideSlots, LensSix128>(const WcRaw64Params);
-
-// ---- the small kernels ------------------------------------------------------------------------------------------------------------------
-// blocks [0, n_edges): the 400 samples of edge frame e to edge_pcm + 400 e (host::wc_source_index's rule); the blocks behind them: the
-// maximum words
-__global__ __launch_bounds__(256) void wc_prepare_kernel(const float *pcm, const host::WcEdge *edges, uint32_t n_edges, float *edge_pcm, int *slots, uint32_t n_slots) {
-    if (blockIdx.x >= n_edges) {
-        const uint64_t i = static_cast<uint64_t>(blockIdx.x - n_edges) * 256 + threadIdx.x;
-        if (i < n_slots) slots[i] = kWcFloorBits;
-        return;
-    }
-    const host::WcEdge e = edges[blockIdx.x];
-    const float *src = pcm + e.pcm_off;
-    float *dst = edge_pcm + static_cast<uint64_t>(blockIdx.x) * host::kWcFft;
-    for (unsigned i = threadIdx.x; i < host::kWcFft; i += 256) {
-        long long idx = static_cast<long long>(e.t * host::kWcHop + i) - static_cast<long long>(host::kWcPad);
-        if (idx < 0) idx = -idx;
-        if (idx >= static_cast<long long>(e.P)) idx = 2 * (static_cast<long long>(e.P) - 1) - idx;
-        dst[i] = idx < static_cast<long long>(e.n_eff) ? src[idx] : 0.0f;
-    }
-}
-
-constexpr int kWcTile = 64;      // frames per tile of the fill and finalise passes
-
-// rows [first_silent, T) of every clip: -10.  Grid (clips, tiles of kWcTile frames).
-__global__ __launch_bounds__(256) void wc_fill_kernel(const host::WcRecord *rec, float *rows, int n_mels) {
-    const host::WcRecord r = rec[blockIdx.x];
-    const uint64_t tiles = (r.T + kWcTile - 1) / kWcTile;
-    for (uint64_t tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
-        const uint64_t t0 = tile * kWcTile, t1 = t0 + kWcTile < r.T ? t0 + kWcTile : r.T;
-        const uint64_t a = (t0 > r.first_silent ? t0 : r.first_silent) * n_mels, b = t1 * n_mels;
-        float *o = rows + r.rows_off;
-        for (uint64_t i = a + threadIdx.x; i < b; i += 256) o[i] = host::kWcFloorLog;
-    }
-}
+template __global__ void wc_prepare_kernel<float>(const float *, const host::WcEdge *, uint32_t, float *, int *, uint32_t);
+template __global__ void wc_fill_kernel<float>(const host::WcRecord *, float *, int);
+template __global__ void wc_finalize_kernel<float>(const host::WcRecord *, const float *, const int *, float *, int, int);
+// int16 PCM in / f16, bf16 out: whisper_centered_io_runs.hip, whisper_centered_io.hip
+#define MS_IO_EXTERN(In, Out) MS_WC_IO_RUNS(extern template __global__ void, In, Out) MS_WC_IO_64(extern template __global__ void, In, Out)
+MS_IO_COMBOS(MS_IO_EXTERN)
+#undef MS_IO_EXTERN
+MS_WC_IO_SMALL(extern template __global__ void)
 
 __global__ __launch_bounds__(256) void wc_clip_max_kernel(int *slots, uint32_t n) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     if (i < n) reinterpret_cast<float *>(slots)[i] = six_float(slots[i]) - 16.0f;
-}
-
-__device__ __forceinline__ float wc_norm(float raw, float lo) { return (__builtin_fmaxf(raw, lo) + 4.0f) * 0.25f; }
-
-// One tile of kWcTile frames x n_mels per pass.  Frame-major: element by element, coalesced.  Mel-major: the tile goes through LDS
-// ([mel][kWcTile + 1]: the column reads of the transpose hit 32 different banks) and leaves as row pieces of kWcTile floats -- 16-byte
-// stores where the clip's rows allow it (T and the clip's first float multiples of four, d_out 16-byte aligned: WHISPER's 3000-frame clips
-// always), single floats otherwise.  Silent frames are not read: their value is a function of the clip maximum alone.
-// Grid (clips, tiles).  LDS: n_mels * (kWcTile + 1) floats (mel-major only).
-__global__ __launch_bounds__(256) void wc_finalize_kernel(const host::WcRecord *rec, const float *rows, const int *slots, float *out, int n_mels, int mel_major) {
-    extern __shared__ __attribute__((aligned(16))) float wc_tile[];
-    const host::WcRecord r = rec[blockIdx.x];
-    const float lo = (six_float(slots[blockIdx.x]) - 16.0f) - 8.0f;
-    const float silent = wc_norm(host::kWcFloorLog, lo);
-    const uint64_t tiles = (r.T + kWcTile - 1) / kWcTile;
-    const float *in = rows + r.rows_off;
-    float *o = out + r.out_off;
-    const int tid = threadIdx.x;
-    for (uint64_t tile = blockIdx.y; tile < tiles; tile += gridDim.y) {
-        const uint64_t t0 = tile * kWcTile;
-        const int nt = static_cast<int>(r.T - t0 < static_cast<uint64_t>(kWcTile) ? r.T - t0 : kWcTile);
-        const int live = r.first_silent <= t0 ? 0 : static_cast<int>(r.first_silent - t0 < static_cast<uint64_t>(nt) ? r.first_silent - t0 : nt);      // frames of the tile with rows
-        const int n = nt * n_mels, nl = live * n_mels;
-        if (!mel_major) {
-            for (int i = tid; i < n; i += 256) o[t0 * n_mels + i] = i < nl ? wc_norm(in[t0 * n_mels + i], lo) : silent;
-            continue;
-        }
-        constexpr int kStride = kWcTile + 1;
-        for (int i = tid; i < nl; i += 256) {
-            const int t = i / n_mels, m = i - t * n_mels;
-            wc_tile[m * kStride + t] = wc_norm(in[t0 * n_mels + i], lo);
-        }
-        __syncthreads();
-        const bool wide = nt == kWcTile && ((r.T | r.out_off) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-        if (wide) {
-            for (int i = tid; i < n_mels * (kWcTile / 4); i += 256) {
-                const int m = i / (kWcTile / 4), q = i - m * (kWcTile / 4);
-                const float *s = wc_tile + m * kStride + 4 * q;
-                float4 v;
-                v.x = 4 * q + 0 < live ? s[0] : silent;
-                v.y = 4 * q + 1 < live ? s[1] : silent;
-                v.z = 4 * q + 2 < live ? s[2] : silent;
-                v.w = 4 * q + 3 < live ? s[3] : silent;
-                *reinterpret_cast<float4 *>(o + static_cast<uint64_t>(m) * r.T + t0 + 4 * q) = v;
-            }
-        } else {
-            for (int i = tid; i < n_mels * kWcTile; i += 256) {
-                const int m = i / kWcTile, t = i - m * kWcTile;
-                if (t < nt) o[static_cast<uint64_t>(m) * r.T + t0 + t] = t < live ? wc_tile[m * kStride + t] : silent;
-            }
-        }
-        __syncthreads();
-    }
 }
 
 }  // namespace melspec
@@ -119,14 +41,37 @@ int wc_unsupported(const melspec_ctx *c) {
     return MELSPEC_ERR_UNSUPPORTED;
 }
 
+// ---- the raw kernels of a (sample, row) combination; io = pcm_dtype | out_dtype << 4 (io_dtypes), 0: the f32 kernels -----------------------
+typedef void (*WcRaw32)(const WcRawParams);
+typedef void (*WcRaw64)(const WcRaw64Params);
+struct WcRawKernels {
+    WcRaw32 runs80;
+    WcRaw64 f64_80, f64_128;
+};
+template <class In, class Out>
+WcRawKernels wc_raw_io_of() {
+    return WcRawKernels{&whisper400_six_runs_raw_io_kernel<kSixMaxSlots, LensSix80, In, Out>, &whisper400_six64_raw_io_kernel<kSixMaxSlots, LensSix80, In, Out>,
+                        &whisper400_six64_raw_io_kernel<kSixWideSlots, LensSix128, In, Out>};
+}
+// the kernels are allowed the whole LDS once per device and combination
+int wc_raw_kernels(int io, const WcRawKernels *&k) {
+    static const WcRawKernels table[2][3] = {
+        {WcRawKernels{&whisper400_six_runs_raw_kernel<kSixMaxSlots, LensSix80>, &whisper400_six64_raw_kernel<kSixMaxSlots, LensSix80>,
+                      &whisper400_six64_raw_kernel<kSixWideSlots, LensSix128>},
+         wc_raw_io_of<float, io_f16>(), wc_raw_io_of<float, io_bf16>()},
+        {wc_raw_io_of<io_s16, float>(), wc_raw_io_of<io_s16, io_f16>(), wc_raw_io_of<io_s16, io_bf16>()}};
+    static std::atomic<uint64_t> attr_done[2][3];
+    const int pcm = io & 15, out = io >> 4;
+    if (pcm < 0 || pcm > 1 || out < 0 || out > 2) return fail(MELSPEC_ERR_INTERNAL, "wc_raw_kernels: no such combination");
+    k = &table[pcm][out];
+    return allow_big_lds_once(attr_done[pcm][out], "hipFuncSetAttribute(whisper400 raw kernels)", k->runs80, k->f64_80, k->f64_128);
+}
+
 // the f64 raw kernel on a six-frame plan (launch_six64's shape)
-int wc_launch64(melspec_ctx *c, const BatchDesc &desc, int *slots, const uint32_t *slot_map, hipStream_t s) {
+int wc_launch64(melspec_ctx *c, const BatchDesc &desc, int *slots, const uint32_t *slot_map, hipStream_t s, int io) {
     if (desc.n_units == 0) return MELSPEC_OK;
-    typedef void (*K)(const WcRaw64Params);
-    const K k = c->six64_wide ? static_cast<K>(&whisper400_six64_raw_kernel<kSixWideSlots, LensSix128>) : static_cast<K>(&whisper400_six64_raw_kernel<kSixMaxSlots, LensSix80>);
-    static std::atomic<uint64_t> attr_done{0};
-    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(whisper400_six64_raw_kernel)", &whisper400_six64_raw_kernel<kSixMaxSlots, LensSix80>,
-                                    &whisper400_six64_raw_kernel<kSixWideSlots, LensSix128>)) return rc;
+    const WcRawKernels *k = nullptr;
+    if (int rc = wc_raw_kernels(io, k)) return rc;
     const uint64_t blocks = (desc.n_units + kSix64Waves - 1) / kSix64Waves;
     const unsigned grid = grid_for_xcd(blocks, c->dev.cus, 1);
     WcRaw64Params q{};
@@ -138,16 +83,16 @@ int wc_launch64(melspec_ctx *c, const BatchDesc &desc, int *slots, const uint32_
     q.f.n_mels = c->n_mels;
     q.f.slots = c->ft6.slots;
     q.slots = slots; q.slot_map = slot_map;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(kSix64Waves * 64), c->lds64x, s, q);
+    hipLaunchKernelGGL(c->six64_wide ? k->f64_128 : k->f64_80, dim3(grid), dim3(kSix64Waves * 64), c->lds64x, s, q);
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
 }
 
 // the f32 raw kernel (launch_fast's shape for the sixteen-wave family; no guard, no vote)
-int wc_launch32(melspec_ctx *c, const BatchDesc &desc, int *slots, hipStream_t s) {
+int wc_launch32(melspec_ctx *c, const BatchDesc &desc, int *slots, hipStream_t s, int io) {
     if (desc.n_units == 0) return MELSPEC_OK;
-    static std::atomic<uint64_t> attr_done{0};
-    if (int rc = allow_big_lds_once(attr_done, "hipFuncSetAttribute(whisper400_six_runs_raw_kernel)", &whisper400_six_runs_raw_kernel<kSixMaxSlots, LensSix80>)) return rc;
+    const WcRawKernels *k = nullptr;
+    if (int rc = wc_raw_kernels(io, k)) return rc;
     const uint64_t blocks = (desc.n_units + kSixWaves - 1) / kSixWaves;
     const unsigned grid = grid_for_xcd(blocks, c->dev.cus, 1);
     WcRawParams q{};
@@ -159,25 +104,53 @@ int wc_launch32(melspec_ctx *c, const BatchDesc &desc, int *slots, hipStream_t s
     q.f.slice_floats = WaveLayout::slice_floats();
     q.f.slots = c->ft6.slots;
     q.slots = slots; q.slot_map = nullptr;
-    hipLaunchKernelGGL((whisper400_six_runs_raw_kernel<kSixMaxSlots, LensSix80>), dim3(grid), dim3(kSixWaves * 64), c->lds6, s, q);
+    hipLaunchKernelGGL(k->runs80, dim3(grid), dim3(kSixWaves * 64), c->lds6, s, q);
     HIP_TRY(hipGetLastError());
     return MELSPEC_OK;
 }
 
+// ---- the small kernels by the call's types -------------------------------------------------------------------------------------------------
+void wc_prepare(const void *d_pcm, int pcm_dtype, const WcEdge *d_edges, uint32_t n_edges, float *d_edge_pcm, int *d_slots, uint32_t n_clips, hipStream_t s) {
+    const dim3 grid(n_edges + (n_clips + 255) / 256);
+    if (pcm_dtype == MELSPEC_PCM_S16)
+        hipLaunchKernelGGL(wc_prepare_kernel<io_s16>, grid, dim3(256), 0, s, static_cast<const io_s16 *>(d_pcm), d_edges, n_edges, d_edge_pcm, d_slots, n_clips);
+    else
+        hipLaunchKernelGGL(wc_prepare_kernel<float>, grid, dim3(256), 0, s, static_cast<const float *>(d_pcm), d_edges, n_edges, d_edge_pcm, d_slots, n_clips);
+}
+void wc_fill(const WcRecord *d_rec, void *d_rows, int out_dtype, int nm, dim3 grid, hipStream_t s) {
+    if (out_dtype == MELSPEC_OUT_F16) hipLaunchKernelGGL(wc_fill_kernel<io_f16>, grid, dim3(256), 0, s, d_rec, static_cast<io_f16 *>(d_rows), nm);
+    else if (out_dtype == MELSPEC_OUT_BF16) hipLaunchKernelGGL(wc_fill_kernel<io_bf16>, grid, dim3(256), 0, s, d_rec, static_cast<io_bf16 *>(d_rows), nm);
+    else hipLaunchKernelGGL(wc_fill_kernel<float>, grid, dim3(256), 0, s, d_rec, static_cast<float *>(d_rows), nm);
+}
+void wc_finalize(const WcRecord *d_rec, const float *d_rows, const int *d_slots, void *d_out, int out_dtype, int nm, int mel_major, dim3 grid, hipStream_t s) {
+    const size_t lds = mel_major ? static_cast<size_t>(nm) * (kWcTile + 1) * sizeof(float) : 0;
+    if (out_dtype == MELSPEC_OUT_F16)
+        hipLaunchKernelGGL(wc_finalize_kernel<io_f16>, grid, dim3(256), lds, s, d_rec, d_rows, d_slots, static_cast<io_f16 *>(d_out), nm, mel_major);
+    else if (out_dtype == MELSPEC_OUT_BF16)
+        hipLaunchKernelGGL(wc_finalize_kernel<io_bf16>, grid, dim3(256), lds, s, d_rec, d_rows, d_slots, static_cast<io_bf16 *>(d_out), nm, mel_major);
+    else
+        hipLaunchKernelGGL(wc_finalize_kernel<float>, grid, dim3(256), lds, s, d_rec, d_rows, d_slots, static_cast<float *>(d_out), nm, mel_major);
+}
+
 // The batch.  ragged: h_offsets / h_lengths [n_clips]; otherwise clip i = d_pcm + i * clip_stride, clip_len samples.  split: d_dst = the
 // caller's raw rows (dst_offsets: where each clip's start, nullptr: packed) and d_clip_max its maxima; otherwise d_dst = the normalised output.
-int wc_run(melspec_ctx *c, const float *d_pcm, bool ragged, const uint64_t *h_offsets, const uint64_t *h_lengths, uint64_t clip_stride, uint64_t clip_len,
-           uint32_t n_clips, uint64_t pad_to, float *d_dst, const uint64_t *dst_offsets, bool split, float *d_clip_max, int mel_major, void *stream) {
+// pcm_dtype / out_dtype: the element types of d_pcm and d_dst (MELSPEC_PCM_* / MELSPEC_OUT_*; every offset, stride and length counts
+// elements of them).  (F32, F32) launches exactly what the f32 calls always did.  The raw rows of a normalised call are the scratch's, f32
+// whatever out_dtype is, and so are the gathered edge samples: the interior launch is the (pcm_dtype, rows) kernel, the edge launch the
+// (F32, rows) one, and out_dtype reaches the split calls' row stores and the fill / finalise passes.
+int wc_run(melspec_ctx *c, const void *d_pcm, int pcm_dtype, bool ragged, const uint64_t *h_offsets, const uint64_t *h_lengths, uint64_t clip_stride, uint64_t clip_len,
+           uint32_t n_clips, uint64_t pad_to, void *d_dst, int out_dtype, const uint64_t *dst_offsets, bool split, float *d_clip_max, int mel_major, void *stream) {
     uint64_t total = 0;
     if (c && wc_supported(c) && wc_pad_ok(pad_to) && (!ragged || (h_offsets && h_lengths)))
         for (uint32_t i = 0; i < n_clips; ++i) total += wc_num_frames(ragged ? h_lengths[i] : clip_len, pad_to);
-    const WcArgs a = wc_args(c != nullptr, c && wc_supported(c), pad_to, ragged, n_clips, h_offsets, h_lengths, clip_stride, clip_len, total, d_pcm, d_dst, split, d_clip_max);
+    const WcArgs a = wc_args_io(c != nullptr, c && wc_supported(c), pcm_dtype, out_dtype, pad_to, ragged, n_clips, h_offsets, h_lengths, clip_stride, clip_len, total, d_pcm,
+                                d_dst, split, d_clip_max);
     if (a.verdict == kWcFail) return a.msg ? fail(a.status, a.msg) : wc_unsupported(c);
     if (a.verdict == kWcDone) return MELSPEC_OK;
     HIP_TRY(hipSetDevice(c->dev.device));
     hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
     if (a.verdict == kWcSlots) {          // no clip has a frame: the maxima alone
-        hipLaunchKernelGGL(wc_prepare_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, s, nullptr, nullptr, 0u, nullptr, reinterpret_cast<int *>(d_clip_max), n_clips);
+        wc_prepare(nullptr, MELSPEC_PCM_F32, nullptr, 0u, nullptr, reinterpret_cast<int *>(d_clip_max), n_clips, s);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(wc_clip_max_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, s, reinterpret_cast<int *>(d_clip_max), n_clips);
         HIP_TRY(hipGetLastError());
@@ -189,12 +162,14 @@ int wc_run(melspec_ctx *c, const float *d_pcm, bool ragged, const uint64_t *h_of
     if (b.edges.size() > 0xffffffffull) return fail(MELSPEC_ERR_INVALID_ARG, "too many clips for one call");
     const uint32_t n_edges = static_cast<uint32_t>(b.edges.size());
     int rc;
-    float *d_rows = d_dst;
+    void *d_rows = d_dst;
+    const int rows_dtype = split ? out_dtype : MELSPEC_OUT_F32;
+    const int io_interior = pcm_dtype | rows_dtype << 4, io_edge = MELSPEC_PCM_F32 | rows_dtype << 4;
     int *d_slots = reinterpret_cast<int *>(d_clip_max);
     if (!split) {
         if ((rc = c->wc.rows.ensure(b.rows_floats * sizeof(float), s))) return rc;
         if ((rc = c->wc.slots.ensure(static_cast<size_t>(n_clips) * sizeof(int), s))) return rc;
-        d_rows = static_cast<float *>(c->wc.rows.p());
+        d_rows = c->wc.rows.p();
         d_slots = static_cast<int *>(c->wc.slots.p());
     }
     if ((rc = c->wc.edge_pcm.ensure((static_cast<size_t>(n_edges) + 1) * kWcFft * sizeof(float), s))) return rc;
@@ -234,35 +209,34 @@ int wc_run(melspec_ctx *c, const float *d_pcm, bool ragged, const uint64_t *h_of
     RaggedSlot *in_slot = nullptr;
     auto done = [&](int code) { plan_ragged_done(sl, s); plan_ragged_done(in_slot, s); return code; };
 
-    hipLaunchKernelGGL(wc_prepare_kernel, dim3(n_edges + (n_clips + 255) / 256), dim3(256), 0, s, d_pcm, d_edges, n_edges, d_edge_pcm, d_slots, n_clips);
+    wc_prepare(d_pcm, pcm_dtype, d_edges, n_edges, d_edge_pcm, d_slots, n_clips, s);
     if (hipGetLastError() != hipSuccess) return done(fail(MELSPEC_ERR_INTERNAL, "wc_prepare_kernel launch failed"));
 
     // the interior: a plain ragged batch of un-centred frames for the existing planner
     if (b.interior_frames) {
         BatchPlan pl;
-        if ((rc = plan_ragged(c->ragged, s, d_pcm, d_rows, b.in_off.data(), b.in_frames, b.in_out_off.data(), n_clips, nm, kSixFrames, pl, in_slot))) return done(rc);
-        if ((rc = wc_f32(c) ? wc_launch32(c, pl.desc, d_slots, s) : wc_launch64(c, pl.desc, d_slots, nullptr, s))) return done(rc);
+        if ((rc = plan_ragged(c->ragged, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), b.in_off.data(), b.in_frames, b.in_out_off.data(), n_clips, nm, kSixFrames, pl, in_slot))) return done(rc);
+        if ((rc = wc_f32(c) ? wc_launch32(c, pl.desc, d_slots, s, io_interior) : wc_launch64(c, pl.desc, d_slots, nullptr, s, io_interior))) return done(rc);
     }
     // the edge frames, in f64 whatever the mode
     if (n_edges) {
         BatchDesc d{};
-        d.pcm = d_edge_pcm; d.out = d_rows; d.n_clips = n_edges; d.n_units = n_edges; d.frames_per_unit = kSixFrames;
+        d.pcm = d_edge_pcm; d.out = static_cast<float *>(d_rows); d.n_clips = n_edges; d.n_units = n_edges; d.frames_per_unit = kSixFrames;
         d.d_off = d_e64; d.d_frames = d_e64 + n_edges; d.d_out_off = d_e64 + 2 * static_cast<size_t>(n_edges); d.d_unit_prefix = d_e64 + 3 * static_cast<size_t>(n_edges);
         d.d_unit_block = d_eblk;
         d.stat_frames = n_edges;
-        if ((rc = wc_launch64(c, d, d_slots, d_map, s))) return done(rc);
+        if ((rc = wc_launch64(c, d, d_slots, d_map, s, io_edge))) return done(rc);
     }
     const unsigned tiles = static_cast<unsigned>(std::min<uint64_t>((b.max_T + kWcTile - 1) / kWcTile, 65535));
     if (split) {
         if (b.silent_frames) {
-            hipLaunchKernelGGL(wc_fill_kernel, dim3(n_clips, tiles), dim3(256), 0, s, d_rec, d_rows, nm);
+            wc_fill(d_rec, d_rows, out_dtype, nm, dim3(n_clips, tiles), s);
             if (hipGetLastError() != hipSuccess) return done(fail(MELSPEC_ERR_INTERNAL, "wc_fill_kernel launch failed"));
         }
         hipLaunchKernelGGL(wc_clip_max_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, s, d_slots, n_clips);
         if (hipGetLastError() != hipSuccess) return done(fail(MELSPEC_ERR_INTERNAL, "wc_clip_max_kernel launch failed"));
     } else {
-        const size_t lds = mel_major ? static_cast<size_t>(nm) * (kWcTile + 1) * sizeof(float) : 0;
-        hipLaunchKernelGGL(wc_finalize_kernel, dim3(n_clips, tiles), dim3(256), lds, s, d_rec, d_rows, d_slots, d_dst, nm, mel_major ? 1 : 0);
+        wc_finalize(d_rec, static_cast<const float *>(d_rows), d_slots, d_dst, out_dtype, nm, mel_major ? 1 : 0, dim3(n_clips, tiles), s);
         if (hipGetLastError() != hipSuccess) return done(fail(MELSPEC_ERR_INTERNAL, "wc_finalize_kernel launch failed"));
     }
     return done(MELSPEC_OK);
@@ -286,40 +260,80 @@ const char *melspec_whisper_kernel_name(const melspec_ctx *c) {
                          : "melspec::whisper400_six64_raw_kernel<9, LensSix80> (f64 FFT, raw rows + clip maximum)";
 }
 
+int melspec_whisper_supports_io(const melspec_ctx *c, int pcm_dtype, int out_dtype) {
+    return wc_supported(c) && wc_pcm_known(pcm_dtype) && wc_out_known(out_dtype) ? 1 : 0;
+}
+
 int melspec_whisper_compute_uniform_device(melspec_ctx *c, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, uint64_t pad_to,
                                            float *d_out, int mel_major, void *stream) {
-    return wc_run(c, d_pcm, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_out, nullptr, false, nullptr, mel_major, stream);
+    return wc_run(c, d_pcm, MELSPEC_PCM_F32, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_out, MELSPEC_OUT_F32, nullptr, false, nullptr, mel_major, stream);
 }
 int melspec_whisper_compute_ragged_device(melspec_ctx *c, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
                                           uint64_t pad_to, float *d_out, const uint64_t *h_out_offsets, int mel_major, void *stream) {
-    return wc_run(c, d_pcm, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_out, h_out_offsets, false, nullptr, mel_major, stream);
+    return wc_run(c, d_pcm, MELSPEC_PCM_F32, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_out, MELSPEC_OUT_F32, h_out_offsets, false, nullptr, mel_major, stream);
 }
 int melspec_whisper_compute_uniform_device_split(melspec_ctx *c, const float *d_pcm, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips, uint64_t pad_to,
                                                  float *d_rows, float *d_clip_max, void *stream) {
-    return wc_run(c, d_pcm, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_rows, nullptr, true, d_clip_max, 0, stream);
+    return wc_run(c, d_pcm, MELSPEC_PCM_F32, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_rows, MELSPEC_OUT_F32, nullptr, true, d_clip_max, 0, stream);
 }
 int melspec_whisper_compute_ragged_device_split(melspec_ctx *c, const float *d_pcm, const uint64_t *h_offsets, const uint64_t *h_lengths, uint32_t n_clips,
                                                 uint64_t pad_to, float *d_rows, const uint64_t *h_rows_offsets, float *d_clip_max, void *stream) {
-    return wc_run(c, d_pcm, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_rows, h_rows_offsets, true, d_clip_max, 0, stream);
+    return wc_run(c, d_pcm, MELSPEC_PCM_F32, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_rows, MELSPEC_OUT_F32, h_rows_offsets, true, d_clip_max, 0, stream);
 }
 
-int melspec_whisper_compute_host(melspec_ctx *c, const float *samples, size_t n_samples, size_t pad_to, float *out, size_t out_capacity_floats, int mel_major,
-                                 size_t *n_frames) {
+int melspec_whisper_compute_uniform_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips,
+                                              uint64_t pad_to, void *d_out, int out_dtype, int mel_major, void *stream) {
+    return wc_run(c, d_pcm, pcm_dtype, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_out, out_dtype, nullptr, false, nullptr, mel_major, stream);
+}
+int melspec_whisper_compute_ragged_device_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                             uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype, const uint64_t *h_out_offsets, int mel_major, void *stream) {
+    return wc_run(c, d_pcm, pcm_dtype, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_out, out_dtype, h_out_offsets, false, nullptr, mel_major, stream);
+}
+int melspec_whisper_compute_uniform_device_split_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len, uint32_t n_clips,
+                                                    uint64_t pad_to, void *d_rows, int out_dtype, float *d_clip_max, void *stream) {
+    return wc_run(c, d_pcm, pcm_dtype, false, nullptr, nullptr, clip_stride, clip_len, n_clips, pad_to, d_rows, out_dtype, nullptr, true, d_clip_max, 0, stream);
+}
+int melspec_whisper_compute_ragged_device_split_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *h_offsets, const uint64_t *h_lengths,
+                                                   uint32_t n_clips, uint64_t pad_to, void *d_rows, int out_dtype, const uint64_t *h_rows_offsets, float *d_clip_max,
+                                                   void *stream) {
+    return wc_run(c, d_pcm, pcm_dtype, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_rows, out_dtype, h_rows_offsets, true, d_clip_max, 0, stream);
+}
+
+}  // extern "C"
+
+namespace {
+// one clip from host memory: the bytes of the call's own types cross the bus
+int wc_host(melspec_ctx *c, const void *samples, int pcm_dtype, size_t n_samples, size_t pad_to, void *out, int out_dtype, size_t out_capacity_elems, int mel_major,
+            size_t *n_frames) {
     if (n_frames) *n_frames = 0;
     if (!c) return fail(MELSPEC_ERR_INVALID_ARG, "ctx is NULL");
+    int io;
+    if (int rc = io_dtypes(pcm_dtype, out_dtype, io)) return rc;
     if (!wc_supported(c)) return wc_unsupported(c);
     if (!wc_pad_ok(pad_to)) return fail(MELSPEC_ERR_INVALID_ARG, "pad_to must be 0 or at least 400");
     const uint64_t T = wc_num_frames(n_samples, pad_to);
     const uint64_t n_up = pad_to && n_samples > pad_to ? pad_to : n_samples;        // what the call reads of the clip
     if (T && n_up && !samples) return fail(MELSPEC_ERR_INVALID_ARG, "samples/out is NULL");
     static const float nothing[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    const int rc = host_one_clip(c->dev.device, c->wc_h2d, c->wc_d2h, c->stream, n_up ? samples : nothing, n_up ? n_up * sizeof(float) : sizeof(nothing), out,
-                                 out_capacity_floats, T * static_cast<uint64_t>(c->n_mels), sizeof(float), [&](void *d_in, void *d_out) {
-                                     return melspec_whisper_compute_uniform_device(c, static_cast<const float *>(d_in), n_up, n_up, 1, pad_to, static_cast<float *>(d_out),
-                                                                                   mel_major, c->stream);
+    const int rc = host_one_clip(c->dev.device, c->wc_h2d, c->wc_d2h, c->stream, n_up ? samples : nothing, n_up ? n_up * wc_pcm_bytes(pcm_dtype) : sizeof(nothing), out,
+                                 out_capacity_elems, T * static_cast<uint64_t>(c->n_mels), wc_out_bytes(out_dtype), [&](void *d_in, void *d_out) {
+                                     return wc_run(c, d_in, pcm_dtype, false, nullptr, nullptr, n_up, n_up, 1, pad_to, d_out, out_dtype, nullptr, false, nullptr, mel_major,
+                                                   c->stream);
                                  });
     if (!rc && n_frames) *n_frames = static_cast<size_t>(T);
     return rc;
+}
+}  // namespace
+
+extern "C" {
+
+int melspec_whisper_compute_host(melspec_ctx *c, const float *samples, size_t n_samples, size_t pad_to, float *out, size_t out_capacity_floats, int mel_major,
+                                 size_t *n_frames) {
+    return wc_host(c, samples, MELSPEC_PCM_F32, n_samples, pad_to, out, MELSPEC_OUT_F32, out_capacity_floats, mel_major, n_frames);
+}
+int melspec_whisper_compute_host_io(melspec_ctx *c, const void *samples, int pcm_dtype, size_t n_samples, size_t pad_to, void *out, int out_dtype,
+                                    size_t out_capacity_elems, int mel_major, size_t *n_frames) {
+    return wc_host(c, samples, pcm_dtype, n_samples, pad_to, out, out_dtype, out_capacity_elems, mel_major, n_frames);
 }
 
 }  // extern "C"

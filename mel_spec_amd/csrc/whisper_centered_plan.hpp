@@ -1,8 +1,9 @@
 // whisper_centered_plan.hpp -- the host side of the centred Whisper features (melspec_whisper_*, whisper_centered.hip) that is arithmetic
 // only: the frame count of a clip, the class of every frame (interior / edge / silent), the interior of a batch as a plain ragged batch for
 // the existing planners, the list of edge frames, the per-clip records of the fill / finalise passes, and the checks of the calls'
-// arguments in their order.  Nothing from HIP in here: tests/cpp/whisper_centered_host.cpp builds it on the host, with and without
-// sanitizers.
+// arguments in their order; for the calls with int16 PCM in / f16, bf16 out (melspec_whisper_*_io) the element sizes, the alignment rule
+// and the 16-byte store rule of the finalise pass.  Nothing from HIP in here: tests/cpp/whisper_centered_host.cpp and
+// tests/cpp/whisper_centered_io_host.cpp build it on the host, with and without sanitizers.
 //
 // A clip x of n samples under pad_to (0: as it is) is the signal s = x[:pad_to] + zeros up to pad_to, P = len(s) samples, of which the
 // first n_eff = min(n, P) are the caller's.  T = P / 160 frames (0 when P < 400); frame t is r[160 t .. 160 t + 400) of
@@ -146,6 +147,38 @@ inline WcArgs wc_args(bool have_ctx, bool supported, uint64_t pad_to, bool ragge
     if (!pcm || !rows) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "device pointer is NULL"};
     if (split && !clip_max) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "d_clip_max is NULL"};
     return {kWcGo, MELSPEC_OK, nullptr};
+}
+
+// ---- 16-bit ends (melspec_whisper_*_io): int16 PCM in, f16 / bf16 out --------------------------------------------------------------------
+// Every offset, stride and length above counts ELEMENTS of the call's sample / row type, so the plans do not change; what is new is the
+// size of an element, the alignment a device pointer needs, and when a mel-major tile of the finalise pass may leave as 16-byte stores.
+constexpr bool wc_pcm_known(int t) { return t == MELSPEC_PCM_F32 || t == MELSPEC_PCM_S16; }
+constexpr bool wc_out_known(int t) { return t == MELSPEC_OUT_F32 || t == MELSPEC_OUT_F16 || t == MELSPEC_OUT_BF16; }
+constexpr size_t wc_pcm_bytes(int t) { return t == MELSPEC_PCM_S16 ? 2 : 4; }
+constexpr size_t wc_out_bytes(int t) { return t == MELSPEC_OUT_F32 ? 4 : 2; }
+// natural alignment of the element types, nothing more: a clip may start at an odd int16 sample, an output at an odd 16-bit element
+inline bool wc_io_misaligned(const void *pcm, int pcm_dtype, const void *dst, int out_dtype) {
+    return (reinterpret_cast<uintptr_t>(pcm) & (wc_pcm_bytes(pcm_dtype) - 1)) != 0 || (reinterpret_cast<uintptr_t>(dst) & (wc_out_bytes(out_dtype) - 1)) != 0;
+}
+// A full mel-major tile of clip (T frames, output at element out_off of the array at address out_addr) leaves as 16-byte stores of
+// 16 / elem_bytes values: piece q of mel row m starts at element out_off + m T + 64 tile + (16 / elem_bytes) q, a multiple of
+// 16 / elem_bytes when T and out_off are, on a 16-byte aligned base.  Anything else goes element by element -- no wider store ever goes
+// to an address whose alignment is not proven here.
+constexpr bool wc_wide_ok(uint64_t T, uint64_t out_off, uintptr_t out_addr, size_t elem_bytes) {
+    return ((T | out_off) & (16 / elem_bytes - 1)) == 0 && (out_addr & 15) == 0;
+}
+// wc_args with the dtype codes in front (right after the NULL context) and the alignment of the device pointers behind their NULL checks;
+// (F32, F32) is wc_args itself
+inline WcArgs wc_args_io(bool have_ctx, bool supported, int pcm_dtype, int out_dtype, uint64_t pad_to, bool ragged, uint32_t n_clips, const void *h_offsets,
+                         const void *h_lengths, uint64_t clip_stride, uint64_t clip_len, uint64_t total_frames, const void *pcm, const void *rows, bool split,
+                         const void *clip_max) {
+    if (!have_ctx) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "ctx is NULL"};
+    if (!wc_pcm_known(pcm_dtype)) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16"};
+    if (!wc_out_known(out_dtype)) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16"};
+    const WcArgs a = wc_args(have_ctx, supported, pad_to, ragged, n_clips, h_offsets, h_lengths, clip_stride, clip_len, total_frames, pcm, rows, split, clip_max);
+    if (a.verdict == kWcGo && (pcm_dtype != MELSPEC_PCM_F32 || out_dtype != MELSPEC_OUT_F32) && wc_io_misaligned(pcm, pcm_dtype, rows, out_dtype))
+        return {kWcFail, MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type"};
+    return a;
 }
 
 }  // namespace host

@@ -72,16 +72,35 @@ struct Six64Layout {
 static_assert(Six64Layout::slice_doubles() * 2 >= SixLayout::kPmaxOff + kSixFrames * SixLayout::kPmaxStride, "the f32 power rows and maxima alias the head of the slice");
 
 // ---- phase 1: window (f64), DFT-20 over n1 of column t, twiddle W_200^{t k1}: the twenty exchange values of this lane ---------------------
-template <class In>
+// RAW_FIRST (the raw kernels of the centred Whisper features, whisper_centered_io_kernels.hpp; no effect on float samples): the twenty
+// int16 pairs are loaded as they are and converted behind the scheduling barrier.  With the conversion in front of it (load2_unaligned's
+// int16 form) the default strategy reuses one register for load and conversion: load, s_waitcnt vmcnt(0), convert, twenty times per unit --
+// the (S16, .) raw kernels ran at 1.5 x the time of the float ones (profiles/whisper_centered_io.txt).  The values are the same.
+template <class In, bool RAW_FIRST = false>
 MS_DEV void six64_phase1(int fl, int t, bool active, int hop, const double *MS_RESTRICT tb, const In *gsrc /* unit's first sample */, cd (&x)[20]) {
     if (!active) return;
     const In *s = gsrc + fl * hop + 2 * t;
     f2 sv[20];
+#if defined(__HIPCC__)
+    if constexpr (RAW_FIRST && std::is_same_v<In, int16_t>) {
+        typedef short s2u __attribute__((ext_vector_type(2), aligned(2)));          // load2_unaligned's 4-byte load from a 2-byte aligned address
+        s2u raw[20];
 #pragma unroll
-    for (int n1 = 0; n1 < 20; ++n1) sv[n1] = load2_unaligned(s + 20 * n1);
+        for (int n1 = 0; n1 < 20; ++n1) raw[n1] = *reinterpret_cast<const s2u *>(s + 20 * n1);
 #if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_sched_barrier(MS_SCHED_LOADS_FIRST);        // six_phase1 (whisper_six.hpp) says why
+        __builtin_amdgcn_sched_barrier(MS_SCHED_LOADS_FIRST);
 #endif
+#pragma unroll
+        for (int n1 = 0; n1 < 20; ++n1) sv[n1] = f2{pcm_value(static_cast<int16_t>(raw[n1].x)), pcm_value(static_cast<int16_t>(raw[n1].y))};
+    } else
+#endif
+    {
+#pragma unroll
+        for (int n1 = 0; n1 < 20; ++n1) sv[n1] = load2_unaligned(s + 20 * n1);
+#if defined(__HIP_DEVICE_COMPILE__)
+        __builtin_amdgcn_sched_barrier(MS_SCHED_LOADS_FIRST);        // six_phase1 (whisper_six.hpp) says why
+#endif
+    }
     const double *w = tb + Six64Blob::kWin + t * Six64Blob::kWinStride;
 #pragma unroll
     for (int n1 = 0; n1 < 20; ++n1) {
@@ -175,7 +194,7 @@ MS_DEV void six64_phase2(int fl, int j, bool active, const double *MS_RESTRICT t
 // kernel's loop body and handed to the step functions one `if (active)` at a time they are phi nodes of the unit loop -- for the lanes
 // without a frame "the value of the previous iteration" -- and 160 VGPRs stay live around the whole loop (the first build spilled 290).
 // LDS operations of a wave execute in program order, divergent or not; the wave barriers only pin the compiler's order.
-template <class In>
+template <class In, bool RAW_FIRST = false>
 MS_DEV void six64_phases12(int fl, int j, bool active, int rofs, int hop, const double *MS_RESTRICT tb, const In *gsrc, double *rows, float *slice) {
     if (!active) return;
     // 16-bit PCM: the lane's frame offsets (fl * hop as a 64-bit element offset ...) are made products of THIS unit.  As loop invariants they
@@ -185,7 +204,7 @@ MS_DEV void six64_phases12(int fl, int j, bool active, int rofs, int hop, const 
     cd u[10], v[10];
     {
         cd x[20];
-        six64_phase1(fl, j, true, hop, tb, gsrc, x);
+        six64_phase1<In, RAW_FIRST>(fl, j, true, hop, tb, gsrc, x);
         six64_store_half(fl, j, true, 0, x, rows);
         __builtin_amdgcn_wave_barrier();
 #ifndef MELSPEC_NO_PRIO

@@ -1006,6 +1006,93 @@ def whisper_split(mel: HipMelSpectrogram, clips, pad_to: int = 480000):
     return _whisper_batch(mel, clips, pad_to, False, True)
 
 
+# ---- ... with int16 PCM in / f16, bf16 out (melspec_whisper_*_io): pcm_dtype / out_dtype are PCM_* / OUT_*, every offset, stride and
+# length counts elements of those types
+def supports_whisper_io(mel: HipMelSpectrogram, pcm_dtype: int, out_dtype: int) -> bool:
+    return bool(lib().melspec_whisper_supports_io(mel._h, pcm_dtype, out_dtype))
+
+
+def whisper_uniform_device_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_out: int, out_dtype: int,
+                              pad_to: int = 480000, mel_major: bool = True, stream: int = 0) -> None:
+    _check(lib().melspec_whisper_compute_uniform_device_io(mel._h, C.c_void_p(d_pcm), pcm_dtype, clip_stride, clip_len, n_clips, pad_to, C.c_void_p(d_out), out_dtype,
+                                                           1 if mel_major else 0, C.c_void_p(stream)))
+
+
+def whisper_ragged_device_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, offsets, lengths, d_out: int, out_dtype: int, pad_to: int = 480000,
+                             out_offsets=None, mel_major: bool = True, stream: int = 0) -> None:
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, out_offsets)
+    _check(lib().melspec_whisper_compute_ragged_device_io(mel._h, C.c_void_p(d_pcm), pcm_dtype, p_off, p_len, tabs[0].shape[0], pad_to, C.c_void_p(d_out), out_dtype,
+                                                          p_out, 1 if mel_major else 0, C.c_void_p(stream)))
+
+
+def whisper_uniform_device_split_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, clip_stride: int, clip_len: int, n_clips: int, d_rows: int, out_dtype: int,
+                                    d_clip_max: int, pad_to: int = 480000, stream: int = 0) -> None:
+    """Raw log10 rows [T][n_mels] per clip in out_dtype and the clips' maxima in f32 (taken over the f32 values before rounding)."""
+    _check(lib().melspec_whisper_compute_uniform_device_split_io(mel._h, C.c_void_p(d_pcm), pcm_dtype, clip_stride, clip_len, n_clips, pad_to, C.c_void_p(d_rows),
+                                                                 out_dtype, C.c_void_p(d_clip_max), C.c_void_p(stream)))
+
+
+def whisper_ragged_device_split_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, offsets, lengths, d_rows: int, out_dtype: int, d_clip_max: int,
+                                   pad_to: int = 480000, rows_offsets=None, stream: int = 0) -> None:
+    tabs, (p_off, p_len, p_out) = _u64_tables(offsets, lengths, rows_offsets)
+    _check(lib().melspec_whisper_compute_ragged_device_split_io(mel._h, C.c_void_p(d_pcm), pcm_dtype, p_off, p_len, tabs[0].shape[0], pad_to, C.c_void_p(d_rows),
+                                                                out_dtype, p_out, C.c_void_p(d_clip_max), C.c_void_p(stream)))
+
+
+def whisper_features_io(mel: HipMelSpectrogram, samples, pad_to: int = 480000, mel_major: bool = True, out="f16") -> np.ndarray:
+    """whisper_features with 16-bit ends: an np.int16 array is 16-bit PCM (value = sample / 32768, exactly), anything else f32; out "f16"
+    returns np.float16, "bf16" the bfloat16 bit patterns as np.uint16, "f32" np.float32.  The int16 bytes and the 16-bit features are what
+    crosses the bus."""
+    x, pcm = _pcm_clip(samples)
+    code = _out_code(out)
+    T = whisper_num_frames(mel, x.shape[0], pad_to)
+    res = np.empty((mel.n_mels, T) if mel_major else (T, mel.n_mels), _OUT_NUMPY[code])
+    nf = C.c_size_t(0)
+    _check(lib().melspec_whisper_compute_host_io(mel._h, x.ctypes.data_as(C.c_void_p) if x.size else None, pcm, x.shape[0], pad_to,
+                                                 res.ctypes.data_as(C.c_void_p) if res.size else None, code, res.size, 1 if mel_major else 0, C.byref(nf)))
+    assert nf.value == T
+    return res
+
+
+def _whisper_batch_io(mel: HipMelSpectrogram, clips, pad_to: int, mel_major: bool, split: bool, out):
+    arrs = [np.asarray(c).reshape(-1) for c in clips]
+    pcm = PCM_S16 if arrs and all(a.dtype == np.int16 for a in arrs) else PCM_F32
+    in_t = np.int16 if pcm == PCM_S16 else np.float32
+    arrs = [np.ascontiguousarray(a, dtype=in_t) for a in arrs]
+    code = _out_code(out)
+    out_t = np.dtype(_OUT_NUMPY[code])
+    n = len(arrs)
+    lens = np.array([a.shape[0] for a in arrs], dtype=np.uint64)
+    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64) if n else np.zeros(0, np.uint64)
+    flat = np.concatenate(arrs) if n and int(lens.sum()) else np.zeros(1, in_t)
+    Ts = [whisper_num_frames(mel, int(k), pad_to) for k in lens]
+    total = sum(Ts) * mel.n_mels
+    d_in, d_out, d_max = DeviceBuffer(max(flat.nbytes, 16)), DeviceBuffer(max(total * out_t.itemsize, 16)), DeviceBuffer(max(n, 1) * 4)
+    try:
+        d_in.upload(flat)
+        if split:
+            whisper_ragged_device_split_io(mel, d_in.ptr, pcm, offs, lens, d_out.ptr, code, d_max.ptr, pad_to)
+        else:
+            whisper_ragged_device_io(mel, d_in.ptr, pcm, offs, lens, d_out.ptr, code, pad_to, None, mel_major)
+        mel.synchronize()
+        res = d_out.download((max(total, 1),), out_t)[:total]
+        g = d_max.download((n,)) if split and n else np.zeros(0, np.float32)
+    finally:
+        d_in.free(); d_out.free(); d_max.free()
+    shapes = [(mel.n_mels, T) if (mel_major and not split) else (T, mel.n_mels) for T in Ts]
+    return _split(res, shapes), g
+
+
+def whisper_features_batch_io(mel: HipMelSpectrogram, clips, pad_to: int = 480000, mel_major: bool = True, out="f16") -> list:
+    """whisper_features_batch with 16-bit ends: clips all np.int16 = 16-bit PCM, otherwise f32; the arrays are of `out`'s type (bf16: bit patterns)."""
+    return _whisper_batch_io(mel, clips, pad_to, mel_major, False, out)[0]
+
+
+def whisper_split_io(mel: HipMelSpectrogram, clips, pad_to: int = 480000, out="f16"):
+    """whisper_split with 16-bit ends: (list of raw log10 rows [T_i, n_mels] of `out`'s type, the clips' maxima [n_clips] in f32)."""
+    return _whisper_batch_io(mel, clips, pad_to, False, True, out)
+
+
 class SparseMelFilterbank:
     """SparseMelFilterbank (src/mel.rs:40-168) + log_mel_spectrogram / norm_mel / norm_mel_vec (:436-469) on the GPU (melspec_bank_*)."""
 
