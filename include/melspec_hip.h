@@ -198,7 +198,8 @@ int melspec_mel_from_stft_host(melspec_ctx *ctx, const void *spec, int dtype, in
  * The frames that reflect or straddle the end of the samples (a handful per clip) are computed in f64 whatever the mode.
  * melspec_whisper_kernel_name names the kernel of the current mode.
  * int16 PCM in and f16 / bf16 out: the melspec_whisper_*_io calls in the 16-bit section below.
- * NOT covered, left for later: the device-resident clip table (_desc); the sharded object; the stream bank.
+ * A clip table in device memory: the melspec_whisper_compute_ragged_device_desc calls behind the 16-bit section below.
+ * NOT covered: a device-resident clip table with pad_to == 0 (the _desc calls need a fixed width); the sharded object; the stream bank.
  *
  * The device calls are stream-ordered and asynchronous (stream NULL: the context's), they do not synchronise with the host and allocate
  * nothing of the caller's; the scratch of the normalised calls (raw rows, one maximum word per clip) is the context's grow-only scratch
@@ -337,7 +338,7 @@ int melspec_compute_host_io(melspec_ctx *ctx, const void *samples, int pcm_dtype
  * (F32, F32) is the f32 call: same kernels, same bits.  Every other context returns MELSPEC_ERR_UNSUPPORTED and leaves its output untouched.
  * Statuses: an unknown dtype code is MELSPEC_ERR_INVALID_ARG, checked right after the NULL context; a d_pcm, d_out or d_rows that is not
  * aligned to its element type is MELSPEC_ERR_INVALID_ARG, checked with the device pointers; everything else is the f32 calls' order.
- * NOT covered: the device-resident clip table (_desc); the sharded object; the stream bank. */
+ * NOT covered: a device-resident clip table with pad_to == 0 (the _desc calls need a fixed width); the sharded object; the stream bank. */
 int melspec_whisper_supports_io(const melspec_ctx *ctx, int pcm_dtype, int out_dtype);
 int melspec_whisper_compute_uniform_device_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, uint64_t clip_stride, uint64_t clip_len,
                                               uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype, int mel_major, void *stream);
@@ -353,6 +354,37 @@ int melspec_whisper_compute_ragged_device_split_io(melspec_ctx *ctx, const void 
 /* One clip from host memory: the int16 bytes are what crosses the bus, and so are the 16-bit features.  out_capacity_elems >= T * n_mels. */
 int melspec_whisper_compute_host_io(melspec_ctx *ctx, const void *samples, int pcm_dtype, size_t n_samples, size_t pad_to, void *out,
                                     int out_dtype, size_t out_capacity_elems, int mel_major, size_t *n_frames);
+
+/* ---- the centred Whisper features from a clip table in device memory ----------------------------------------------------------------
+ * The four ragged calls above with every h_ table replaced by a device array: d_offsets / d_lengths [n_clips] count samples (elements of
+ * the PCM type), d_out_offsets / d_rows_offsets count output elements (NULL: packed in clip order).  A kernel on `stream` reads them and
+ * builds the plan -- a VAD or segmenter on the GPU hands its segment table over without a copy to the host.  The host never reads a table
+ * and never waits for the call's stream; the tables are read in stream order and must stay valid until the call's work has run.  The
+ * context's plan and scratch buffers are used in stream order: a call on another stream than the context's previous call first waits for
+ * that previous stream, as every call that uses the context's scratch does.  The result is,
+ * bit for bit, what the host-table call writes for the same tables: every mode, bank, layout and dtype pair, steps 1 - 6 above,
+ * element-counted offsets and natural alignment unchanged.
+ * pad_to must be at least 400 (0 is MELSPEC_ERR_INVALID_ARG: without a fixed width the frame count of a clip is known only on the
+ * device): every clip has T = pad_to / 160 frames, so the output holds n_clips * T * n_mels elements and the call needs no bound of the
+ * caller's.  A length above pad_to is trimmed, a length of 0 is an all-silent clip; no length is rejected and no sample at or past
+ * min(length, pad_to) of a clip is read.
+ * Statuses, in this order: NULL context; (_io) the dtype codes; an unsupported context (MELSPEC_ERR_UNSUPPORTED, the contexts of
+ * melspec_whisper_supports); pad_to; n_clips == 0 (OK, nothing queued); NULL d_offsets / d_lengths; NULL d_pcm / destination; (split)
+ * NULL d_clip_max; (_io) alignment to the element type; more than 0xffffffff / 5 clips (MELSPEC_ERR_INVALID_ARG).  A refused call queues
+ * nothing and writes nothing.  Growing the context's scratch may allocate; a second call of the same size allocates nothing. */
+int melspec_whisper_supports_desc(const melspec_ctx *ctx);
+int melspec_whisper_compute_ragged_device_desc(melspec_ctx *ctx, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths,
+                                               uint32_t n_clips, uint64_t pad_to, float *d_out, const uint64_t *d_out_offsets, int mel_major,
+                                               void *stream);
+int melspec_whisper_compute_ragged_device_desc_split(melspec_ctx *ctx, const float *d_pcm, const uint64_t *d_offsets,
+                                                     const uint64_t *d_lengths, uint32_t n_clips, uint64_t pad_to, float *d_rows,
+                                                     const uint64_t *d_rows_offsets, float *d_clip_max, void *stream);
+int melspec_whisper_compute_ragged_device_desc_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, const uint64_t *d_offsets,
+                                                  const uint64_t *d_lengths, uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype,
+                                                  const uint64_t *d_out_offsets, int mel_major, void *stream);
+int melspec_whisper_compute_ragged_device_desc_split_io(melspec_ctx *ctx, const void *d_pcm, int pcm_dtype, const uint64_t *d_offsets,
+                                                        const uint64_t *d_lengths, uint32_t n_clips, uint64_t pad_to, void *d_rows,
+                                                        int out_dtype, const uint64_t *d_rows_offsets, float *d_clip_max, void *stream);
 
 /* Benchmark helper (the reference's #[ignore] Instant-timed benches, src/cuda.rs:547-613): runs
  * `warmup` untimed and `iters` timed melspec_compute_uniform_device calls on the context's own

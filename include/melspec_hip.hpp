@@ -179,6 +179,29 @@ public:
         detail::check(melspec_whisper_compute_ragged_device_split(ctx_, d_pcm, offsets.data(), lengths.data(), static_cast<std::uint32_t>(offsets.size()), pad_to,
                                                                   d_rows, rows_offsets, d_clip_max, stream), false);
     }
+    // the ragged calls with their clip table in device memory (melspec_whisper_compute_ragged_device_desc*): u64 offsets / lengths / output offsets
+    // read by a planner kernel on `stream`; pad_to >= 400; the bits of the host-table calls.  The _io forms take MELSPEC_PCM_* / MELSPEC_OUT_*.
+    bool supports_whisper_desc() const { return melspec_whisper_supports_desc(ctx_) != 0; }
+    void whisper_ragged_device_desc(const float *d_pcm, const std::uint64_t *d_offsets, const std::uint64_t *d_lengths, std::uint32_t n_clips, float *d_out,
+                                    std::uint64_t pad_to = 480000, const std::uint64_t *d_out_offsets = nullptr, bool mel_major = true, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device_desc(ctx_, d_pcm, d_offsets, d_lengths, n_clips, pad_to, d_out, d_out_offsets, mel_major ? 1 : 0, stream), false);
+    }
+    void whisper_ragged_device_desc_split(const float *d_pcm, const std::uint64_t *d_offsets, const std::uint64_t *d_lengths, std::uint32_t n_clips, float *d_rows,
+                                          float *d_clip_max, std::uint64_t pad_to = 480000, const std::uint64_t *d_rows_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device_desc_split(ctx_, d_pcm, d_offsets, d_lengths, n_clips, pad_to, d_rows, d_rows_offsets, d_clip_max, stream), false);
+    }
+    void whisper_ragged_device_desc_io(const void *d_pcm, int pcm_dtype, const std::uint64_t *d_offsets, const std::uint64_t *d_lengths, std::uint32_t n_clips,
+                                       void *d_out, int out_dtype, std::uint64_t pad_to = 480000, const std::uint64_t *d_out_offsets = nullptr, bool mel_major = true,
+                                       void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device_desc_io(ctx_, d_pcm, pcm_dtype, d_offsets, d_lengths, n_clips, pad_to, d_out, out_dtype, d_out_offsets,
+                                                                    mel_major ? 1 : 0, stream), false);
+    }
+    void whisper_ragged_device_desc_split_io(const void *d_pcm, int pcm_dtype, const std::uint64_t *d_offsets, const std::uint64_t *d_lengths, std::uint32_t n_clips,
+                                             void *d_rows, int out_dtype, float *d_clip_max, std::uint64_t pad_to = 480000,
+                                             const std::uint64_t *d_rows_offsets = nullptr, void *stream = nullptr) {
+        detail::check(melspec_whisper_compute_ragged_device_desc_split_io(ctx_, d_pcm, pcm_dtype, d_offsets, d_lengths, n_clips, pad_to, d_rows, out_dtype, d_rows_offsets,
+                                                                          d_clip_max, stream), false);
+    }
     melspec_ctx *raw() { return ctx_; }
 
 private:

@@ -97,6 +97,11 @@ SIGNATURES = {
     "melspec_whisper_compute_uniform_device_split_io": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp, _vp]),
     "melspec_whisper_compute_ragged_device_split_io": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, C.c_uint64, _vp, C.c_int, _u64p, _vp, _vp]),
     "melspec_whisper_compute_host_io": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, C.c_size_t, _vp, C.c_int, C.c_size_t, C.c_int, C.POINTER(C.c_size_t)]),
+    "melspec_whisper_supports_desc": (C.c_int, [_vp]),
+    "melspec_whisper_compute_ragged_device_desc": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_int, _vp]),
+    "melspec_whisper_compute_ragged_device_desc_split": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "melspec_whisper_compute_ragged_device_desc_io": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp, C.c_int, _vp]),
+    "melspec_whisper_compute_ragged_device_desc_split_io": (C.c_int, [_vp, _vp, C.c_int, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.c_int, _vp, _vp, _vp]),
     "melspec_release_scratch": (C.c_int, [_vp]),
     "melspec_fbank_release_scratch": (C.c_int, [_vp]),
     "melspec_blm_release_scratch": (C.c_int, [_vp]),

@@ -487,17 +487,23 @@ constexpr unsigned long long kAutoMinFrames = 256;
 constexpr unsigned long long kStatFromGated = 1ull << 39;
 
 // Scratch of the centred Whisper features (whisper_centered.hip), grow-only, used in stream order: the raw rows and the clip-maximum words of
-// the normalised calls, the gathered samples of the edge frames, the ring its tables travel through
+// the normalised calls, the gathered samples of the edge frames, the ring its tables travel through; for the _desc calls the plan that
+// wc_plan_desc_kernel writes (dtab) and the interior's plan that plan_ragged_device_kernel makes of it (dplan)
 struct WcScratch {
     StreamBuf rows, slots, edge_pcm;
     RaggedScratch ring;
-    void release() { rows.release(); slots.release(); edge_pcm.release(); ring.release(); }
+    DevicePlan dtab, dplan;
+    void release() { rows.release(); slots.release(); edge_pcm.release(); ring.release(); dtab.release(); dplan.release(); }
     // `synced`: a stream the caller has just synchronised
     int release_after(hipStream_t synced) {
         int rc = rows.release_after(synced);
         if (!rc) rc = slots.release_after(synced);
         if (!rc) rc = edge_pcm.release_after(synced);
         ring.release();
+        for (DevicePlan *d : {&dtab, &dplan}) {
+            if (!rc && d->used && d->last != synced && hipStreamSynchronize(d->last) != hipSuccess) rc = MELSPEC_ERR_INTERNAL;
+            d->release();
+        }
         return rc;
     }
 };

@@ -6,8 +6,12 @@
 // One call is, on its stream:  the tables' upload (the interior's plan through plan_ragged, everything else in one slot of the feature's
 // own ring) -> wc_prepare_kernel (maximum words, edge samples) -> the raw kernel on the interior -> the f64 raw kernel on the edge frames
 // -> wc_finalize_kernel (normalised calls) or wc_fill_kernel + wc_clip_max_kernel (split calls).
+// With the clip table in device memory (the _desc calls, wc_run_desc):  wc_plan_desc_kernel (whisper_desc_kernels.hpp) -> wc_prepare_desc_kernel
+// -> plan_ragged_device_kernel + the raw kernel on the interior -> the f64 raw kernel on the edge frames -> the same last passes; nothing is
+// uploaded and the launches are sized for the most a table of n_clips clips can ask for.
 #include "host_common.hpp"
 #include "whisper_centered_io_kernels.hpp"
+#include "whisper_desc_kernels.hpp"
 
 namespace melspec {
 extern template __global__ void whisper400_six_runs_raw_kernel<kSixMaxSlots, LensSix80>(const WcRawParams);      // whisper_centered_runs.hip
@@ -21,6 +25,9 @@ template __global__ void wc_finalize_kernel<float>(const host::WcRecord *, const
 MS_IO_COMBOS(MS_IO_EXTERN)
 #undef MS_IO_EXTERN
 MS_WC_IO_SMALL(extern template __global__ void)
+// the clip table in device memory (the _desc calls): the gather that reads its count from the plan
+template __global__ void wc_prepare_desc_kernel<float>(const float *, const host::WcEdge *, const uint64_t *, uint32_t, float *, int *, uint32_t);
+template __global__ void wc_prepare_desc_kernel<io_s16>(const io_s16 *, const host::WcEdge *, const uint64_t *, uint32_t, float *, int *, uint32_t);
 
 __global__ __launch_bounds__(256) void wc_clip_max_kernel(int *slots, uint32_t n) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -242,6 +249,91 @@ int wc_run(melspec_ctx *c, const void *d_pcm, int pcm_dtype, bool ragged, const 
     return done(MELSPEC_OK);
 }
 
+// The same batch with its tables in device memory (the _desc calls): d_offsets / d_lengths [n_clips] and the optional dst_offsets are read
+// by wc_plan_desc_kernel on the stream; the host reads none of them and waits for nothing.  pad_to >= 400 fixes T, so the outputs' sizes,
+// the packed offsets and every scratch size are the host's; the classes of the frames are not, so the launches are sized for the most
+// there can be -- T - 2 interior frames and five edge frames per clip, the true counts at BatchDesc::d_n_units -- and the fill pass and
+// the interior launch run whatever the table holds.  Kernel choice, maximum words and the f64 edge launch: wc_run's.
+int wc_run_desc(melspec_ctx *c, bool io, const void *d_pcm, int pcm_dtype, const uint64_t *d_offsets, const uint64_t *d_lengths, uint32_t n_clips, uint64_t pad_to,
+                void *d_dst, int out_dtype, const uint64_t *d_dst_offsets, bool split, float *d_clip_max, int mel_major, void *stream) {
+    const WcArgs a = wc_args_desc_io(c != nullptr, c && wc_supported(c), io, pcm_dtype, out_dtype, pad_to, n_clips, d_offsets, d_lengths, d_pcm, d_dst, split, d_clip_max);
+    if (a.verdict == kWcFail) return a.msg ? fail(a.status, a.msg) : wc_unsupported(c);
+    if (a.verdict == kWcDone) return MELSPEC_OK;
+    HIP_TRY(hipSetDevice(c->dev.device));
+    hipStream_t s = stream ? static_cast<hipStream_t>(stream) : c->stream;
+    const int nm = c->n_mels;
+    const uint64_t T = pad_to / kWcHop;
+    const uint32_t cap = static_cast<uint32_t>(wc_desc_cap(n_clips));
+    int rc;
+    void *d_rows = d_dst;
+    const int rows_dtype = split ? out_dtype : MELSPEC_OUT_F32;
+    const int io_interior = pcm_dtype | rows_dtype << 4, io_edge = MELSPEC_PCM_F32 | rows_dtype << 4;
+    int *d_slots = reinterpret_cast<int *>(d_clip_max);
+    if (!split) {
+        if ((rc = c->wc.rows.ensure(static_cast<size_t>(n_clips) * T * nm * sizeof(float), s))) return rc;
+        if ((rc = c->wc.slots.ensure(static_cast<size_t>(n_clips) * sizeof(int), s))) return rc;
+        d_rows = c->wc.rows.p();
+        d_slots = static_cast<int *>(c->wc.slots.p());
+    }
+    if ((rc = c->wc.edge_pcm.ensure((static_cast<size_t>(cap) + 1) * kWcFft * sizeof(float), s))) return rc;
+    float *d_edge_pcm = static_cast<float *>(c->wc.edge_pcm.p());
+
+    // the plan: DevicePlan's rule -- in stream order, a call on another stream first waits for the stream that used the buffer last
+    DevicePlan &dp = c->wc.dtab;
+    const size_t bytes = wc_desc_bytes(n_clips);
+    if (dp.used && dp.last != s) HIP_TRY(hipStreamSynchronize(dp.last));
+    if (bytes > dp.buf.cap && dp.used) HIP_TRY(hipStreamSynchronize(dp.last));
+    if ((rc = dp.buf.ensure(bytes))) return rc;
+    dp.used = true; dp.last = s;
+    WcPlanDescParams q{};
+    q.in.off = d_offsets; q.in.len = d_lengths;
+    q.in.rows_off = split ? d_dst_offsets : nullptr; q.in.out_off = split ? nullptr : d_dst_offsets;
+    q.in.n_clips = n_clips; q.in.n_mels = static_cast<uint32_t>(nm); q.in.pad_to = pad_to;
+    q.plan = dp.buf.p;
+    hipLaunchKernelGGL(wc_plan_desc_kernel, dim3(1), dim3(kWcDescThreads), 0, s, q);
+    HIP_TRY(hipGetLastError());
+    const WcDescTables t = wc_desc_tables(dp.buf.p, n_clips);
+
+    {
+        const dim3 grid(static_cast<unsigned>(std::min<uint64_t>(static_cast<uint64_t>(cap) + (n_clips + 255) / 256, 0x7fffffffull)));          // grid-stride past the limit
+        if (pcm_dtype == MELSPEC_PCM_S16)
+            hipLaunchKernelGGL(wc_prepare_desc_kernel<io_s16>, grid, dim3(256), 0, s, static_cast<const io_s16 *>(d_pcm), t.edges, t.n_edges, cap, d_edge_pcm, d_slots, n_clips);
+        else
+            hipLaunchKernelGGL(wc_prepare_desc_kernel<float>, grid, dim3(256), 0, s, static_cast<const float *>(d_pcm), t.edges, t.n_edges, cap, d_edge_pcm, d_slots, n_clips);
+        HIP_TRY(hipGetLastError());
+    }
+    // the interior: the plan's (offset + 120, length, rows two rows in) through the planner of melspec_compute_ragged_device_desc, into a
+    // buffer of this feature's own
+    const uint64_t bound = wc_desc_interior_bound(n_clips, pad_to);
+    if (bound) {
+        BatchPlan pl;
+        if ((rc = plan_ragged_device(c->wc.dplan, s, static_cast<const float *>(d_pcm), static_cast<float *>(d_rows), t.in_off, t.in_len, t.in_out_off, n_clips, kWcFft, kWcHop,
+                                     static_cast<uint32_t>(nm), kSixFrames, bound, pl)))
+            return rc;
+        if ((rc = wc_f32(c) ? wc_launch32(c, pl.desc, d_slots, s, io_interior) : wc_launch64(c, pl.desc, d_slots, nullptr, s, io_interior))) return rc;
+    }
+    // the edge frames, in f64 whatever the mode: five slots per clip, the true count on the device
+    {
+        BatchDesc d{};
+        d.pcm = d_edge_pcm; d.out = static_cast<float *>(d_rows); d.n_clips = cap; d.n_units = cap; d.frames_per_unit = kSixFrames;
+        d.d_off = t.e_off; d.d_frames = t.e_frames; d.d_out_off = t.e_out_off; d.d_unit_prefix = t.e_prefix;
+        d.d_unit_block = t.e_blk;
+        d.d_n_units = t.n_edges;
+        if ((rc = wc_launch64(c, d, d_slots, t.e_map, s, io_edge))) return rc;
+    }
+    const unsigned tiles = static_cast<unsigned>(std::min<uint64_t>((T + kWcTile - 1) / kWcTile, 65535));
+    if (split) {
+        wc_fill(t.rec, d_rows, out_dtype, nm, dim3(n_clips, tiles), s);
+        if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, "wc_fill_kernel launch failed");
+        hipLaunchKernelGGL(wc_clip_max_kernel, dim3((n_clips + 255) / 256), dim3(256), 0, s, d_slots, n_clips);
+        if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, "wc_clip_max_kernel launch failed");
+    } else {
+        wc_finalize(t.rec, static_cast<const float *>(d_rows), d_slots, d_dst, out_dtype, nm, mel_major ? 1 : 0, dim3(n_clips, tiles), s);
+        if (hipGetLastError() != hipSuccess) return fail(MELSPEC_ERR_INTERNAL, "wc_finalize_kernel launch failed");
+    }
+    return MELSPEC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -297,6 +389,28 @@ int melspec_whisper_compute_ragged_device_split_io(melspec_ctx *c, const void *d
                                                    uint32_t n_clips, uint64_t pad_to, void *d_rows, int out_dtype, const uint64_t *h_rows_offsets, float *d_clip_max,
                                                    void *stream) {
     return wc_run(c, d_pcm, pcm_dtype, true, h_offsets, h_lengths, 0, 0, n_clips, pad_to, d_rows, out_dtype, h_rows_offsets, true, d_clip_max, 0, stream);
+}
+
+// ---- the clip table in device memory ---------------------------------------------------------------------------------------------------------
+int melspec_whisper_supports_desc(const melspec_ctx *c) { return wc_supported(c) ? 1 : 0; }
+
+int melspec_whisper_compute_ragged_device_desc(melspec_ctx *c, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths, uint32_t n_clips,
+                                               uint64_t pad_to, float *d_out, const uint64_t *d_out_offsets, int mel_major, void *stream) {
+    return wc_run_desc(c, false, d_pcm, MELSPEC_PCM_F32, d_offsets, d_lengths, n_clips, pad_to, d_out, MELSPEC_OUT_F32, d_out_offsets, false, nullptr, mel_major, stream);
+}
+int melspec_whisper_compute_ragged_device_desc_split(melspec_ctx *c, const float *d_pcm, const uint64_t *d_offsets, const uint64_t *d_lengths, uint32_t n_clips,
+                                                     uint64_t pad_to, float *d_rows, const uint64_t *d_rows_offsets, float *d_clip_max, void *stream) {
+    return wc_run_desc(c, false, d_pcm, MELSPEC_PCM_F32, d_offsets, d_lengths, n_clips, pad_to, d_rows, MELSPEC_OUT_F32, d_rows_offsets, true, d_clip_max, 0, stream);
+}
+int melspec_whisper_compute_ragged_device_desc_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *d_offsets, const uint64_t *d_lengths,
+                                                  uint32_t n_clips, uint64_t pad_to, void *d_out, int out_dtype, const uint64_t *d_out_offsets, int mel_major,
+                                                  void *stream) {
+    return wc_run_desc(c, true, d_pcm, pcm_dtype, d_offsets, d_lengths, n_clips, pad_to, d_out, out_dtype, d_out_offsets, false, nullptr, mel_major, stream);
+}
+int melspec_whisper_compute_ragged_device_desc_split_io(melspec_ctx *c, const void *d_pcm, int pcm_dtype, const uint64_t *d_offsets, const uint64_t *d_lengths,
+                                                        uint32_t n_clips, uint64_t pad_to, void *d_rows, int out_dtype, const uint64_t *d_rows_offsets,
+                                                        float *d_clip_max, void *stream) {
+    return wc_run_desc(c, true, d_pcm, pcm_dtype, d_offsets, d_lengths, n_clips, pad_to, d_rows, out_dtype, d_rows_offsets, true, d_clip_max, 0, stream);
 }
 
 }  // extern "C"

@@ -2,8 +2,10 @@
 // only: the frame count of a clip, the class of every frame (interior / edge / silent), the interior of a batch as a plain ragged batch for
 // the existing planners, the list of edge frames, the per-clip records of the fill / finalise passes, and the checks of the calls'
 // arguments in their order; for the calls with int16 PCM in / f16, bf16 out (melspec_whisper_*_io) the element sizes, the alignment rule
-// and the 16-byte store rule of the finalise pass.  Nothing from HIP in here: tests/cpp/whisper_centered_host.cpp and
-// tests/cpp/whisper_centered_io_host.cpp build it on the host, with and without sanitizers.
+// and the 16-byte store rule of the finalise pass; for the calls whose clip table lives in device memory (melspec_whisper_*_desc*) the plan
+// buffer's layout and the per-thread functions of the planner kernel.  Nothing from HIP in here but the host-device qualifier:
+// tests/cpp/whisper_centered_host.cpp, tests/cpp/whisper_centered_io_host.cpp and tests/cpp/whisper_desc_plan_host.cpp build it on the
+// host, with and without sanitizers.
 //
 // A clip x of n samples under pad_to (0: as it is) is the signal s = x[:pad_to] + zeros up to pad_to, P = len(s) samples, of which the
 // first n_eff = min(n, P) are the caller's.  T = P / 160 frames (0 when P < 400); frame t is r[160 t .. 160 t + 400) of
@@ -21,6 +23,13 @@
 #include <vector>
 
 #include "../../include/melspec_hip.h"
+
+// the per-clip arithmetic is one text for the host and for the planner / gather kernels of the _desc calls (blm_desc_plan.hpp: MS_BLM_HD)
+#if defined(__HIPCC__)
+#define MS_WC_HD __host__ __device__ inline
+#else
+#define MS_WC_HD inline
+#endif
 
 namespace melspec {
 namespace host {
@@ -40,7 +49,7 @@ struct WcClip {
     uint64_t first_silent;   // frames first_silent .. T - 1 (== T: none)
 };
 
-inline WcClip wc_clip(uint64_t n, uint64_t pad_to) {
+MS_WC_HD WcClip wc_clip(uint64_t n, uint64_t pad_to) {
     WcClip c{};
     c.P = pad_to ? pad_to : n;
     c.n_eff = n < c.P ? n : c.P;
@@ -55,20 +64,30 @@ inline WcClip wc_clip(uint64_t n, uint64_t pad_to) {
     return c;
 }
 inline uint64_t wc_num_frames(uint64_t n, uint64_t pad_to) { return wc_clip(n, pad_to).T; }
-inline WcClass wc_class(const WcClip &c, uint64_t t) {
+MS_WC_HD WcClass wc_class(const WcClip &c, uint64_t t) {
     if (t >= c.first_silent) return kWcSilent;
     if (t >= 2 && t < 2 + c.interior) return kWcInterior;
     return kWcEdge;
 }
-// edge frames of a clip, in frame order; returns their number (<= kWcMaxEdges)
-inline unsigned wc_edges(const WcClip &c, uint64_t (&t_of)[kWcMaxEdges]) {
-    unsigned k = 0;
-    for (uint64_t t = 0; t < 2 && t < c.first_silent; ++t) t_of[k++] = t;
-    for (uint64_t t = 2 + c.interior; t < c.first_silent && k < kWcMaxEdges; ++t) t_of[k++] = t;
-    return k;
+// edge frames of a clip, in frame order: their number (<= kWcMaxEdges) and the frame of the k-th one -- frames 0 and 1 below first_silent,
+// then the frames from 2 + interior up to first_silent
+MS_WC_HD unsigned wc_edge_count(const WcClip &c) {
+    const uint64_t head = c.first_silent < 2 ? c.first_silent : 2;
+    uint64_t tail = c.first_silent > 2 + c.interior ? c.first_silent - (2 + c.interior) : 0;
+    if (tail > kWcMaxEdges - head) tail = kWcMaxEdges - head;
+    return static_cast<unsigned>(head + tail);
+}
+MS_WC_HD uint64_t wc_edge_frame(const WcClip &c, unsigned k) {
+    const uint64_t head = c.first_silent < 2 ? c.first_silent : 2;
+    return k < head ? k : 2 + c.interior + (k - head);
+}
+MS_WC_HD unsigned wc_edges(const WcClip &c, uint64_t (&t_of)[kWcMaxEdges]) {
+    const unsigned n = wc_edge_count(c);
+    for (unsigned k = 0; k < n; ++k) t_of[k] = wc_edge_frame(c, k);
+    return n;
 }
 // sample i (0 .. 399) of frame t: the index into the clip it is read from, or -1: a zero of the extension.  The rule of the gather kernel.
-inline int64_t wc_source_index(const WcClip &c, uint64_t t, unsigned i) {
+MS_WC_HD int64_t wc_source_index(const WcClip &c, uint64_t t, unsigned i) {
     int64_t idx = static_cast<int64_t>(t * kWcHop + i) - static_cast<int64_t>(kWcPad);
     if (idx < 0) idx = -idx;
     if (idx >= static_cast<int64_t>(c.P)) idx = 2 * (static_cast<int64_t>(c.P) - 1) - idx;
@@ -179,6 +198,132 @@ inline WcArgs wc_args_io(bool have_ctx, bool supported, int pcm_dtype, int out_d
     if (a.verdict == kWcGo && (pcm_dtype != MELSPEC_PCM_F32 || out_dtype != MELSPEC_OUT_F32) && wc_io_misaligned(pcm, pcm_dtype, rows, out_dtype))
         return {kWcFail, MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type"};
     return a;
+}
+
+// ---- the clip table in device memory (melspec_whisper_compute_ragged_device_desc*) ---------------------------------------------------------
+// pad_to >= 400 is required, so every clip has T = pad_to / 160 frames and the packed offsets are i * T * n_mels: what the host cannot know
+// is each clip's classes.  One workgroup of kWcDescThreads threads plans the batch (wc_plan_desc_kernel, whisper_desc_kernels.hpp); thread
+// tid owns the clips of wc_desc_slice, counts their edge frames (wc_desc_count), and once the counts in front of it are summed writes
+// its clips' entries (wc_desc_write); the entries that do not depend on the table are written for the whole capacity (wc_desc_fixed).
+// The functions are the kernel's text; tests/cpp/whisper_desc_plan_host.cpp runs them serially for 1024 "threads" against wc_plan.
+//
+// The plan buffer (wc_desc_bytes), every array 8-byte aligned, cap = kWcMaxEdges * n_clips edge slots:
+//   rec [n]                    WcRecord, what the fill / finalise passes read
+//   in_off, in_len, in_out_off [n] u64: the interior as a ragged batch of un-centred frames for plan_ragged_device_kernel -- clip start
+//                              offset + 120, length 400 + 160 (interior - 1) samples or 0, rows two rows in
+//   edges [cap]                WcEdge, compacted in clip order; entries at and past *n_edges are not written and not read
+//   e_off, e_frames, e_out_off [cap], e_prefix [cap + 1], 4 spare words (the look-ahead of locate_unit): the edge launch's batch, one
+//                              "clip" of one frame per edge -- e_off = 400 e, e_frames = 1, e_prefix = e for the whole capacity;
+//                              e_out_off [e] = the frame's row, written for e < *n_edges only
+//   n_edges                    u64, the true count: BatchDesc::d_n_units of the edge launch, the gather kernel's bound
+//   e_blk [cap / 16 + 1]       u32 = 16 k;  e_map [cap] u32: the clip (maximum word) of edge e, written for e < *n_edges only
+constexpr uint32_t kWcDescThreads = 1024;
+constexpr uint32_t kWcDescUnitBlock = 16;                          // kUnitBlock
+constexpr uint32_t kWcDescMaxClips = 0xffffffffu / kWcMaxEdges;    // the edge slots are counted in 32 bits
+
+struct WcDescIn {
+    const uint64_t *off, *len;              // the caller's tables
+    const uint64_t *rows_off, *out_off;     // either may be null: packed in clip order (wc_plan's arguments)
+    uint32_t n_clips, n_mels;
+    uint64_t pad_to;
+};
+struct WcDescTables {
+    WcRecord *rec;
+    uint64_t *in_off, *in_len, *in_out_off;
+    WcEdge *edges;
+    uint64_t *e_off, *e_frames, *e_out_off, *e_prefix, *n_edges;
+    uint32_t *e_blk, *e_map;
+};
+MS_WC_HD uint64_t wc_desc_cap(uint32_t n_clips) { return kWcMaxEdges * static_cast<uint64_t>(n_clips); }
+MS_WC_HD uint64_t wc_desc_blocks(uint32_t n_clips) { return wc_desc_cap(n_clips) / kWcDescUnitBlock + 1; }
+MS_WC_HD size_t wc_desc_bytes(uint32_t n_clips) {
+    const size_t n = n_clips, cap = static_cast<size_t>(wc_desc_cap(n_clips));
+    const size_t b = n * sizeof(WcRecord) + 3 * n * sizeof(uint64_t) + cap * sizeof(WcEdge) + (4 * cap + 1 + 4 + 1) * sizeof(uint64_t) +
+                     (static_cast<size_t>(wc_desc_blocks(n_clips)) + cap) * sizeof(uint32_t);
+    return (b + 15) & ~static_cast<size_t>(15);
+}
+MS_WC_HD WcDescTables wc_desc_tables(void *buf, uint32_t n_clips) {
+    WcDescTables t;
+    const size_t n = n_clips, cap = static_cast<size_t>(wc_desc_cap(n_clips));
+    t.rec = static_cast<WcRecord *>(buf);
+    t.in_off = reinterpret_cast<uint64_t *>(t.rec + n); t.in_len = t.in_off + n; t.in_out_off = t.in_len + n;
+    t.edges = reinterpret_cast<WcEdge *>(t.in_out_off + n);
+    t.e_off = reinterpret_cast<uint64_t *>(t.edges + cap); t.e_frames = t.e_off + cap; t.e_out_off = t.e_frames + cap; t.e_prefix = t.e_out_off + cap;
+    t.n_edges = t.e_prefix + cap + 1 + 4;
+    t.e_blk = reinterpret_cast<uint32_t *>(t.n_edges + 1); t.e_map = t.e_blk + wc_desc_blocks(n_clips);
+    return t;
+}
+// the interior of a clip as a length the un-centred frame count recovers: frames(n) = n < 400 ? 0 : (n - 400) / 160 + 1
+MS_WC_HD uint64_t wc_interior_len(const WcClip &c) { return c.interior ? kWcFft + kWcHop * (c.interior - 1) : 0; }
+// what the host sizes the interior launch from: every clip has at most T - 2 interior frames
+MS_WC_HD uint64_t wc_desc_interior_bound(uint32_t n_clips, uint64_t pad_to) {
+    const uint64_t T = pad_to / kWcHop;
+    return static_cast<uint64_t>(n_clips) * (T > 2 ? T - 2 : 0);
+}
+
+// the clips of thread tid: a contiguous slice, [c0, c1) (tid * per in 32 bits would wrap for n_clips near 2^32)
+MS_WC_HD void wc_desc_slice(uint32_t n_clips, uint32_t tid, uint32_t &c0, uint32_t &c1) {
+    const uint32_t per = n_clips / kWcDescThreads + (n_clips % kWcDescThreads != 0);
+    const uint64_t b0 = static_cast<uint64_t>(tid) * per;
+    c0 = b0 < n_clips ? static_cast<uint32_t>(b0) : n_clips;
+    c1 = b0 + per < n_clips ? static_cast<uint32_t>(b0 + per) : n_clips;
+}
+MS_WC_HD uint64_t wc_desc_count(const WcDescIn &q, uint32_t c0, uint32_t c1) {
+    uint64_t edges = 0;
+    for (uint32_t c = c0; c < c1; ++c) edges += wc_edge_count(wc_clip(q.len[c], q.pad_to));
+    return edges;
+}
+// first_edge: the edge frames of the clips in front of c0
+MS_WC_HD void wc_desc_write(const WcDescIn &q, const WcDescTables &t, uint32_t c0, uint32_t c1, uint64_t first_edge) {
+    const uint64_t nm = q.n_mels;
+    for (uint32_t c = c0; c < c1; ++c) {
+        const uint64_t off = q.off[c];
+        const WcClip k = wc_clip(q.len[c], q.pad_to);
+        const uint64_t cursor = static_cast<uint64_t>(c) * k.T * nm;
+        const uint64_t ro = q.rows_off ? q.rows_off[c] : cursor, oo = q.out_off ? q.out_off[c] : cursor;
+        t.rec[c] = WcRecord{ro, oo, k.T, k.first_silent};
+        t.in_off[c] = off + kWcShift; t.in_len[c] = wc_interior_len(k); t.in_out_off[c] = ro + 2 * nm;
+        const unsigned ne = wc_edge_count(k);
+        for (unsigned j = 0; j < ne; ++j, ++first_edge) {
+            const uint64_t te = wc_edge_frame(k, j);
+            t.edges[first_edge] = WcEdge{off, k.n_eff, k.P, te, ro + te * nm, c};
+            t.e_out_off[first_edge] = ro + te * nm;
+            t.e_map[first_edge] = c;
+        }
+    }
+}
+// the entries that are the same for every table, slots tid, tid + kWcDescThreads, ... of the capacity
+MS_WC_HD void wc_desc_fixed(const WcDescTables &t, uint32_t n_clips, uint32_t tid) {
+    const uint64_t cap = wc_desc_cap(n_clips), blocks = wc_desc_blocks(n_clips);
+    for (uint64_t e = tid; e < cap; e += kWcDescThreads) { t.e_off[e] = e * kWcFft; t.e_frames[e] = 1; t.e_prefix[e] = e; }
+    for (uint64_t e = cap + tid; e < cap + 1 + 4; e += kWcDescThreads) t.e_prefix[e] = cap;
+    for (uint64_t b = tid; b < blocks; b += kWcDescThreads) t.e_blk[b] = static_cast<uint32_t>(b * kWcDescUnitBlock);
+}
+
+// The arguments of the _desc calls, in this order: the context, (io) the dtype codes, its support, pad_to -- which must be a fixed width
+// here --, no clips, the tables, the device pointers, (split) d_clip_max, (io) the alignment to the element type, the clip count.  No
+// verdict depends on the table's contents: the host never reads it.
+inline WcArgs wc_args_desc_io(bool have_ctx, bool supported, bool io, int pcm_dtype, int out_dtype, uint64_t pad_to, uint32_t n_clips, const void *d_offsets,
+                              const void *d_lengths, const void *pcm, const void *dst, bool split, const void *clip_max) {
+    if (!have_ctx) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "ctx is NULL"};
+    if (io && !wc_pcm_known(pcm_dtype)) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "pcm_dtype must be MELSPEC_PCM_F32 or MELSPEC_PCM_S16"};
+    if (io && !wc_out_known(out_dtype)) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "out_dtype must be MELSPEC_OUT_F32, MELSPEC_OUT_F16 or MELSPEC_OUT_BF16"};
+    if (!supported) return {kWcFail, MELSPEC_ERR_UNSUPPORTED, nullptr};
+    if (pad_to == 0)
+        return {kWcFail, MELSPEC_ERR_INVALID_ARG, "pad_to must be at least 400 with a device-resident clip table: without a fixed width the frame counts are known on the device only"};
+    if (pad_to < kWcFft) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "pad_to must be at least 400"};
+    if (n_clips == 0) return {kWcDone, MELSPEC_OK, nullptr};
+    if (!d_offsets || !d_lengths) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "offset/length array is NULL"};
+    if (!pcm || !dst) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "device pointer is NULL"};
+    if (split && !clip_max) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "d_clip_max is NULL"};
+    if (io && (pcm_dtype != MELSPEC_PCM_F32 || out_dtype != MELSPEC_OUT_F32) && wc_io_misaligned(pcm, pcm_dtype, dst, out_dtype))
+        return {kWcFail, MELSPEC_ERR_INVALID_ARG, "device pointer is not aligned to its element type"};
+    if (n_clips > kWcDescMaxClips) return {kWcFail, MELSPEC_ERR_INVALID_ARG, "too many clips for one call"};
+    return {kWcGo, MELSPEC_OK, nullptr};
+}
+inline WcArgs wc_args_desc(bool have_ctx, bool supported, uint64_t pad_to, uint32_t n_clips, const void *d_offsets, const void *d_lengths, const void *pcm,
+                           const void *dst, bool split, const void *clip_max) {
+    return wc_args_desc_io(have_ctx, supported, false, MELSPEC_PCM_F32, MELSPEC_OUT_F32, pad_to, n_clips, d_offsets, d_lengths, pcm, dst, split, clip_max);
 }
 
 }  // namespace host

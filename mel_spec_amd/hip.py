@@ -1039,6 +1039,41 @@ def whisper_ragged_device_split_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype
                                                                 out_dtype, p_out, C.c_void_p(d_clip_max), C.c_void_p(stream)))
 
 
+# ---- ... with the clip table in device memory (melspec_whisper_compute_ragged_device_desc*): d_offsets / d_lengths / the optional output
+# offsets (0 = packed in clip order) are device pointers to u64 arrays of n_clips entries, read by a planner kernel on `stream`; nothing is
+# copied back, nothing waits.  pad_to must be at least 400; the bits are the host-table calls' on the same tables.
+def _dp(p: int):
+    return C.c_void_p(p) if p else None
+
+
+def supports_whisper_desc(mel: HipMelSpectrogram) -> bool:
+    return bool(lib().melspec_whisper_supports_desc(mel._h))
+
+
+def whisper_ragged_device_desc(mel: HipMelSpectrogram, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, pad_to: int = 480000,
+                               d_out_offsets: int = 0, mel_major: bool = True, stream: int = 0) -> None:
+    _check(lib().melspec_whisper_compute_ragged_device_desc(mel._h, _dp(d_pcm), _dp(d_offsets), _dp(d_lengths), n_clips, pad_to, _dp(d_out), _dp(d_out_offsets),
+                                                            1 if mel_major else 0, _dp(stream)))
+
+
+def whisper_ragged_device_desc_split(mel: HipMelSpectrogram, d_pcm: int, d_offsets: int, d_lengths: int, n_clips: int, d_rows: int, d_clip_max: int,
+                                     pad_to: int = 480000, d_rows_offsets: int = 0, stream: int = 0) -> None:
+    _check(lib().melspec_whisper_compute_ragged_device_desc_split(mel._h, _dp(d_pcm), _dp(d_offsets), _dp(d_lengths), n_clips, pad_to, _dp(d_rows), _dp(d_rows_offsets),
+                                                                  _dp(d_clip_max), _dp(stream)))
+
+
+def whisper_ragged_device_desc_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, d_offsets: int, d_lengths: int, n_clips: int, d_out: int, out_dtype: int,
+                                  pad_to: int = 480000, d_out_offsets: int = 0, mel_major: bool = True, stream: int = 0) -> None:
+    _check(lib().melspec_whisper_compute_ragged_device_desc_io(mel._h, _dp(d_pcm), pcm_dtype, _dp(d_offsets), _dp(d_lengths), n_clips, pad_to, _dp(d_out), out_dtype,
+                                                               _dp(d_out_offsets), 1 if mel_major else 0, _dp(stream)))
+
+
+def whisper_ragged_device_desc_split_io(mel: HipMelSpectrogram, d_pcm: int, pcm_dtype: int, d_offsets: int, d_lengths: int, n_clips: int, d_rows: int, out_dtype: int,
+                                        d_clip_max: int, pad_to: int = 480000, d_rows_offsets: int = 0, stream: int = 0) -> None:
+    _check(lib().melspec_whisper_compute_ragged_device_desc_split_io(mel._h, _dp(d_pcm), pcm_dtype, _dp(d_offsets), _dp(d_lengths), n_clips, pad_to, _dp(d_rows),
+                                                                     out_dtype, _dp(d_rows_offsets), _dp(d_clip_max), _dp(stream)))
+
+
 def whisper_features_io(mel: HipMelSpectrogram, samples, pad_to: int = 480000, mel_major: bool = True, out="f16") -> np.ndarray:
     """whisper_features with 16-bit ends: an np.int16 array is 16-bit PCM (value = sample / 32768, exactly), anything else f32; out "f16"
     returns np.float16, "bf16" the bfloat16 bit patterns as np.uint16, "f32" np.float32.  The int16 bytes and the 16-bit features are what

@@ -1265,6 +1265,19 @@ unsafe extern "C" {
                                                    stream: *mut c_void) -> c_int;
     fn melspec_whisper_compute_host(ctx: *mut Ctx, samples: *const f32, n_samples: usize, pad_to: usize, out: *mut f32, out_capacity_floats: usize,
                                     mel_major: c_int, n_frames: *mut usize) -> c_int;
+    // ... with the clip table in device memory (pad_to >= 400)
+    fn melspec_whisper_supports_desc(ctx: *const Ctx) -> c_int;
+    fn melspec_whisper_compute_ragged_device_desc(ctx: *mut Ctx, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
+                                                  pad_to: u64, d_out: *mut f32, d_out_offsets: *const u64, mel_major: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_ragged_device_desc_split(ctx: *mut Ctx, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
+                                                        pad_to: u64, d_rows: *mut f32, d_rows_offsets: *const u64, d_clip_max: *mut f32,
+                                                        stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_ragged_device_desc_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, d_offsets: *const u64, d_lengths: *const u64,
+                                                     n_clips: u32, pad_to: u64, d_out: *mut c_void, out_dtype: c_int, d_out_offsets: *const u64,
+                                                     mel_major: c_int, stream: *mut c_void) -> c_int;
+    fn melspec_whisper_compute_ragged_device_desc_split_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, d_offsets: *const u64,
+                                                           d_lengths: *const u64, n_clips: u32, pad_to: u64, d_rows: *mut c_void, out_dtype: c_int,
+                                                           d_rows_offsets: *const u64, d_clip_max: *mut f32, stream: *mut c_void) -> c_int;
     // int16 PCM in / f16, bf16 rows out
     fn melspec_supports_io(ctx: *const Ctx, pcm_dtype: c_int, out_dtype: c_int) -> c_int;
     fn melspec_compute_uniform_device_io(ctx: *mut Ctx, d_pcm: *const c_void, pcm_dtype: c_int, clip_stride: u64, clip_len: u64, n_clips: u32,
@@ -1480,6 +1493,45 @@ impl HipMelSpectrogram {
         assert_eq!(offsets.len(), lengths.len());
         check(melspec_whisper_compute_ragged_device_split(self.ctx, d_pcm, offsets.as_ptr(), lengths.as_ptr(), offsets.len() as u32, pad_to, d_rows,
                                                           std::ptr::null(), d_clip_max, stream))
+    }
+
+    /// Does this context compute the Whisper features from a clip table in device memory?
+    pub fn supports_whisper_desc(&self) -> bool {
+        unsafe { melspec_whisper_supports_desc(self.ctx) != 0 }
+    }
+
+    /// `whisper_ragged_device` with the u64 tables in device memory, read by a planner kernel on `stream`; `pad_to` at least 400.
+    /// # Safety
+    /// `d_offsets` / `d_lengths` (and `d_out_offsets`, may be null: packed) must be device arrays of `n_clips` entries that stay valid until the
+    /// call's work has run; `d_out` must hold `n_clips * (pad_to / 160) * n_mels` floats (or span the caller's offsets).
+    pub unsafe fn whisper_ragged_device_desc(&mut self, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32, pad_to: u64,
+                                             d_out: *mut f32, d_out_offsets: *const u64, mel_major: bool, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_ragged_device_desc(self.ctx, d_pcm, d_offsets, d_lengths, n_clips, pad_to, d_out, d_out_offsets, mel_major as c_int, stream))
+    }
+
+    /// # Safety
+    /// As `whisper_ragged_device_desc`; `d_clip_max` must hold `n_clips` floats.
+    pub unsafe fn whisper_ragged_device_desc_split(&mut self, d_pcm: *const f32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32, pad_to: u64,
+                                                   d_rows: *mut f32, d_rows_offsets: *const u64, d_clip_max: *mut f32, stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_ragged_device_desc_split(self.ctx, d_pcm, d_offsets, d_lengths, n_clips, pad_to, d_rows, d_rows_offsets, d_clip_max, stream))
+    }
+
+    /// # Safety
+    /// As `whisper_ragged_device_desc`, in elements of `pcm_dtype` (`PCM_*`) and `out_dtype` (`OUT_*`).
+    pub unsafe fn whisper_ragged_device_desc_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
+                                                pad_to: u64, d_out: *mut c_void, out_dtype: i32, d_out_offsets: *const u64, mel_major: bool,
+                                                stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_ragged_device_desc_io(self.ctx, d_pcm, pcm_dtype as c_int, d_offsets, d_lengths, n_clips, pad_to, d_out, out_dtype as c_int,
+                                                            d_out_offsets, mel_major as c_int, stream))
+    }
+
+    /// # Safety
+    /// As `whisper_ragged_device_desc_split`, in elements of `pcm_dtype` and `out_dtype`; `d_clip_max` stays f32.
+    pub unsafe fn whisper_ragged_device_desc_split_io(&mut self, d_pcm: *const c_void, pcm_dtype: i32, d_offsets: *const u64, d_lengths: *const u64, n_clips: u32,
+                                                      pad_to: u64, d_rows: *mut c_void, out_dtype: i32, d_rows_offsets: *const u64, d_clip_max: *mut f32,
+                                                      stream: *mut c_void) -> Result<(), HipError> {
+        check(melspec_whisper_compute_ragged_device_desc_split_io(self.ctx, d_pcm, pcm_dtype as c_int, d_offsets, d_lengths, n_clips, pad_to, d_rows,
+                                                                  out_dtype as c_int, d_rows_offsets, d_clip_max, stream))
     }
 
     /// The kernel the Whisper features run on in the current precision mode.
