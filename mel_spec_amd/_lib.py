@@ -263,6 +263,20 @@ SIGNATURES = {
     "melspec_tga_synchronize": (C.c_int, [_vp]),
 }
 
+# include/melspec_resample.h: the resampler's symbols, a table of their own (SIGNATURES is melspec_hip.h's list, symbol for symbol)
+RESAMPLE_SIGNATURES = {
+    "melspec_resample_geometry": (C.c_int, [C.c_uint32, C.c_uint32, _u32p, _u32p, _u32p, _u32p]),
+    "melspec_resample_taps": (C.c_int, [C.c_uint32, C.c_uint32, _f64p, C.c_size_t]),
+    "melspec_resample_out_len": (C.c_size_t, [C.c_uint32, C.c_uint32, C.c_size_t]),
+    "melspec_resampler_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_uint32, C.c_uint32]),
+    "melspec_resampler_destroy": (None, [_vp]),
+    "melspec_resampler_kernel_name": (C.c_char_p, [_vp]),
+    "melspec_resample_uniform_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, _vp, C.c_uint64, _vp]),
+    "melspec_resample_ragged_device": (C.c_int, [_vp, _vp, C.c_int, _u64p, _u64p, C.c_uint32, _vp, _u64p, _vp]),
+    "melspec_resample_host": (C.c_int, [_vp, _vp, C.c_int, C.c_size_t, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "melspec_resampler_synchronize": (C.c_int, [_vp, _vp]),
+}
+
 _lib = None
 
 
@@ -281,6 +295,12 @@ def lib() -> C.CDLL:
             if older and not hasattr(L, name):
                 continue
             fn = getattr(L, name)   # AttributeError if the ABI lost a symbol
+            fn.restype = res
+            fn.argtypes = args
+        for name, (res, args) in RESAMPLE_SIGNATURES.items():
+            if older and not hasattr(L, name):
+                continue
+            fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args
         _lib = L

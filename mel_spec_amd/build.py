@@ -31,9 +31,10 @@ LAB_LIB_PATH = os.path.join(PKG_DIR, "libmelspec_hip_lab.so")   # -DMELSPEC_LAB:
 # gather, fill and finalise kernels), likewise; the f32 one gets melspec_runs.hip's strategy
 # (csrc/whisper_desc_kernels.hpp -- the planner and the gather of the calls whose clip table lives in device memory -- is part of
 # whisper_centered.hip: new kernels beside the old ones, profiles/whisper_desc_resources.txt)
+# resample.hip: the polyphase resampler in front of the frontends (csrc/resample_kernels.hpp, include/melspec_resample.h), a unit of its own
 SOURCES = ["host_api.hip", "whisper400.hip", "fbank512.hip", "pow2.hip", "aux.hip", "melspec_runs.hip", "melspec_io_runs.hip", "melspec_io64.hip",
            "fbank512_io.hip", "fbank512_kaldi_io.hip", "fbank512_kaldi_split_io.hip", "fbank512_stats.hip", "fbank512_stats_ragged.hip", "fbank512_stats_io.hip", "fbank512_stream.hip", "fbank512_nemo_stream.hip", "stream_banks_io.hip",
-           "whisper_centered.hip", "whisper_centered_runs.hip", "whisper_centered_io.hip", "whisper_centered_io_runs.hip"]
+           "whisper_centered.hip", "whisper_centered_runs.hip", "whisper_centered_io.hip", "whisper_centered_io_runs.hip", "resample.hip"]
 UNIT_FLAGS = {"melspec_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "melspec_io_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
               "whisper_centered_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "whisper_centered_io_runs.hip": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 

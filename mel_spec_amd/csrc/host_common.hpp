@@ -14,6 +14,8 @@
 //   melspec_runs.hip  the run-per-wave f32 Whisper kernels, compiled with their own scheduling strategy
 //   whisper_centered.hip  the centred Whisper features (melspec_whisper_*): raw rows + clip maxima from the six-frame kernels, the finalise pass
 //   whisper_centered_plan.hpp  their frame classes, tables and argument checks (no HIP: host-testable)
+//   resample.hip    the polyphase resampler in front of the frontends (melspec_resample_*, include/melspec_resample.h), an object of its own
+//   resample_plan.hpp  its geometry, tap table, clip table and tiles (no HIP: host-testable)
 #pragma once
 #include <hip/hip_runtime.h>
 
